@@ -12,7 +12,16 @@ are summed once at the end with one RCCL all-reduce, inside the timed region.
 `python bench.py --gpus N` without a launcher spawns the N ranks itself (torch.distributed.run as a child process,
 before anything here touches a GPU) and relays rank 0's line.
 
-ONE JSON line on rank 0 (contract in the task statement), with these extra objects:
+A plain run does only what the headline figure needs: it builds the workload, warms up, times --steps steps, writes
+--dump-outputs if given and prints the line.  `--full` adds everything else below (per-kernel events in the timed region,
+the extra runs, the oracle and reference legs, bench_detail.json).
+
+`--dump-outputs DIR`: the accumulators of the last timed step as float64 .npy files (dbtk_ctx_counts: counts — a fixed,
+seeded sample of the TR k-mers, in OUT.trkmc.ar order — kmc, nmapread, counters; summed over the ranks when N > 1).  Every
+timed step aligns the same resident batch into accumulators reset before the first, so the last step's values are the
+totals divided by --steps (checked to divide exactly).
+
+ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...), with these extra objects under --full:
   roofline      the dominant kernel of the timed region: algorithmic bytes / HIP-event time inside the region
   probe_roofline  the same figures for k_probe, the kernel the north star's 40 % target names
   mixes         N = 1: the all-hit mix (every pair from a locus: k_probe dominates) and the graph-walk mix
@@ -86,7 +95,30 @@ def parse_args(argv=None):
     ap.add_argument("--extra-lanes", action="store_true", default=True, help="also run the timed steps on two overlapped lanes (the library's default outside this bench) and report them as `two_lanes` [on]")
     ap.add_argument("--no-extra-lanes", dest="extra_lanes", action="store_false")
     ap.add_argument("--lib", default=None, help="diagnostic: another build of libdbtk_hip.so (tuning variants)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: per-kernel tables and rooflines, the sustained and two-lane "
+                         "runs, the extra mixes, end to end, the CPU baselines and parity checks, bench_detail.json (the options above that "
+                         "tune those legs take effect only here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; the TR k-mer counts as a fixed, seeded sample)")
     return ap.parse_args(argv)
+
+
+DUMP_COUNTS = 4_000_000  # TR k-mer counts written by --dump-outputs (32 MB as float64): a fixed, seeded sample when there are more
+DUMP_SEED = 20250808
+
+
+def dump_outputs(ctx, steps, out_dir):
+    """The last timed step's results as float64 .npy files (module docstring)."""
+    r = ctx.counts()
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(r["counts"])
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_COUNTS, replace=False)) if n > DUMP_COUNTS else np.arange(n)
+    for name, v in (("counts", r["counts"][idx]), ("kmc", r["kmc"]), ("nmapread", r["nmapread"]), ("counters", r["counters"])):
+        v = v.astype(np.uint64)
+        if (v % np.uint64(steps)).any():
+            raise SystemExit(f"{name}: the accumulators of {steps} timed steps of the same batch are not {steps} equal parts")
+        np.save(os.path.join(out_dir, name + ".npy"), (v // np.uint64(steps)).astype(np.float64))
 
 
 def spawn_ranks(args):
@@ -240,7 +272,7 @@ def _roof(r, formula=None):
     return o
 
 
-def compact_line(out):
+def compact_line(out, detail=True):
     """The ONE line the driver parses (< MAX_LINE characters).  Everything else — per-kernel tables of every mix, path statistics, the
     command line's legs with their stderr lines, every reference run — goes to bench_detail.json."""
     c = {k: _r(out[k]) for k in ("metric", "value", "unit", "n_gpus", "ranks_seen", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -325,7 +357,8 @@ def compact_line(out):
                       "and the drop-in command line reaches cli_first_pass / cli_later_pass (file in /dev/shm, batch loop only)")
         c["end_to_end"] = ce
     c["bench_wall_s"] = _r(out.get("bench_wall_s"), 4)
-    c["detail"] = "bench_detail.json"
+    if detail:
+        c["detail"] = "bench_detail.json"
     line = json.dumps(c, separators=(",", ":"))
     if len(line) >= MAX_LINE:  # never lose the contract's fields to a long note
         for k in ("end_to_end", "mixes"):
@@ -478,13 +511,14 @@ def main():
     log = (lambda *a: print("[bench]", *a, file=sys.stderr, flush=True)) if rank == 0 else (lambda *a: None)
     t_start = time.time()
     solo = world == 1
-    do_mixes = solo and args.mix_reads > 0
+    full = args.full
+    do_mixes = full and solo and args.mix_reads > 0
     do_walk = do_mixes and not args.no_walk
-    do_ref = solo and rank == 0 and args.ref_reads > 0 and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "danbing-tk"))
+    do_ref = full and solo and rank == 0 and args.ref_reads > 0 and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "danbing-tk"))
 
     # ---- workload: RPGG replica per GPU, read shard per rank
     ncpu = os.cpu_count() or 8
-    nth = max(2, ncpu // world)
+    nth = max(2, usable_cpus() // world)  # (the generators' results do not depend on their thread count)
     t0 = time.time()
     syn = pkg.Synth(nloci=args.nloci, k=21, flank=700, seed=20250808, nthreads=nth)
     if do_walk:
@@ -526,6 +560,8 @@ def main():
     g = pkg.Rpgg(dbtk, h)
     params = abi.default_params(ksize=21, n_filter=4, nm_filter=1, cthreshold=45, okam=0)
     ctx = dbtk.context(g, params, device=local_rank)
+    if not full:
+        ctx.timers_enable(False)  # (nothing reads per-kernel times in a plain run)
     hbm_tables = ctx.table_bytes()
     log(f"handle + HBM tables: {g.ntrkmers} TR k-mers, {time.time() - t0:.1f}s; {hbm_tables.get('total', 0) / 1e9:.1f} GB of tables")
     d_seq = torch.from_numpy(seq).to(dev)
@@ -573,23 +609,25 @@ def main():
     ctx.synchronize()
     reduce_counts()  # untimed: RCCL communicator / kernel warm-up (the reduced values are discarded by the reset)
     ctx.reset()
-    ctx.timers_reset()
-    ctx.timers_enable(args.timer_every)  # HIP-event pairs around the kernels of every n-th step of the timed region
-    if os.environ.get("DBTK_NO_TIMERS"):
-        ctx.timers_enable(False)
+    if full:
+        ctx.timers_reset()
+        ctx.timers_enable(args.timer_every)  # HIP-event pairs around the kernels of every n-th step of the timed region
+        if os.environ.get("DBTK_NO_TIMERS"):
+            ctx.timers_enable(False)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     ctx.synchronize()
-    if world > 1:  # per-rank work counters, before the reduce sums them over ranks
+    if full and world > 1:  # per-rank work counters, before the reduce sums them over ranks
         local_ctr = ctx.counters()
     reduce_counts()
     barrier()
     dt = time.perf_counter() - t0
-    ktimes = ctx.kernel_times()      # HIP events recorded inside the timed region, read after it
-    if world == 1:
-        local_ctr = ctx.counters()
+    if full:
+        ktimes = ctx.kernel_times()      # HIP events recorded inside the timed region, read after it
+        if world == 1:
+            local_ctr = ctx.counters()
     per_rank_ms = [dt / args.steps * 1e3]
     if use_dist:
         # every rank's own time for the same K steps (barrier to barrier), so that a first multi-GPU run is diagnosable from its one
@@ -625,24 +663,29 @@ def main():
     total_reads = 2 * npairs * args.steps * world
     value = total_reads / dt
     log(f"timed region: {args.steps} steps, {dt / args.steps * 1e3:.3f} ms/step, {value / 1e9:.2f} G reads/s on {world} GPU(s)")
+    if args.dump_outputs and rank == 0:  # (before anything below runs more batches on this context)
+        dump_outputs(ctx, args.steps, args.dump_outputs)
+        log(f"outputs of the last timed step: {args.dump_outputs}")
 
-    # ---- roofline (this rank): algorithmic bytes of SURVEY.md 8(d) per launch / HIP-event time
-    ctr = local_ctr.astype(np.float64)
-    timed_steps = (args.steps + args.timer_every - 1) // max(args.timer_every, 1) if args.timer_every > 1 else args.steps
-    ps0 = ctx.path_stats()  # (reset with the accumulators after the warm-up: the timed steps' pairs only)
-    table = kernel_table(ktimes, algorithmic_bytes(abi, ctr, ps=ps0), args.steps, timed_steps)
-    dom = max((k for k in table if ":" not in k), key=lambda k: table[k]["avg_ms"] * table[k]["launches"])
-    roof = roofline_of(dom, table)
-    traffic, traffic_src, stale = pmc_traffic(dom, table, ctr[abi.C_BASES] / max(table[dom]["launches"], 1))
-    roof.update(traffic=traffic, traffic_source=traffic_src, traffic_stale=stale, kernels=table)
-    # the contract's probe figure: 12 B per index look-up of kfilter, nothing else, over the probe stage's time; the same stage
-    # priced with the classify / count work the fused kernel also does is roofline.kernels["k_probe"] in the detail file
-    probe_roof = roofline_of("k_probe: look-ups only", table) if "k_probe" in table else None
-    if probe_roof:
-        probe_roof["kernel"] = "k_probe"
+    roof = probe_roof = None
+    if full:
+        # ---- roofline (this rank): algorithmic bytes of SURVEY.md 8(d) per launch / HIP-event time
+        ctr = local_ctr.astype(np.float64)
+        timed_steps = (args.steps + args.timer_every - 1) // max(args.timer_every, 1) if args.timer_every > 1 else args.steps
+        ps0 = ctx.path_stats()  # (reset with the accumulators after the warm-up: the timed steps' pairs only)
+        table = kernel_table(ktimes, algorithmic_bytes(abi, ctr, ps=ps0), args.steps, timed_steps)
+        dom = max((k for k in table if ":" not in k), key=lambda k: table[k]["avg_ms"] * table[k]["launches"])
+        roof = roofline_of(dom, table)
+        traffic, traffic_src, stale = pmc_traffic(dom, table, ctr[abi.C_BASES] / max(table[dom]["launches"], 1))
+        roof.update(traffic=traffic, traffic_source=traffic_src, traffic_stale=stale, kernels=table)
+        # the contract's probe figure: 12 B per index look-up of kfilter, nothing else, over the probe stage's time; the same stage
+        # priced with the classify / count work the fused kernel also does is roofline.kernels["k_probe"] in the detail file
+        probe_roof = roofline_of("k_probe: look-ups only", table) if "k_probe" in table else None
+        if probe_roof:
+            probe_roof["kernel"] = "k_probe"
 
     sustained = None
-    if solo and args.sustain_seconds > 0:
+    if full and solo and args.sustain_seconds > 0:
         ctx.timers_enable(False)
         nsus = max(args.steps, int(np.ceil(args.sustain_seconds / max(dt / args.steps, 1e-6))))
         dts = time_steps(ctx, step, nsus, 0)
@@ -650,7 +693,7 @@ def main():
                          note="the same step back to back for >= --sustain-seconds of wall time, no per-kernel events")
         log(f"sustained: {nsus} steps in {dts:.2f}s = {sustained['value'] / 1e9:.2f} G reads/s")
     two_lanes = None
-    if solo and args.lanes == 1 and args.extra_lanes:
+    if full and solo and args.lanes == 1 and args.extra_lanes:
         os.environ["DBTK_LANES"] = "2"
         ctx2 = dbtk.context(g, params, device=local_rank)
         os.environ["DBTK_LANES"] = "1"
@@ -665,7 +708,7 @@ def main():
     k25_files = 0  # pairs of the k = 25 all-hit FASTA written for the command line's config-4 leg
     dense_checks = []  # per mix: the GPU half of its dense-slice parity check (the oracle half runs with the CPU legs)
     nhit = 0  # pairs of the all-hit FASTA the CLI walk legs read
-    if solo and rank == 0:
+    if full and solo and rank == 0:
         mixes = {}
         only = args.only_mix
         if do_mixes:
@@ -1045,14 +1088,15 @@ def main():
             "roofline": roof, "probe_roofline": probe_roof, "hbm_bytes_tables": hbm_tables, "reduce_check": reduce_check, "sustained": sustained, "mixes": mixes, "end_to_end": e2e, "cpu_baseline": cpu, "parity": parity,
             "two_lanes": two_lanes, "bench_wall_s": time.time() - t_start,
         }
-        line = compact_line(out)
-        detail = os.environ.get("DBTK_BENCH_DETAIL") or os.path.join(ROOT, "bench_detail.json")
-        try:
-            with open(detail, "w") as fh:
-                json.dump(out, fh)
-            log(f"detail (mixes, per-kernel tables, end-to-end legs, reference runs): {detail}")
-        except OSError as e:
-            log(f"could not write {detail}: {e}")
+        line = compact_line(out, detail=full)
+        if full:
+            detail = os.environ.get("DBTK_BENCH_DETAIL") or os.path.join(ROOT, "bench_detail.json")
+            try:
+                with open(detail, "w") as fh:
+                    json.dump(out, fh)
+                log(f"detail (mixes, per-kernel tables, end-to-end legs, reference runs): {detail}")
+            except OSError as e:
+                log(f"could not write {detail}: {e}")
         assert len(line) < MAX_LINE, f"bench line is {len(line)} characters: the driver reads the last 8 000 of stdout"
         print(line, flush=True)
     if use_dist:

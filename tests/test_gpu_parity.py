@@ -724,7 +724,7 @@ def test_bench_collective_path_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port",
            str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--nloci", "3000", "--reads", "400000",
-           "--mix-reads", "0", "--no-e2e", "--ref-reads", "0", "--cpu-seconds", "4", "--parity-pairs", "30000"]
+           "--mix-reads", "0", "--no-e2e", "--ref-reads", "0", "--cpu-seconds", "4", "--parity-pairs", "30000", "--full"]
     import tempfile
     detail = os.path.join(tempfile.mkdtemp(prefix="dbtk_bench_"), "detail.json")
     env = dict(os.environ, DBTK_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"), DBTK_BENCH_DETAIL=detail)
@@ -770,6 +770,43 @@ def test_bench_two_ranks_on_one_gpu():
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["scaling"] == "weak" and d["value"] > 0
     assert len(d["per_rank_ms_per_step"]) == 2 and max(d["per_rank_ms_per_step"]) == pytest.approx(d["ms_per_step"], rel=1e-3)  # (every rank's own time: a first multi-GPU run is diagnosable from the line)
     assert d["reduce_check"] == dict(ranks=2, steps=2, pairs_per_rank=60000, bit_exact=True)
+
+
+def test_bench_plain_run_dumps_its_outputs(dbtk, oracle, tmp_path):
+    """A plain bench.py run (no --full): the contract's fields, none of the extras, no detail file — and --dump-outputs writes the last
+    timed step's accumulators, which equal the oracle's on the same seeded workload."""
+    import json
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    nloci, reads, steps = 3000, 400000, 3
+    out = tmp_path / "outputs"
+    detail = tmp_path / "detail.json"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--nloci", str(nloci),
+           "--reads", str(reads), "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, env=dict(os.environ, DBTK_BENCH_DETAIL=str(detail)), timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["steps"] == steps and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "reads/s" and d["higher_is_better"] is True
+    assert d["value"] == pytest.approx(reads * steps / (d["ms_per_step"] * steps / 1e3), rel=1e-3)
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["parity"] is None and "mixes" not in d and "detail" not in d
+    assert not detail.exists()
+    dumped = {n: np.load(out / f"{n}.npy") for n in ("counts", "kmc", "nmapread", "counters")}
+    assert all(v.dtype == np.float64 for v in dumped.values()) and sum(v.nbytes for v in dumped.values()) <= 64 << 20
+    # the same workload as bench.py builds it
+    syn = bind.pkg.Synth(nloci=nloci, k=21, flank=700, seed=20250808, nthreads=4)
+    arrs = syn.arrays()
+    h = C.c_void_p()
+    dbtk._chk(dbtk.L.dbtk_rpgg_from_arrays(C.byref(arrs), C.byref(h)))
+    g = bind.pkg.Rpgg(dbtk, h)
+    seq, off = syn.reads(reads // 2, rlen=150, hit_frac=0.02, seed=1, first_pair=0, nthreads=4)
+    go = oracle.from_arrays(arrs)
+    o = oracle.align(go, abi.default_params(ksize=21, n_filter=4, nm_filter=1, cthreshold=45, okam=0), seq, off, trace=False)
+    assert len(dumped["counts"]) == g.ntrkmers  # (fewer TR k-mers than the sample's size: all of them)
+    got = {n: v.astype(np.uint32 if n == "nmapread" else np.uint64) for n, v in dumped.items()}
+    assert got["counts"].sum() > 0
+    compare(o, got, g.output_order(), g.ntrkmers, reads // 2, recs=False)
+    oracle.free(go)
+    g.close()
+    syn.close()
 
 
 def test_checked_launches_mode(tmp_path):
