@@ -431,6 +431,7 @@ EXPORTS = [
 # include/dbtk_pred.h (the danbing-tk-pred step)
 EXPORTS_PRED = [
     "dbtk_pred_create", "dbtk_pred_free", "dbtk_pred_create_from_file", "dbtk_pred_nk", "dbtk_pred_ntr", "dbtk_pred_load_samples",
+    "dbtk_pred_load_device", "dbtk_pred_load_ctx",
     "dbtk_pred_correct", "dbtk_pred_matrix", "dbtk_pred_bias", "dbtk_pred_times",
 ]
 
@@ -445,6 +446,8 @@ class Pred:
         L.dbtk_pred_free.argtypes = [C.c_void_p]
         L.dbtk_pred_free.restype = None
         L.dbtk_pred_load_samples.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, u64p, C.POINTER(C.c_float)]
+        L.dbtk_pred_load_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_float)]
+        L.dbtk_pred_load_ctx.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_float]
         L.dbtk_pred_correct.argtypes = [C.c_void_p]
         L.dbtk_pred_matrix.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.dbtk_pred_bias.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
@@ -463,6 +466,17 @@ class Pred:
         counts = np.ascontiguousarray(counts, np.uint64)
         depths = np.ascontiguousarray(depths, np.float32)
         self._lib._chk(self._lib.L.dbtk_pred_load_samples(self.h, first, counts.shape[0], _ptr(counts, u64p), depths.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def load_device(self, first, n, d_counts, depths):
+        """dbtk_pred_load_device, in its argument order.  d_counts: address of n * nk uint64 counts in device memory (an int, or
+        anything with data_ptr())."""
+        depths = np.ascontiguousarray(depths, np.float32)
+        ptr = d_counts.data_ptr() if hasattr(d_counts, "data_ptr") else int(d_counts)
+        self._lib._chk(self._lib.L.dbtk_pred_load_device(self.h, first, n, C.c_void_p(ptr), depths.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def load_ctx(self, sample, ctx, depth):
+        """Column `sample` from the accumulated counts of a Context, without a round trip through the host."""
+        self._lib._chk(self._lib.L.dbtk_pred_load_ctx(self.h, sample, ctx.h, float(depth)))
 
     def correct(self):
         self._lib._chk(self._lib.L.dbtk_pred_correct(self.h))

@@ -12,7 +12,8 @@
 // Ingest: the three stages overlap — one thread parses and pairs (no per-line strings: spans of
 // the read buffer go straight into the batch's flat arrays), one thread per GPU aligns, the main thread formats and
 // writes the records in batch order.
-// New flags live under their own namespace: --gpus N (GPUs to use, default 1).
+// New flags live under their own namespace: --gpus N (GPUs to use, default 1); --cohort MANIFEST (many samples per RPGG load,
+// optionally straight into the danbing-tk-pred step: see "cohort mode" below).
 // stderr is informational (the reference's also carries timings); stdout and the
 // output files are byte-compatible.
 #include <errno.h>
@@ -44,13 +45,40 @@
 #include <vector>
 
 #include "../../include/dbtk.h"
+#include "../../include/dbtk_pred.h"
+#include "dbtk_pred_io.h"
 
 namespace {
 
+// cohort mode (--cohort): a failure belongs to a sample.  The message names it, the samples before it still get their files
+// (the hook waits for the thread that writes them), and the process ends with status 1 instead of the single run's abort.
+std::function<void()> g_cohort_drain;     // set in cohort mode.  Called by a failing thread: on the reader's side it returns once every earlier
+                                          // sample's outputs are written and closed — or the finisher has failed too; on the finisher it only
+                                          // says so (a drain that waited for a finisher that waits for the drain would hang the process)
+std::string g_cohort_sample;              // "sample <index> (<reads file>)" being read and aligned (any thread of the batch loop)
+thread_local std::string tl_cohort_sample;  // ... or being finished by this thread (counts, pred column, output files)
+std::mutex g_die_m;                       // one message at a time on stderr (held for the message only, never while draining)
+
 [[noreturn]] void die_assert(const std::string& what) {
+    if (g_cohort_drain) {
+        {
+            std::lock_guard<std::mutex> l(g_die_m);
+            const std::string& tag = tl_cohort_sample.empty() ? g_cohort_sample : tl_cohort_sample;
+            fprintf(stderr, "danbing-tk: %s%s%s\n", tag.c_str(), tag.empty() ? "" : ": ", what.c_str());
+            fflush(stderr);
+        }
+        g_cohort_drain();
+        _exit(1);  // (whichever failing thread gets here first ends the process; every one of them has printed its message)
+    }
     // the reference `assert`s on unusable files (abort, exit status 134)
     fprintf(stderr, "danbing-tk: %s\n", what.c_str());
     abort();
+}
+
+// a command line the cohort mode refuses, decided before anything is loaded: exit status 1, the flag named
+[[noreturn]] void refuse(const std::string& what) {
+    fprintf(stderr, "danbing-tk: %s\n", what.c_str());
+    exit(1);
 }
 
 struct Opts {
@@ -67,7 +95,13 @@ struct Opts {
              MAX_NT = 2, maxncorrection = 4;
     float readsPerBatchFactor = 1;
     std::string trPrefix, trFname, fastxFname, outPrefix, qcFn, baitFname;
+    // cohort mode
+    std::string cohortFn;              // --cohort MANIFEST
+    bool cohortNames = false;          // --cohort-names: OUT.tr.kmers per sample (the -on form)
+    bool noTrkmc = false;              // --no-trkmc: no per-sample files; the counts never leave HBM
+    std::vector<std::string> pred;     // --pred IKMER.META RAW.gt CORRECTED.gt BIAS.tsv
 };
+struct CohortSample { std::string reads, prefix; float depth = 0; };
 
 bool readable(const std::string& fn) {
     FILE* f = fopen(fn.c_str(), "rb");
@@ -105,6 +139,14 @@ void usage() {
             "  --aln-aligners <INT>   with -a / -ae: aligner threads (each with its own context) per GPU, so that fetching and formatting one\n"
             "                         batch's records overlaps the next batches' kernels [4]\n"
             "  --gz-level <INT>       zlib level of --aln-gz [1: measured 40x less deflate time than gzip's default 6 for 16 %% more bytes]\n"
+            "Cohort (many samples against one RPGG load; takes the place of -fa/-fq and -o/-on; needs -ka; one GPU):\n"
+            "  --cohort <MANIFEST>    one sample per line: reads file <TAB> output prefix [<TAB> read depth]; FASTA or FASTQ by the file's\n"
+            "                         first byte; per sample the files of a single run, one totals block each on stderr\n"
+            "  --cohort-names         per sample OUT.tr.kmers with names (the -on form) instead of OUT.trkmc.ar + OUT.tr.summary.txt\n"
+            "  --pred <IKMER.META> <RAW.gt> <CORRECTED.gt> <BIAS.tsv>\n"
+            "                         after the last sample, what danbing-tk-pred does with their counts and the manifest's read depths\n"
+            "                         (the counts go from the aligner into the genotype matrix without leaving the GPU)\n"
+            "  --no-trkmc             with --pred: write no per-sample files at all\n"
             "Developer:\n"
             "  -s <1|2>  -e <1|2>  -v <INT>  -g|-gc|-gcc <INT> [INT]  -a  -ae  -tb  -ik  -t <INT>  -m <FILE>  -au\n\n");
 }
@@ -341,6 +383,10 @@ int main(int argc, char* argv[]) {
         else if (a == "--ingest-shards") o.ingestShards = atoi(need(++argi).c_str());
         else if (a == "--gz-level") o.gzLevel = atoi(need(++argi).c_str());
         else if (a == "--aln-aligners") o.alnAligners = atoi(need(++argi).c_str());
+        else if (a == "--cohort") o.cohortFn = need(++argi);
+        else if (a == "--cohort-names") o.cohortNames = true;
+        else if (a == "--no-trkmc") o.noTrkmc = true;
+        else if (a == "--pred") { o.pred.clear(); for (int i = 0; i < 4; ++i) o.pred.push_back(need(++argi)); }
         else {
             fprintf(stderr, "invalid option: %s\n", a.c_str());
             abort();  // the reference does `throw;` with no active exception -> std::terminate
@@ -350,6 +396,72 @@ int main(int argc, char* argv[]) {
     // (`danbing-tk -gc 85 3 -ae ...`, README.md:38-39) then runs unchanged
     if (const char* e = getenv("DBTK_V13_THREADING")) if (atoi(e) != 0) o.v13 = true;
 
+    // ---- cohort mode: what it refuses, and its manifest — all of it before the GPU is asked for anything
+    const bool cohort = !o.cohortFn.empty();
+    std::vector<CohortSample> samples;
+    if (!cohort) {
+        if (o.cohortNames) refuse("--cohort-names needs --cohort");
+        if (!o.pred.empty()) refuse("--pred needs --cohort (for count files that exist already there is danbing-tk-pred)");
+        if (o.noTrkmc) refuse("--no-trkmc needs --cohort and --pred");
+    } else {
+        if (!o.fastxFname.empty()) refuse("--cohort takes the place of -fa/-fq: the reads files are in the manifest");
+        if (!o.outPrefix.empty()) refuse("--cohort takes the place of -o/-on: the output prefixes are in the manifest (--cohort-names for the -on form)");
+        if (o.okam) refuse("--cohort needs -ka: the kam records of many samples on one stdout are of no use");
+        if (o.extractFastX) refuse("--cohort cannot be combined with -e");
+        if (o.simmode) refuse("--cohort cannot be combined with -s");
+        if (o.aln) refuse("--cohort cannot be combined with -a/-ae");
+        if (o.bait) refuse("--cohort cannot be combined with -b");
+        if (o.trackBait) refuse("--cohort cannot be combined with -tb");
+        if (o.outputBubbles) refuse("--cohort cannot be combined with -bu");
+        if (o.ngpus > 1) refuse("--cohort runs on one GPU: --gpus > 1 is not supported with it");
+        if (o.ingestShards > 1) refuse("--cohort reads one sample at a time: --ingest-shards is not supported with it");
+        if (o.parseOnly) refuse("--cohort cannot be combined with --parse-only");
+        if (o.threading && !o.v13) refuse("--cohort with -g/-gc/-gcc needs --v13-threading (without it those flags leave every count at zero)");
+        if (o.noTrkmc && o.pred.empty()) refuse("--cohort with --no-trkmc needs --pred: without it the run would write nothing");
+        FILE* mf = fopen(o.cohortFn.c_str(), "rb");
+        if (!mf) refuse("--cohort: cannot open the manifest " + o.cohortFn);
+        std::string text;
+        { char buf[1 << 16]; size_t n; while ((n = fread(buf, 1, sizeof buf, mf)) > 0) text.append(buf, n); }
+        fclose(mf);
+        size_t at = 0, lineno = 0;
+        while (at < text.size()) {
+            size_t e = text.find('\n', at);
+            if (e == std::string::npos) e = text.size();
+            std::string line = text.substr(at, e - at);
+            at = e + 1; ++lineno;
+            if (!line.empty() && line.back() == '\r') line.pop_back();
+            if (line.empty()) continue;
+            std::vector<std::string> col;
+            for (size_t p = 0;;) { const size_t t = line.find('\t', p); col.push_back(line.substr(p, t == std::string::npos ? t : t - p)); if (t == std::string::npos) break; p = t + 1; }
+            const std::string where = "--cohort: " + o.cohortFn + " line " + std::to_string(lineno) + ": ";
+            const size_t needc = o.pred.empty() ? 2 : 3;
+            if (col.size() < needc || col[0].empty() || (col[1].empty() && !o.noTrkmc))
+                refuse(where + "expected reads file <TAB> output prefix" + (o.pred.empty() ? "" : " <TAB> read depth (--pred needs the depth)") + ", found " + std::to_string(col.size()) + " column(s)");
+            CohortSample sm;
+            sm.reads = col[0]; sm.prefix = col[1];
+            if (!o.pred.empty()) {
+                char* endp = nullptr;
+                errno = 0;
+                sm.depth = strtof(col[2].c_str(), &endp);
+                if (endp == col[2].c_str() || *endp || errno || !(sm.depth > 0) || sm.depth > 3e38f) refuse(where + "read depth '" + col[2] + "' is not a positive number");
+            }
+            samples.push_back(sm);
+        }
+        if (samples.empty()) refuse("--cohort: " + o.cohortFn + " names no sample");
+        if (!o.pred.empty()) {
+            // the four files of --pred now, not after the table build (IKMER.META) or after the last sample (the outputs, hours into a large
+            // cohort): IKMER.META must be readable, the three outputs creatable.  The probe leaves nothing behind — and no stale output of an
+            // earlier run either, as -o does with OUT.trkmc.ar (AQ.cpp:2417)
+            if (!readable(o.pred[0])) refuse("--pred: cannot open " + o.pred[0]);
+            for (int i = 1; i < 4; ++i) {
+                FILE* f = fopen(o.pred[i].c_str(), "wb");
+                if (!f) refuse("--pred: cannot create " + o.pred[i]);
+                fclose(f);
+                (void)unlink(o.pred[i].c_str());
+            }
+        }
+    }
+
     fprintf(stderr,
             "use baitDB: %d\nextract fastX: %d\noutput bubbles: %d\nis Fastq: %d\nsim mode: %d\ngraph threading mode: %d\n"
             "output kmer assignment (kam): %d\nk: %llu\n# of subsampled kmers in pre-filtering: %llu\n"
@@ -357,7 +469,11 @@ int main(int argc, char* argv[]) {
             "fastx: %s\nquery: %s.(tr/ntr).kmers\nGPUs: %d\n\n",
             o.bait, o.extractFastX, o.outputBubbles, o.isFastq, o.simmode, o.threading, o.okam, (unsigned long long)o.ksize,
             (unsigned long long)o.N_FILTER, (unsigned long long)o.NM_FILTER, (unsigned long long)o.Cthreshold,
-            (unsigned long long)o.NM_TR, o.fastxFname.c_str(), o.trPrefix.c_str(), o.ngpus);
+            (unsigned long long)o.NM_TR, cohort ? o.cohortFn.c_str() : o.fastxFname.c_str(), o.trPrefix.c_str(), o.ngpus);
+    if (cohort) {
+        fprintf(stderr, "cohort: %zu samples%s%s\n\n", samples.size(), o.pred.empty() ? "" : ", genotype matrices to ", o.pred.empty() ? "" : o.pred[1].c_str());
+        o.fastxFname = samples[0].reads;  // (what the warm-up thread sizes the pinned buffers by)
+    }
 
     // ---- load (AQ.cpp:2459-2504)
     time_t time1 = time(nullptr);
@@ -507,6 +623,39 @@ int main(int argc, char* argv[]) {
     if (!o.parseOnly)
         for (int d = 0; d < o.ngpus; ++d)
             if (dbtk_ctx_create(rpgg, &P, dev_of(d), &ctx[d])) die_assert(dbtk_last_error());
+    // cohort mode: a second context on the same device (the tables are shared: it costs its accumulators and scratch) so that one
+    // sample is read and aligned while the one before it is finished, and the genotype matrix of --pred — all of it before the
+    // first sample, so that HBM that does not suffice ends the run before any work is done
+    dbtk_ctx_t* cohort_ctx[2] = {ctx[0], nullptr};
+    int cohort_nctx = 2;
+    if (const char* e = getenv("DBTK_COHORT_CONTEXTS")) if (atoi(e) == 1) cohort_nctx = 1;  // (measurements: what the second context buys)
+    dbtk_pred_t* pred = nullptr;
+    if (cohort) {
+        // what the run holds in HBM from here on, for the message when it does not fit: tables, accumulators, the matrix of --pred
+        // (a context's batch scratch is allocated by its first batches and is not part of this)
+        auto hbm_sizes = [&] {
+            const char* nm[16]; uint64_t tb[16], tsum = 0;
+            const int nt = dbtk_ctx_table_bytes(ctx[0], nm, tb, 16);
+            for (int i = 0; i < nt; ++i) if (strcmp(nm[i], "index_images:from_cache")) tsum += tb[i];
+            return "the RPGG's tables hold " + std::to_string(tsum) + " bytes, " + std::to_string(cohort_nctx) + " contexts' accumulators " +
+                   std::to_string((uint64_t)cohort_nctx * 8 * (dbtk_rpgg_ntrkmers(rpgg) + 2 * nloci + DBTK_C_COUNT)) + " bytes, the genotype matrix of --pred " +
+                   std::to_string(o.pred.empty() ? 0 : 4 * dbtk_rpgg_ntrkmers(rpgg) * (uint64_t)samples.size()) + " bytes";
+        };
+        if (cohort_nctx == 2 && dbtk_ctx_create(rpgg, &P, dev_of(0), &cohort_ctx[1])) {
+            const std::string err = dbtk_last_error();
+            die_assert("the second context could not be created (" + err + "): " + hbm_sizes());
+        }
+        if (!o.pred.empty()) {
+            const dbtk_status_t ps = dbtk_pred_create_from_file(dev_of(0), samples.size(), o.pred[0].c_str(), &pred);
+            if (ps == DBTK_ERR_NOMEM) {
+                const std::string err = dbtk_last_error();
+                die_assert("not enough HBM for the cohort: " + hbm_sizes() + "; " + err);
+            }
+            if (ps) die_assert(dbtk_last_error());
+            if (dbtk_pred_nk(pred) != dbtk_rpgg_ntrkmers(rpgg))
+                die_assert(o.pred[0] + " describes " + std::to_string(dbtk_pred_nk(pred)) + " TR k-mers, " + o.trFname + " holds " + std::to_string(dbtk_rpgg_ntrkmers(rpgg)) + ": not the same RPGG build");
+        }
+    }
     fprintf(stderr, "load: RPGG files %.2f s, tables in HBM %.2f s\n", tl1 - tl0, wall() - tl1);
     if (pin_n && getenv("DBTK_VERBOSE")) fprintf(stderr, "pinned ahead: %u chunk buffers in %.3f s (beside the RPGG files)\n", pin_n, pin_s);
     if (!o.parseOnly && ctx[0]) {  // what the RPGG occupies on a GPU, table by table
@@ -532,7 +681,7 @@ int main(int argc, char* argv[]) {
     // (with -g / -gc no pair record is ever produced — at HEAD nothing happens behind the threading gate, AQ.cpp:2070-2090; under the v1.3
     // contract the walk counts exactly and prints alignments, not kam lines — so no record buffer travels and the blocks take the record-free path)
     const bool want_recs = !o.threading && (o.okam || o.extractFastX);
-    const bool fq = o.isFastq;
+    bool fq = o.isFastq;  // (cohort mode: per sample)
     time1 = time(nullptr);
     fprintf(stderr, "threads created\n");
     typedef std::unique_ptr<Batch> BatchP;
@@ -1384,191 +1533,332 @@ int main(int argc, char* argv[]) {
         nReads += nR; read_busy += rb; gpu_busy += gb; write_busy += wb;
         dev_ingest_reads += nR;
     };
-    // the ranges
-    std::vector<uint64_t> cuts{0, ~0ull};
-    {
-        struct stat sb;
-        uint64_t min_size = 64u << 20;  // below this one pipeline is as good
-        if (const char* e = getenv("DBTK_SHARD_MIN")) min_size = strtoull(e, nullptr, 10);  // (tests)
-        const int want = std::max(o.ngpus, o.ingestShards);  // ranges asked for: one per GPU, or more (--ingest-shards)
-        if (want > 1 && !o.simmode && stat(o.fastxFname.c_str(), &sb) == 0 && S_ISREG(sb.st_mode) && (uint64_t)sb.st_size > min_size) {
-            const uint64_t size = (uint64_t)sb.st_size;
-            FILE* f = fopen(o.fastxFname.c_str(), "rb");
-            std::vector<uint64_t> c{0};
-            std::vector<char> buf(1 << 20);
-            for (int i = 1; f && i < want; ++i) {
-                // the first record start at or after size * i / N: a line that begins with '>' (2-line FASTA: sequence lines never do),
-                // or — FASTQ, where a quality line may begin with '@' — a line beginning with '@' whose second next line begins with '+'
-                uint64_t at = size / want * i;
-                if (fseeko(f, (off_t)at, SEEK_SET)) break;
-                const size_t n = fread(buf.data(), 1, buf.size(), f);
-                size_t p = 0, found = n;
-                while (p < n && buf[p] != '\n') ++p;  // skip to the end of the line the cut fell into
-                ++p;
-                while (p < n) {
-                    const char* l1 = (const char*)memchr(buf.data() + p, '\n', n - p);
-                    if (!l1) break;
-                    if (!fq) { if (buf[p] == '>') { found = p; break; } }
-                    else if (buf[p] == '@') {
-                        const char* l2 = (const char*)memchr(l1 + 1, '\n', n - (l1 + 1 - buf.data()));
-                        if (l2 && (size_t)(l2 + 1 - buf.data()) < n && l2[1] == '+') { found = p; break; }
-                    }
-                    p = l1 + 1 - buf.data();
-                }
-                if (found == n) { c.clear(); break; }  // (no record start in sight: lines longer than the window) -> one range
-                {   // on a PAIR boundary where the file is interleaved: if the record found here carries the title of the record before
-                    // it... which is not in the window; equivalently: if records 0 and 1 from here have different titles but 1 and 2 the
-                    // same, record 0 is the second mate of the pair the cut fell into -> start one record later.  (The device reader needs
-                    // its range to start with a pair; the host reader saves a round through the cross-range pairing.)
-                    const size_t Lr = fq ? 4 : 2;
-                    size_t tb[3], tl[3], q = found;
-                    int have = 0;
-                    for (; have < 3 && q < n; ++have) {
-                        const char* e = (const char*)memchr(buf.data() + q, '\n', n - q);
-                        if (!e) break;
-                        tb[have] = q; tl[have] = (size_t)(e - (buf.data() + q));
-                        if (tl[have] >= 2 && buf[q + tl[have] - 2] == '/' && (buf[q + tl[have] - 1] == '1' || buf[q + tl[have] - 1] == '2')) tl[have] -= 2;  // prunePEinfo
-                        size_t r = q;
-                        bool whole = true;
-                        for (size_t l = 0; l < Lr; ++l) {
-                            const char* e2 = (const char*)memchr(buf.data() + r, '\n', n - r);
-                            if (!e2) { whole = false; break; }
-                            r = (size_t)(e2 - buf.data()) + 1;
+    // one input — o.fastxFname, fq — through the batch loop on the contexts in `ctx` (cohort mode: once per sample)
+    auto run_input = [&] {
+        // the ranges
+        std::vector<uint64_t> cuts{0, ~0ull};
+        {
+            struct stat sb;
+            uint64_t min_size = 64u << 20;  // below this one pipeline is as good
+            if (const char* e = getenv("DBTK_SHARD_MIN")) min_size = strtoull(e, nullptr, 10);  // (tests)
+            const int want = std::max(o.ngpus, o.ingestShards);  // ranges asked for: one per GPU, or more (--ingest-shards)
+            if (want > 1 && !o.simmode && stat(o.fastxFname.c_str(), &sb) == 0 && S_ISREG(sb.st_mode) && (uint64_t)sb.st_size > min_size) {
+                const uint64_t size = (uint64_t)sb.st_size;
+                FILE* f = fopen(o.fastxFname.c_str(), "rb");
+                std::vector<uint64_t> c{0};
+                std::vector<char> buf(1 << 20);
+                for (int i = 1; f && i < want; ++i) {
+                    // the first record start at or after size * i / N: a line that begins with '>' (2-line FASTA: sequence lines never do),
+                    // or — FASTQ, where a quality line may begin with '@' — a line beginning with '@' whose second next line begins with '+'
+                    uint64_t at = size / want * i;
+                    if (fseeko(f, (off_t)at, SEEK_SET)) break;
+                    const size_t n = fread(buf.data(), 1, buf.size(), f);
+                    size_t p = 0, found = n;
+                    while (p < n && buf[p] != '\n') ++p;  // skip to the end of the line the cut fell into
+                    ++p;
+                    while (p < n) {
+                        const char* l1 = (const char*)memchr(buf.data() + p, '\n', n - p);
+                        if (!l1) break;
+                        if (!fq) { if (buf[p] == '>') { found = p; break; } }
+                        else if (buf[p] == '@') {
+                            const char* l2 = (const char*)memchr(l1 + 1, '\n', n - (l1 + 1 - buf.data()));
+                            if (l2 && (size_t)(l2 + 1 - buf.data()) < n && l2[1] == '+') { found = p; break; }
                         }
-                        if (!whole) { ++have; break; }
-                        q = r;
+                        p = l1 + 1 - buf.data();
                     }
-                    auto same = [&](int i, int j) { return tl[i] == tl[j] && memcmp(buf.data() + tb[i], buf.data() + tb[j], tl[i]) == 0; };
-                    if (have == 3 && !same(0, 1) && same(1, 2)) found = tb[1];
+                    if (found == n) { c.clear(); break; }  // (no record start in sight: lines longer than the window) -> one range
+                    {   // on a PAIR boundary where the file is interleaved: if the record found here carries the title of the record before
+                        // it... which is not in the window; equivalently: if records 0 and 1 from here have different titles but 1 and 2 the
+                        // same, record 0 is the second mate of the pair the cut fell into -> start one record later.  (The device reader needs
+                        // its range to start with a pair; the host reader saves a round through the cross-range pairing.)
+                        const size_t Lr = fq ? 4 : 2;
+                        size_t tb[3], tl[3], q = found;
+                        int have = 0;
+                        for (; have < 3 && q < n; ++have) {
+                            const char* e = (const char*)memchr(buf.data() + q, '\n', n - q);
+                            if (!e) break;
+                            tb[have] = q; tl[have] = (size_t)(e - (buf.data() + q));
+                            if (tl[have] >= 2 && buf[q + tl[have] - 2] == '/' && (buf[q + tl[have] - 1] == '1' || buf[q + tl[have] - 1] == '2')) tl[have] -= 2;  // prunePEinfo
+                            size_t r = q;
+                            bool whole = true;
+                            for (size_t l = 0; l < Lr; ++l) {
+                                const char* e2 = (const char*)memchr(buf.data() + r, '\n', n - r);
+                                if (!e2) { whole = false; break; }
+                                r = (size_t)(e2 - buf.data()) + 1;
+                            }
+                            if (!whole) { ++have; break; }
+                            q = r;
+                        }
+                        auto same = [&](int i, int j) { return tl[i] == tl[j] && memcmp(buf.data() + tb[i], buf.data() + tb[j], tl[i]) == 0; };
+                        if (have == 3 && !same(0, 1) && same(1, 2)) found = tb[1];
+                    }
+                    c.push_back(at + found);
                 }
-                c.push_back(at + found);
+                if (f) fclose(f);
+                if ((int)c.size() == want) { c.push_back(size); cuts = c; }
             }
-            if (f) fclose(f);
-            if ((int)c.size() == want) { c.push_back(size); cuts = c; }
         }
-    }
-    const int nshards = (int)cuts.size() - 1;
-    npipes = nshards;
-    nshards_now = nshards;
-    // more ranges than GPUs: range i gets a context of its own on GPU i % ngpus (the contexts of a GPU share its tables;
-    // an aligner thread and its context belong together: dbtk_align_batch is re-entrant per context, not within one)
-    if (!o.parseOnly)
-        for (int i = (int)ctx.size(); i < nshards; ++i) {
-            ctx.push_back(nullptr);
-            if (dbtk_ctx_create(rpgg, &P, dev_of(i % o.ngpus), &ctx[i])) die_assert(dbtk_last_error());
-        }
-    // the further aligner contexts of -a / -ae (made beside the first one, above)
-    if (extra.joinable()) extra.join();
-    if (!extra_err.empty()) die_assert(extra_err);
-    if (nshards == 1) for (dbtk_ctx_t* c : extra_ctx) ctx.push_back(c);
-    else for (dbtk_ctx_t* c : extra_ctx) dbtk_ctx_free(c);
-    if (!o.parseOnly && emit_aln && nshards == 1)
-        for (int i = (int)ctx.size(); i < aln_aligners * o.ngpus; ++i) {  // (none were made ahead: several GPUs or --ingest-shards, and the input gave one range)
-            ctx.push_back(nullptr);
-            if (dbtk_ctx_create(rpgg, &P, dev_of(i % o.ngpus), &ctx[i])) die_assert(dbtk_last_error());
-        }
-    std::vector<std::vector<Left>> lefts(nshards);
-    {
-        std::vector<std::thread> shards;
-        // the device reader first, where it applies: a regular file (pread at offsets), no per-read work the host must do (-s parses
-        // titles, -tb replays batches from host copies of the reads, -a / -ae has its own several-contexts-per-GPU emit path)
-        struct stat sb;
-        const bool is_file = stat(o.fastxFname.c_str(), &sb) == 0 && S_ISREG(sb.st_mode);
-        // (-a / -ae: the lines are assembled and gzip-compressed on the device too — a Huffman-only deflate, about zlib's level 1 in size; an
-        // explicit --gz-level other than 1 keeps the host's zlib, and with it the host reader)
-        bool dev_ingest = !o.parseOnly && !o.hostIngest && !o.simmode && !P.trackbait && (!emit_aln || o.gzLevel == 1) && (is_file || nshards == 1);
-        if (const char* e = getenv("DBTK_DEVICE_INGEST")) if (atoi(e) == 0) dev_ingest = false;
-        auto one = [&](int i) {
-            uint64_t lo = nshards == 1 ? 0 : cuts[i];
-            const uint64_t hi = nshards == 1 ? (is_file ? (uint64_t)sb.st_size : ~0ull) : cuts[i + 1];
-            if (dev_ingest) {
-                uint64_t resume = lo;
-                std::string replay;
-                int pfd = -1;
-                run_device_ingest(ctx[i], lo, hi, &resume, !is_file, &replay, &pfd);
-                if (resume >= hi) return;
-                fprintf(stderr, "device reader: input is not interleaved at byte %llu; the host reader takes over\n", (unsigned long long)resume);
-                lo = resume;
-                if (!is_file) {  // the pipe cannot be read again: a stream of what was taken but not paired, then the descriptor
-                    struct Cookie { std::string pre; size_t at; int fd; };
-                    Cookie* ck = new Cookie{std::move(replay), 0, pfd};
-                    cookie_io_functions_t fn;
-                    memset(&fn, 0, sizeof(fn));
-                    fn.read = [](void* c, char* buf, size_t n) -> ssize_t {
-                        Cookie* k = (Cookie*)c;
-                        if (k->at < k->pre.size()) { const size_t m2 = std::min(n, k->pre.size() - k->at); memcpy(buf, k->pre.data() + k->at, m2); k->at += m2; return (ssize_t)m2; }
-                        for (;;) { const ssize_t r = read(k->fd, buf, n); if (r < 0 && errno == EINTR) continue; return r; }
-                    };
-                    fn.close = [](void* c) -> int { Cookie* k = (Cookie*)c; close(k->fd); delete k; return 0; };
-                    handover_stream = fopencookie(ck, "rb", fn);
-                    if (!handover_stream) die_assert("fopencookie failed");
-                }
+        const int nshards = (int)cuts.size() - 1;
+        npipes = nshards;
+        nshards_now = nshards;
+        // more ranges than GPUs: range i gets a context of its own on GPU i % ngpus (the contexts of a GPU share its tables;
+        // an aligner thread and its context belong together: dbtk_align_batch is re-entrant per context, not within one)
+        if (!o.parseOnly)
+            for (int i = (int)ctx.size(); i < nshards; ++i) {
+                ctx.push_back(nullptr);
+                if (dbtk_ctx_create(rpgg, &P, dev_of(i % o.ngpus), &ctx[i])) die_assert(dbtk_last_error());
             }
-            const auto r = nshards == 1 ? run_shard(0, 0, o.parseOnly ? o.ngpus : (int)ctx.size(), lo, ~0ull, lefts[0]) : run_shard(i, i, 1, lo, hi, lefts[i]);
-            std::lock_guard<std::mutex> lk(tot_m);
-            nReads += std::get<0>(r); read_busy += std::get<1>(r); cut_busy += std::get<2>(r); pair_busy += std::get<3>(r);
-            gpu_busy += std::get<4>(r); write_busy += std::get<5>(r); nsplit_used += std::get<6>(r);
-        };
-        for (int i = 1; i < nshards; ++i) shards.emplace_back(one, i);
-        one(0);
-        for (auto& t : shards) t.join();
-    }
-    if (nshards > 1) {
-        // cross-range pairing of what the ranges left over, in range order (the reader's rule: the first record of a title is
-        // parked, the next one with that title completes the pair as seq1), then one last batch on GPU 0
-        std::unordered_map<std::string, std::pair<std::string, std::string>> parked;
-        Batch b;
-        uint64_t nleft = 0;
-        auto reset_left = [&] { b.flat.clear(); b.off.assign(1, 0); b.qar.clear(); b.qoff.assign(1, 0); b.tar.clear(); b.toff.assign(1, 0); b.src.clear(); b.nreads = 0; b.nrec = 0; };
-        // one batch of what the ranges left over through GPU 0 (in chunks of a batch's size: mates far apart in the file — an R1 block
-        // followed by an R2 block — leave nearly the whole file here, and one batch of that would neither fit the host nor a 32-bit
-        // pair index)
-        auto flush_left = [&] {
-            nReads += b.nreads; nleft += b.nreads;
-            if (b.nreads && !o.parseOnly) {
-                const uint64_t npairs = b.nreads / 2;
-                std::vector<uint8_t> flatq;
-                const bool send_qual = use_bait && fq;
-                if (send_qual) {
-                    flatq.assign(b.flat.size() + 1, (uint8_t)'!');
-                    for (uint64_t r = 0; r < b.nreads; ++r)
-                        memcpy(flatq.data() + b.off[r], b.qar.data() + b.qoff[r], std::min(b.qoff[r + 1] - b.qoff[r], b.off[r + 1] - b.off[r]));
+        // the further aligner contexts of -a / -ae (made beside the first one, above)
+        if (extra.joinable()) extra.join();
+        if (!extra_err.empty()) die_assert(extra_err);
+        if (nshards == 1) for (dbtk_ctx_t* c : extra_ctx) ctx.push_back(c);
+        else for (dbtk_ctx_t* c : extra_ctx) dbtk_ctx_free(c);
+        if (!o.parseOnly && emit_aln && nshards == 1)
+            for (int i = (int)ctx.size(); i < aln_aligners * o.ngpus; ++i) {  // (none were made ahead: several GPUs or --ingest-shards, and the input gave one range)
+                ctx.push_back(nullptr);
+                if (dbtk_ctx_create(rpgg, &P, dev_of(i % o.ngpus), &ctx[i])) die_assert(dbtk_last_error());
+            }
+        std::vector<std::vector<Left>> lefts(nshards);
+        {
+            std::vector<std::thread> shards;
+            // the device reader first, where it applies: a regular file (pread at offsets), no per-read work the host must do (-s parses
+            // titles, -tb replays batches from host copies of the reads, -a / -ae has its own several-contexts-per-GPU emit path)
+            struct stat sb;
+            const bool is_file = stat(o.fastxFname.c_str(), &sb) == 0 && S_ISREG(sb.st_mode);
+            // (-a / -ae: the lines are assembled and gzip-compressed on the device too — a Huffman-only deflate, about zlib's level 1 in size; an
+            // explicit --gz-level other than 1 keeps the host's zlib, and with it the host reader)
+            bool dev_ingest = !o.parseOnly && !o.hostIngest && !o.simmode && !P.trackbait && (!emit_aln || o.gzLevel == 1) && (is_file || nshards == 1);
+            if (const char* e = getenv("DBTK_DEVICE_INGEST")) if (atoi(e) == 0) dev_ingest = false;
+            auto one = [&](int i) {
+                uint64_t lo = nshards == 1 ? 0 : cuts[i];
+                const uint64_t hi = nshards == 1 ? (is_file ? (uint64_t)sb.st_size : ~0ull) : cuts[i + 1];
+                if (dev_ingest) {
+                    uint64_t resume = lo;
+                    std::string replay;
+                    int pfd = -1;
+                    run_device_ingest(ctx[i], lo, hi, &resume, !is_file, &replay, &pfd);
+                    if (resume >= hi) return;
+                    fprintf(stderr, "device reader: input is not interleaved at byte %llu; the host reader takes over\n", (unsigned long long)resume);
+                    lo = resume;
+                    if (!is_file) {  // the pipe cannot be read again: a stream of what was taken but not paired, then the descriptor
+                        struct Cookie { std::string pre; size_t at; int fd; };
+                        Cookie* ck = new Cookie{std::move(replay), 0, pfd};
+                        cookie_io_functions_t fn;
+                        memset(&fn, 0, sizeof(fn));
+                        fn.read = [](void* c, char* buf, size_t n) -> ssize_t {
+                            Cookie* k = (Cookie*)c;
+                            if (k->at < k->pre.size()) { const size_t m2 = std::min(n, k->pre.size() - k->at); memcpy(buf, k->pre.data() + k->at, m2); k->at += m2; return (ssize_t)m2; }
+                            for (;;) { const ssize_t r = read(k->fd, buf, n); if (r < 0 && errno == EINTR) continue; return r; }
+                        };
+                        fn.close = [](void* c) -> int { Cookie* k = (Cookie*)c; close(k->fd); delete k; return 0; };
+                        handover_stream = fopencookie(ck, "rb", fn);
+                        if (!handover_stream) die_assert("fopencookie failed");
+                    }
                 }
-                if (want_recs) b.recs.resize(npairs);
-                b.flat.push_back(0);
-                if (dbtk_align_batch(ctx[0], b.flat.data(), b.off.data(), send_qual ? flatq.data() : nullptr, npairs, want_recs ? b.recs.data() : nullptr,
-                                     want_recs ? npairs : 0, &b.nrec)) die_assert(std::string("align: ") + dbtk_last_error());
-                b.flat.pop_back();
-                if (emit_aln) {
-                    uint64_t used = 0;
-                    b.aln_idx.resize(npairs);
-                    dbtk_status_t sa = dbtk_ctx_aln_text(ctx[0], b.aln_idx.data(), npairs, nullptr, 0, &used);
-                    if (sa == DBTK_ERR_OVERFLOW) { b.aln.grow((size_t)used + 16); sa = dbtk_ctx_aln_text(ctx[0], b.aln_idx.data(), npairs, b.aln.data(), b.aln.size(), &used); }
-                    if (sa) die_assert(std::string("alignment records: ") + dbtk_last_error());
-                    prepare_alignments(b);
-                }
-                emit(b);
-            } else if (b.nreads && o.parseOnly) digest_batch(b);
+                const auto r = nshards == 1 ? run_shard(0, 0, o.parseOnly ? o.ngpus : (int)ctx.size(), lo, ~0ull, lefts[0]) : run_shard(i, i, 1, lo, hi, lefts[i]);
+                std::lock_guard<std::mutex> lk(tot_m);
+                nReads += std::get<0>(r); read_busy += std::get<1>(r); cut_busy += std::get<2>(r); pair_busy += std::get<3>(r);
+                gpu_busy += std::get<4>(r); write_busy += std::get<5>(r); nsplit_used += std::get<6>(r);
+            };
+            for (int i = 1; i < nshards; ++i) shards.emplace_back(one, i);
+            one(0);
+            for (auto& t : shards) t.join();
+        }
+        if (nshards > 1) {
+            // cross-range pairing of what the ranges left over, in range order (the reader's rule: the first record of a title is
+            // parked, the next one with that title completes the pair as seq1), then one last batch on GPU 0
+            std::unordered_map<std::string, std::pair<std::string, std::string>> parked;
+            Batch b;
+            uint64_t nleft = 0;
+            auto reset_left = [&] { b.flat.clear(); b.off.assign(1, 0); b.qar.clear(); b.qoff.assign(1, 0); b.tar.clear(); b.toff.assign(1, 0); b.src.clear(); b.nreads = 0; b.nrec = 0; };
+            // one batch of what the ranges left over through GPU 0 (in chunks of a batch's size: mates far apart in the file — an R1 block
+            // followed by an R2 block — leave nearly the whole file here, and one batch of that would neither fit the host nor a 32-bit
+            // pair index)
+            auto flush_left = [&] {
+                nReads += b.nreads; nleft += b.nreads;
+                if (b.nreads && !o.parseOnly) {
+                    const uint64_t npairs = b.nreads / 2;
+                    std::vector<uint8_t> flatq;
+                    const bool send_qual = use_bait && fq;
+                    if (send_qual) {
+                        flatq.assign(b.flat.size() + 1, (uint8_t)'!');
+                        for (uint64_t r = 0; r < b.nreads; ++r)
+                            memcpy(flatq.data() + b.off[r], b.qar.data() + b.qoff[r], std::min(b.qoff[r + 1] - b.qoff[r], b.off[r + 1] - b.off[r]));
+                    }
+                    if (want_recs) b.recs.resize(npairs);
+                    b.flat.push_back(0);
+                    if (dbtk_align_batch(ctx[0], b.flat.data(), b.off.data(), send_qual ? flatq.data() : nullptr, npairs, want_recs ? b.recs.data() : nullptr,
+                                         want_recs ? npairs : 0, &b.nrec)) die_assert(std::string("align: ") + dbtk_last_error());
+                    b.flat.pop_back();
+                    if (emit_aln) {
+                        uint64_t used = 0;
+                        b.aln_idx.resize(npairs);
+                        dbtk_status_t sa = dbtk_ctx_aln_text(ctx[0], b.aln_idx.data(), npairs, nullptr, 0, &used);
+                        if (sa == DBTK_ERR_OVERFLOW) { b.aln.grow((size_t)used + 16); sa = dbtk_ctx_aln_text(ctx[0], b.aln_idx.data(), npairs, b.aln.data(), b.aln.size(), &used); }
+                        if (sa) die_assert(std::string("alignment records: ") + dbtk_last_error());
+                        prepare_alignments(b);
+                    }
+                    emit(b);
+                } else if (b.nreads && o.parseOnly) digest_batch(b);
+                reset_left();
+            };
             reset_left();
-        };
-        reset_left();
-        for (auto& lv : lefts)
-            for (auto& r : lv) {
-                auto it = parked.find(r.title);
-                if (it == parked.end()) { parked[r.title] = std::make_pair(r.seq, r.qual); continue; }
-                const std::string s2 = it->second.first, q2 = it->second.second;
-                parked.erase(it);
-                if (r.seq.size() < minReadSize || s2.size() < minReadSize) continue;
-                if (o.simmode) b.src.push_back(parse_src(r.title, o.simmode, nloci));
-                b.tar.insert(b.tar.end(), r.title.begin(), r.title.end()); b.toff.push_back(b.tar.size());
-                b.add_read(r.seq.data(), r.seq.size(), r.qual.data(), r.qual.size(), fq);
-                b.add_read(s2.data(), s2.size(), q2.data(), q2.size(), fq);
-                b.nreads += 2;
-                if (b.nreads >= readsPerBatch) flush_left();
+            for (auto& lv : lefts)
+                for (auto& r : lv) {
+                    auto it = parked.find(r.title);
+                    if (it == parked.end()) { parked[r.title] = std::make_pair(r.seq, r.qual); continue; }
+                    const std::string s2 = it->second.first, q2 = it->second.second;
+                    parked.erase(it);
+                    if (r.seq.size() < minReadSize || s2.size() < minReadSize) continue;
+                    if (o.simmode) b.src.push_back(parse_src(r.title, o.simmode, nloci));
+                    b.tar.insert(b.tar.end(), r.title.begin(), r.title.end()); b.toff.push_back(b.tar.size());
+                    b.add_read(r.seq.data(), r.seq.size(), r.qual.data(), r.qual.size(), fq);
+                    b.add_read(s2.data(), s2.size(), q2.data(), q2.size(), fq);
+                    b.nreads += 2;
+                    if (b.nreads >= readsPerBatch) flush_left();
+                }
+            flush_left();
+            fprintf(stderr, "cross-range pairing: %llu reads\n", (unsigned long long)nleft);
+        }
+    };  // run_input
+    // ---- cohort mode: one RPGG load, one table build, one warm-up; then per sample what a single run does from its batch loop on.
+    // Two contexts alternate: while this thread reads and aligns sample i + 1 on one, the finisher thread takes sample i's counts
+    // off the other — into the genotype matrix (device to device), to the host, into its files — and resets it.
+    double cohort_wait_s = 0, cohort_finish_s = 0;
+    uint64_t cohort_reads = 0;
+    if (cohort) {
+        struct Done { size_t index; dbtk_ctx_t* c; uint64_t nreads; long sec; };
+        std::mutex fm;
+        std::condition_variable fcv;
+        std::deque<Done> fq_;
+        bool fstop = false;
+        size_t nfinished = 0, nqueued = 0;  // samples the finisher is done with / was handed
+        bool finisher_failed = false;       // the finisher is on its way out through die_assert: nothing more will be finished
+        std::thread::id finisher_id;
+        const uint64_t ntrk = dbtk_rpgg_ntrkmers(rpgg);
+        std::vector<uint64_t> counts(o.noTrkmc ? 0 : ntrk), kmc(nloci), counters(DBTK_C_COUNT);
+        std::vector<uint32_t> nmapread(nloci);
+        auto tag_of = [&](size_t i) { return "sample " + std::to_string(i) + " (" + samples[i].reads + ")"; };
+        auto finish = [&](const Done& d) {
+            const double t0 = now();
+            tl_cohort_sample = tag_of(d.index);
+            const CohortSample& sm = samples[d.index];
+            // (a sticky device error — an over-long read the device truncated — comes out of the first of these calls: no column, no file)
+            if (pred && dbtk_pred_load_ctx(pred, d.index, d.c, sm.depth)) die_assert(dbtk_last_error());
+            if (dbtk_ctx_counts(d.c, o.noTrkmc ? nullptr : counts.data(), o.noTrkmc ? nullptr : kmc.data(), o.noTrkmc ? nullptr : nmapread.data(), counters.data()))
+                die_assert(dbtk_last_error());
+            char blk[1024];
+            snprintf(blk, sizeof blk,
+                     "# sample %zu %s\n"
+                     "%llu reads processed in total.\n%llu reads removed by subsampled kmer-filter.\n%llu reads removed by kmer-filter.\n"
+                     "%llu reads removed by bait locus.\n%llu reads removed by qual filter.\n%llu reads removed during locus assignment.\n"
+                     "%llu reads removed by QC filter.\n%llu reads entered threading step.\n%llu reads passsed threading.\n"
+                     "%llu reads assigned to TR region.\nparallel query completed in %ld sec.\n",
+                     d.index, sm.prefix.c_str(), (unsigned long long)d.nreads, (unsigned long long)counters[DBTK_C_SUBFILTERED], (unsigned long long)counters[DBTK_C_KMERFILTERED],
+                     (unsigned long long)counters[DBTK_C_BAITFILTERED], (unsigned long long)counters[DBTK_C_QUALFILTERED],
+                     (unsigned long long)counters[DBTK_C_LOCUSFILTERED], (unsigned long long)counters[DBTK_C_QCFILTERED],
+                     (unsigned long long)counters[DBTK_C_THREADING], (unsigned long long)counters[DBTK_C_FEASIBLE],
+                     (unsigned long long)counters[DBTK_C_ASGN], d.sec);
+            fputs(blk, stderr);
+            if (!o.noTrkmc && dbtk_write_outputs(rpgg, counts.data(), kmc.data(), nmapread.data(), sm.prefix.c_str(), o.cohortNames)) {
+                const std::string err = dbtk_last_error();  // no partial file stays behind
+                for (const char* ext : {".trkmc.ar", ".tr.summary.txt", ".tr.kmers"}) (void)unlink((sm.prefix + ext).c_str());
+                die_assert(err);
             }
-        flush_left();
-        fprintf(stderr, "cross-range pairing: %llu reads\n", (unsigned long long)nleft);
-    }
+            if (dbtk_ctx_reset(d.c)) die_assert(dbtk_last_error());
+            tl_cohort_sample.clear();
+            cohort_finish_s += now() - t0;
+        };
+        std::thread finisher;
+        if (cohort_nctx == 2)
+            finisher = std::thread([&] {
+                for (;;) {
+                    Done d;
+                    {
+                        std::unique_lock<std::mutex> l(fm);
+                        fcv.wait(l, [&] { return !fq_.empty() || fstop; });
+                        if (fq_.empty()) return;
+                        d = fq_.front(); fq_.pop_front();
+                    }
+                    finish(d);
+                    { std::lock_guard<std::mutex> l(fm); ++nfinished; }
+                    fcv.notify_all();
+                }
+            });
+        finisher_id = finisher.get_id();
+        // what die_assert waits for: the samples handed to the finisher before the failing one.  When the finisher itself fails it waits
+        // for nothing, and tells a reader thread that may be draining at this moment not to wait for it either.
+        g_cohort_drain = [&] {
+            if (std::this_thread::get_id() == finisher_id) {
+                { std::lock_guard<std::mutex> l(fm); finisher_failed = true; }
+                fcv.notify_all();
+                return;
+            }
+            std::unique_lock<std::mutex> l(fm);
+            fcv.wait(l, [&] { return nfinished == nqueued || finisher_failed; });
+        };
+        for (size_t i = 0; i < samples.size(); ++i) {
+            dbtk_ctx_t* cur = cohort_ctx[i % (size_t)cohort_nctx];
+            {   // the context's previous sample (i - 2) has left it
+                const double t0 = now();
+                std::unique_lock<std::mutex> l(fm);
+                fcv.wait(l, [&] { return nfinished + (size_t)cohort_nctx > i; });
+                cohort_wait_s += now() - t0;
+            }
+            g_cohort_sample = tag_of(i);
+            {   // FASTA or FASTQ by the first byte
+                FILE* f = fopen(samples[i].reads.c_str(), "rb");
+                if (!f) die_assert("cannot open the reads file");
+                const int c0 = fgetc(f);
+                fclose(f);
+                if (c0 != '>' && c0 != '@' && c0 != EOF) die_assert("neither FASTA ('>') nor FASTQ ('@')");
+                fq = c0 == '@';
+            }
+            o.fastxFname = samples[i].reads;
+            ctx[0] = cur;
+            nReads = 0;
+            handover_stream = nullptr;
+            const time_t ts = time(nullptr);
+            run_input();
+            { std::lock_guard<std::mutex> lk(tot_m); for (auto g : spent_ingests) dbtk_ingest_free(g); spent_ingests.clear(); }  // (its pinned buffers go to the next sample's reader)
+            const Done d{i, cur, nReads, (long)(time(nullptr) - ts)};
+            cohort_reads += nReads;
+            if (cohort_nctx == 2) {
+                { std::lock_guard<std::mutex> l(fm); fq_.push_back(d); ++nqueued; }
+                fcv.notify_all();
+            } else {
+                const double t0 = now();
+                finish(d);
+                cohort_wait_s += now() - t0;
+                ++nfinished; ++nqueued;
+            }
+        }
+        g_cohort_sample.clear();
+        nReads = cohort_reads;  // (the `ingest:` line below speaks of the whole run)
+        { std::lock_guard<std::mutex> l(fm); fstop = true; }
+        fcv.notify_all();
+        if (finisher.joinable()) finisher.join();
+        ctx[0] = cohort_ctx[0];
+        if (cohort_ctx[1]) ctx.push_back(cohort_ctx[1]);  // (freed with the others on the tidy way out)
+        if (pred) {  // what danbing-tk-pred does from here (pred.cpp:52-82), in its file layouts; its progress lines go to stderr here
+            const uint64_t ns = samples.size(), ntr = dbtk_pred_ntr(pred);
+            std::vector<float> mat(ns * ntrk), bias(ns * ntr);
+            std::string err;
+            if (dbtk_pred_matrix(pred, mat.data())) die_assert(dbtk_last_error());
+            if (!dbtk_pred_io::save_matrix(o.pred[1], mat.data(), ns, ntrk, stderr, &err)) die_assert(err);
+            if (dbtk_pred_correct(pred)) die_assert(dbtk_last_error());
+            if (dbtk_pred_matrix(pred, mat.data())) die_assert(dbtk_last_error());
+            if (!dbtk_pred_io::save_matrix(o.pred[2], mat.data(), ns, ntrk, stderr, &err)) die_assert(err);
+            if (dbtk_pred_bias(pred, bias.data())) die_assert(dbtk_last_error());
+            if (!dbtk_pred_io::save_bias_tsv(o.pred[3], bias.data(), ns, ntr, stderr, &err)) die_assert(err);
+        }
+        const double dt = now() - loop_t0;
+        fprintf(stderr, "cohort: %zu samples in %.2f s (%.3f s per sample)\n", samples.size(), dt, dt / samples.size());
+        if (getenv("DBTK_VERBOSE"))
+            fprintf(stderr, "cohort: finishing the samples (pred column, counts to the host, files, reset) took %.3f s on %s; the reader waited %.3f s of it with the GPU idle (%.1f %% of the run)\n",
+                    cohort_finish_s, cohort_nctx == 2 ? "the finisher thread, beside the next sample's batch loop" : "the one thread (DBTK_COHORT_CONTEXTS=1)", cohort_wait_s, 100 * cohort_wait_s / dt);
+        g_cohort_drain = nullptr;
+    } else run_input();
     fflush(stdout);
     const double t_tail0 = now();
     { std::lock_guard<std::mutex> l(ep_m); ep_stop = true; }
@@ -1591,69 +1881,71 @@ int main(int argc, char* argv[]) {
         dbtk_rpgg_free(rpgg);
         return 0;
     }
-    // ---- totals + dumps (AQ.cpp:2611-2656)
+    // ---- totals + dumps (AQ.cpp:2611-2656); cohort mode has written each sample's as it went
     const double t_out = wall();
-    const int nctx = (int)ctx.size();
-    std::vector<uint64_t> counts(dbtk_rpgg_ntrkmers(rpgg)), kmc(nloci), counters(DBTK_C_COUNT);
-    std::vector<uint32_t> nmapread(nloci);
-    if (nctx == o.ngpus) {  // one context per GPU: the sum is RCCL's (AQ.cpp:2146-2158 across devices)
-        if (o.ngpus > 1 && dbtk_allreduce(ctx.data(), o.ngpus)) die_assert(dbtk_last_error());
-        if (dbtk_ctx_counts(ctx[0], counts.data(), kmc.data(), nmapread.data(), counters.data())) die_assert(dbtk_last_error());
-    } else {  // several contexts per GPU (--ingest-shards): their accumulators are summed on the host
-        std::vector<uint64_t> c1(counts.size()), k1(nloci), r1(DBTK_C_COUNT);
-        std::vector<uint32_t> n1(nloci);
-        for (int d = 0; d < nctx; ++d) {
-            if (dbtk_ctx_counts(ctx[d], c1.data(), k1.data(), n1.data(), r1.data())) die_assert(dbtk_last_error());
-            for (size_t i = 0; i < counts.size(); ++i) counts[i] += c1[i];
-            for (uint64_t l = 0; l < nloci; ++l) { kmc[l] += k1[l]; nmapread[l] += n1[l]; }
-            for (int i = 0; i < DBTK_C_COUNT; ++i) counters[i] += r1[i];
-        }
-    }
-    {   // which kernels took the pairs (a diagnostic of this implementation, free-form like the rest of stderr)
-        uint64_t ps[DBTK_PATH_STATS] = {0}, one[DBTK_PATH_STATS];
-        for (int d = 0; d < nctx; ++d) { const int n = dbtk_ctx_path_stats(ctx[d], one, (int)DBTK_PATH_STATS); for (int i = 0; i < n; ++i) ps[i] += one[i]; }
-        fprintf(stderr, "kernel paths: locus-resident probe %llu pairs in %llu items (%llu resolved there, %llu taken back), lean probe %llu pairs; locus-resident walk %llu pairs in %llu items, global walk %llu pairs\n",
-                (unsigned long long)(ps[3] + ps[4] + ps[5]), (unsigned long long)(ps[0] + ps[1] + ps[2]), (unsigned long long)ps[14], (unsigned long long)ps[15], (unsigned long long)ps[6],
-                (unsigned long long)(ps[10] + ps[11] + ps[12]), (unsigned long long)(ps[7] + ps[8] + ps[9]), (unsigned long long)ps[13]);
-    }
-    fprintf(stderr,
-            "%llu reads processed in total.\n%llu reads removed by subsampled kmer-filter.\n%llu reads removed by kmer-filter.\n"
-            "%llu reads removed by bait locus.\n%llu reads removed by qual filter.\n%llu reads removed during locus assignment.\n"
-            "%llu reads removed by QC filter.\n%llu reads entered threading step.\n%llu reads passsed threading.\n"
-            "%llu reads assigned to TR region.\nparallel query completed in %ld sec.\n",
-            (unsigned long long)nReads, (unsigned long long)counters[DBTK_C_SUBFILTERED], (unsigned long long)counters[DBTK_C_KMERFILTERED],
-            (unsigned long long)counters[DBTK_C_BAITFILTERED], (unsigned long long)counters[DBTK_C_QUALFILTERED],
-            (unsigned long long)counters[DBTK_C_LOCUSFILTERED], (unsigned long long)counters[DBTK_C_QCFILTERED],
-            (unsigned long long)counters[DBTK_C_THREADING], (unsigned long long)counters[DBTK_C_FEASIBLE],
-            (unsigned long long)counters[DBTK_C_ASGN], (long)(time(nullptr) - time1));
-    if (!o.extractFastX) {
-        fprintf(stderr, "writing kmers...\n");
-        if (dbtk_write_outputs(rpgg, counts.data(), kmc.data(), nmapread.data(), o.outPrefix.c_str(), o.writeKmerName))
-            die_assert(dbtk_last_error());
-        if (P.trackbait) {  // dumpBaitKmerHits, AQ.cpp:2652-2655
-            fprintf(stderr, "writing bait kmer hit statistics...\n");
-            for (int d = 1; d < nctx; ++d) if (dbtk_ctx_merge_bait_hits(ctx[0], ctx[d])) die_assert(dbtk_last_error());
-            if (dbtk_ctx_write_bait_hits(ctx[0], o.outPrefix.c_str())) die_assert(dbtk_last_error());
-        } else if (o.trackBait) {
-            // -tb where the bait filter never runs (no -b, or -g): the reference still dumps its tracker — sized nloci when -b
-            // read a bait DB (AQ.cpp:2496-2499), empty otherwise
-            fprintf(stderr, "writing bait kmer hit statistics...\n");
-            const uint64_t nl = o.bait ? nloci : 0, zero = 0, szv = 8;
-            FILE* f = fopen((o.outPrefix + ".btk.kmdb").c_str(), "wb");
-            if (!f) die_assert("cannot create " + o.outPrefix + ".btk.kmdb");
-            fwrite(&nl, 8, 1, f);
-            for (uint64_t l = 0; l < nl; ++l) fwrite(&zero, 8, 1, f);
-            fwrite(&zero, 8, 1, f); fwrite(&szv, 8, 1, f);
-            fclose(f);
-        }
-        if (o.outputBubbles) {  // dumpBubbles, AQ.cpp:2648-2651
-            fprintf(stderr, "writing bubbles...\n");
-            if (P.bubbles) {
-                for (int d = 1; d < nctx; ++d) if (dbtk_ctx_merge_bubbles(ctx[0], ctx[d])) die_assert(dbtk_last_error());
-                if (dbtk_ctx_write_bubbles(ctx[0], o.outPrefix.c_str())) die_assert(dbtk_last_error());
+    if (!cohort) {
+        const int nctx = (int)ctx.size();
+        std::vector<uint64_t> counts(dbtk_rpgg_ntrkmers(rpgg)), kmc(nloci), counters(DBTK_C_COUNT);
+        std::vector<uint32_t> nmapread(nloci);
+        if (nctx == o.ngpus) {  // one context per GPU: the sum is RCCL's (AQ.cpp:2146-2158 across devices)
+            if (o.ngpus > 1 && dbtk_allreduce(ctx.data(), o.ngpus)) die_assert(dbtk_last_error());
+            if (dbtk_ctx_counts(ctx[0], counts.data(), kmc.data(), nmapread.data(), counters.data())) die_assert(dbtk_last_error());
+        } else {  // several contexts per GPU (--ingest-shards): their accumulators are summed on the host
+            std::vector<uint64_t> c1(counts.size()), k1(nloci), r1(DBTK_C_COUNT);
+            std::vector<uint32_t> n1(nloci);
+            for (int d = 0; d < nctx; ++d) {
+                if (dbtk_ctx_counts(ctx[d], c1.data(), k1.data(), n1.data(), r1.data())) die_assert(dbtk_last_error());
+                for (size_t i = 0; i < counts.size(); ++i) counts[i] += c1[i];
+                for (uint64_t l = 0; l < nloci; ++l) { kmc[l] += k1[l]; nmapread[l] += n1[l]; }
+                for (int i = 0; i < DBTK_C_COUNT; ++i) counters[i] += r1[i];
             }
         }
-    }
+        {   // which kernels took the pairs (a diagnostic of this implementation, free-form like the rest of stderr)
+            uint64_t ps[DBTK_PATH_STATS] = {0}, one[DBTK_PATH_STATS];
+            for (int d = 0; d < nctx; ++d) { const int n = dbtk_ctx_path_stats(ctx[d], one, (int)DBTK_PATH_STATS); for (int i = 0; i < n; ++i) ps[i] += one[i]; }
+            fprintf(stderr, "kernel paths: locus-resident probe %llu pairs in %llu items (%llu resolved there, %llu taken back), lean probe %llu pairs; locus-resident walk %llu pairs in %llu items, global walk %llu pairs\n",
+                    (unsigned long long)(ps[3] + ps[4] + ps[5]), (unsigned long long)(ps[0] + ps[1] + ps[2]), (unsigned long long)ps[14], (unsigned long long)ps[15], (unsigned long long)ps[6],
+                    (unsigned long long)(ps[10] + ps[11] + ps[12]), (unsigned long long)(ps[7] + ps[8] + ps[9]), (unsigned long long)ps[13]);
+        }
+        fprintf(stderr,
+                "%llu reads processed in total.\n%llu reads removed by subsampled kmer-filter.\n%llu reads removed by kmer-filter.\n"
+                "%llu reads removed by bait locus.\n%llu reads removed by qual filter.\n%llu reads removed during locus assignment.\n"
+                "%llu reads removed by QC filter.\n%llu reads entered threading step.\n%llu reads passsed threading.\n"
+                "%llu reads assigned to TR region.\nparallel query completed in %ld sec.\n",
+                (unsigned long long)nReads, (unsigned long long)counters[DBTK_C_SUBFILTERED], (unsigned long long)counters[DBTK_C_KMERFILTERED],
+                (unsigned long long)counters[DBTK_C_BAITFILTERED], (unsigned long long)counters[DBTK_C_QUALFILTERED],
+                (unsigned long long)counters[DBTK_C_LOCUSFILTERED], (unsigned long long)counters[DBTK_C_QCFILTERED],
+                (unsigned long long)counters[DBTK_C_THREADING], (unsigned long long)counters[DBTK_C_FEASIBLE],
+                (unsigned long long)counters[DBTK_C_ASGN], (long)(time(nullptr) - time1));
+        if (!o.extractFastX) {
+            fprintf(stderr, "writing kmers...\n");
+            if (dbtk_write_outputs(rpgg, counts.data(), kmc.data(), nmapread.data(), o.outPrefix.c_str(), o.writeKmerName))
+                die_assert(dbtk_last_error());
+            if (P.trackbait) {  // dumpBaitKmerHits, AQ.cpp:2652-2655
+                fprintf(stderr, "writing bait kmer hit statistics...\n");
+                for (int d = 1; d < nctx; ++d) if (dbtk_ctx_merge_bait_hits(ctx[0], ctx[d])) die_assert(dbtk_last_error());
+                if (dbtk_ctx_write_bait_hits(ctx[0], o.outPrefix.c_str())) die_assert(dbtk_last_error());
+            } else if (o.trackBait) {
+                // -tb where the bait filter never runs (no -b, or -g): the reference still dumps its tracker — sized nloci when -b
+                // read a bait DB (AQ.cpp:2496-2499), empty otherwise
+                fprintf(stderr, "writing bait kmer hit statistics...\n");
+                const uint64_t nl = o.bait ? nloci : 0, zero = 0, szv = 8;
+                FILE* f = fopen((o.outPrefix + ".btk.kmdb").c_str(), "wb");
+                if (!f) die_assert("cannot create " + o.outPrefix + ".btk.kmdb");
+                fwrite(&nl, 8, 1, f);
+                for (uint64_t l = 0; l < nl; ++l) fwrite(&zero, 8, 1, f);
+                fwrite(&zero, 8, 1, f); fwrite(&szv, 8, 1, f);
+                fclose(f);
+            }
+            if (o.outputBubbles) {  // dumpBubbles, AQ.cpp:2648-2651
+                fprintf(stderr, "writing bubbles...\n");
+                if (P.bubbles) {
+                    for (int d = 1; d < nctx; ++d) if (dbtk_ctx_merge_bubbles(ctx[0], ctx[d])) die_assert(dbtk_last_error());
+                    if (dbtk_ctx_write_bubbles(ctx[0], o.outPrefix.c_str())) die_assert(dbtk_last_error());
+                }
+            }
+        }
+    }  // (!cohort)
     // Every output is written and closed.  Handing 28 - 47 GB of HBM tables, the pinned buffers and the 3 GB of the handle back piece by
     // piece takes 0.2 - 0.3 s of a run whose batch loop takes as long: the process ends here and the driver reclaims them at once
     // (DBTK_TIDY_EXIT=1: free everything first — leak checkers, make asan).  A process that runs under a tool which flushes its data in
@@ -1665,6 +1957,7 @@ int main(int argc, char* argv[]) {
                       getenv("HSA_TOOLS_LIB") || getenv("GCOV_PREFIX");
     if (tidy) {
         for (auto g : spent_ingests) dbtk_ingest_free(g);
+        if (pred) dbtk_pred_free(pred);
         for (auto c : ctx) dbtk_ctx_free(c);
         dbtk_rpgg_free(rpgg);
     }

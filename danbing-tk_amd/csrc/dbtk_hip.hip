@@ -2882,3 +2882,13 @@ dbtk_status_t dbtk_ingest_aln_lines(dbtk_ingest_t* g, uint32_t slot, dbtk_ctx_t*
 }
 
 }  // extern "C"
+
+// (dbtk_internal.h: for dbtk_pred_load_ctx)
+dbtk_status_t dbtk::ctx_facts(const dbtk_ctx_t* c, dbtk::CtxFacts* out) {
+    if (!c || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
+    out->device = c->device; out->ntrkmers = c->ntr;
+    out->unflushed_pairs = c->m_pairs + c->alt.m_pairs;
+    for (auto& l : c->parked) out->unflushed_pairs += l.m_pairs;
+    return DBTK_OK;
+}
+

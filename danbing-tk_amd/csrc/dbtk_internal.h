@@ -54,6 +54,10 @@ template <class F> dbtk_status_t guarded(F&& f) noexcept {
     catch (const std::exception& e) { set_error(std::string("internal error: ") + e.what()); return DBTK_ERR_FORMAT; }
     catch (...) { set_error("internal error"); return DBTK_ERR_FORMAT; }
 }
+// What dbtk_pred_load_ctx (dbtk_pred.hip) must know of a context and the public seam does not say: its device, the length of the
+// counts part of its accumulators, and the pairs appended by dbtk_ingest_align_merged (on any lane) that no batch has taken yet.
+struct CtxFacts { int device; uint64_t ntrkmers, unflushed_pairs; };
+dbtk_status_t ctx_facts(const dbtk_ctx_t* c, CtxFacts* out);
 }  // namespace dbtk
 
 #endif

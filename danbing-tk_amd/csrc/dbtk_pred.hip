@@ -51,6 +51,16 @@ __global__ void __launch_bounds__(64) k_pred_load(const uint64_t* __restrict__ c
     }
 }
 
+// ---- one sample whose counts are already in HBM (dbtk_pred_load_ctx / dbtk_pred_load_device with n = 1): column `sample` of G.
+// One lane per k-mer: the counts are read coalesced (8 bytes per lane), every store is 4 bytes into a row of its own (row stride
+// 4 * ns bytes), so the column costs nk partial-line writes.  Measured against the staged, LDS-turned form: kept,
+// because next to a sample's batch loop neither is visible and this one needs no staging buffer and no flush before G is read.
+// The arithmetic is k_pred_load's: one conversion, one division, both correctly rounded.
+__global__ void __launch_bounds__(256) k_pred_load_col(const uint64_t* __restrict__ counts, float depth, float* __restrict__ G, uint64_t nk, uint64_t ns, uint64_t sample) {
+    for (uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x; k < nk; k += (uint64_t)gridDim.x * 256)
+        G[k * ns + sample] = (float)counts[k] / depth;
+}
+
 // ---- bias_correction, first half (pred.h:217-228): B(s, j) = gt(s, iki[j]) / ikmc[j]; bias(s) = B.rowwise().mean(): the sum
 // over the locus' invariant k-mers in their order, per sample, then / n.  One lane per sample: row iki[j] of G is read
 // coalesced, the adds of a lane are sequential (the order Eigen's scalar reduction takes).
@@ -115,6 +125,7 @@ struct dbtk_pred {
     uint32_t *d_nk = nullptr, *d_nik = nullptr, *d_iki = nullptr, *d_loc = nullptr;  // d_loc[k]: locus of k-mer k, NOLOC where bias_correction skips it
     float* d_ikmc = nullptr;
     uint64_t* d_counts = nullptr; float* d_depth = nullptr; uint64_t stage_cap = 0;  // staging of dbtk_pred_load_samples
+    float* d_depth2 = nullptr; uint64_t depth_cap = 0;                                 // the depths of dbtk_pred_load_device
     hipStream_t stream = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     float ms[3] = {0, 0, 0};
@@ -152,7 +163,15 @@ static dbtk_status_t dbtk_pred_create_impl(int device_id, uint64_t ns, uint64_t 
     hipError_t e;
     if ((e = hipStreamCreate(&p->stream)) != hipSuccess) fail(e, "hipStreamCreate");
     for (int i = 0; i < 4 && !st; ++i) if ((e = hipEventCreate(&p->ev[i])) != hipSuccess) fail(e, "hipEventCreate");
-    if (!st && (e = hipMalloc(&p->d_G, nk * ns * sizeof(float))) != hipSuccess) fail(e, "hipMalloc (genotype matrix)");
+    if (!st && (e = hipMalloc(&p->d_G, nk * ns * sizeof(float))) != hipSuccess) {
+        if (e == hipErrorOutOfMemory) {  // the one allocation of this handle that competes with an aligner's tables for the HBM
+            (void)hipGetLastError();
+            size_t fr = 0, tot = 0;
+            (void)hipMemGetInfo(&fr, &tot);
+            set_error("genotype matrix: 4 * nk * ns = " + std::to_string(nk * ns * sizeof(float)) + " bytes do not fit, " + std::to_string(fr) + " of " + std::to_string(tot) + " bytes of HBM are free");
+            st = DBTK_ERR_NOMEM;
+        } else fail(e, "hipMalloc (genotype matrix)");
+    }
     if (!st && (e = hipMalloc(&p->d_bias, ntr * ns * sizeof(float))) != hipSuccess) fail(e, "hipMalloc (bias matrix)");
     if (!st && (e = hipMalloc(&p->d_nk, ntr * 4)) != hipSuccess) fail(e, "hipMalloc");
     if (!st && (e = hipMalloc(&p->d_nik, ntr * 4)) != hipSuccess) fail(e, "hipMalloc");
@@ -175,7 +194,7 @@ static dbtk_status_t dbtk_pred_create_impl(int device_id, uint64_t ns, uint64_t 
 void dbtk_pred_free(dbtk_pred_t* p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
-    void* ptrs[] = {p->d_G, p->d_bias, p->d_nk, p->d_nik, p->d_iki, p->d_loc, p->d_ikmc, p->d_counts, p->d_depth};
+    void* ptrs[] = {p->d_G, p->d_bias, p->d_nk, p->d_nik, p->d_iki, p->d_loc, p->d_ikmc, p->d_counts, p->d_depth, p->d_depth2};
     for (void* q : ptrs) if (q) (void)hipFree(q);
     for (auto& e : p->ev) if (e) (void)hipEventDestroy(e);
     if (p->stream) (void)hipStreamDestroy(p->stream);
@@ -231,6 +250,71 @@ static dbtk_status_t dbtk_pred_load_samples_impl(dbtk_pred_t* p, uint64_t first_
     hipLaunchKernelGGL(k_pred_load, dim3((uint32_t)kt, gy), dim3(64), 0, p->stream, p->d_counts, p->d_depth, p->d_G, p->nk, p->ns, first_sample, (uint32_t)n);
     PCHK(hipGetLastError());
     PCHK(hipStreamSynchronize(p->stream));  // (the caller's buffers are free again)
+    return DBTK_OK;
+}
+
+// counts of n samples in device memory -> their columns; asynchronous on p->stream.  One sample: the column kernel; more: the tile
+// kernel (the depths travel through p->d_depth2, a buffer of its own: p->d_depth belongs to dbtk_pred_load_samples' staging and is
+// sized with it).
+static dbtk_status_t pred_load_device_async(dbtk_pred_t* p, uint64_t first_sample, uint64_t n, const uint64_t* d_counts, const float* read_depth) {
+    if (n == 1) {
+        const uint32_t nb = (uint32_t)std::min<uint64_t>((p->nk + 255) / 256, 1u << 16);
+        hipLaunchKernelGGL(k_pred_load_col, dim3(nb), dim3(256), 0, p->stream, d_counts, read_depth[0], p->d_G, p->nk, p->ns, first_sample);
+        PCHK(hipGetLastError());
+        return DBTK_OK;
+    }
+    if (n > p->depth_cap) {
+        if (p->d_depth2) PCHK(hipFree(p->d_depth2));
+        p->d_depth2 = nullptr; p->depth_cap = 0;
+        PCHK(hipMalloc(&p->d_depth2, n * 4));
+        p->depth_cap = n;
+    }
+    PCHK(hipMemcpyAsync(p->d_depth2, read_depth, n * 4, hipMemcpyHostToDevice, p->stream));
+    const uint64_t kt = (p->nk + PT_K - 1) / PT_K;
+    if (kt > 0x7FFFFFFFull) { set_error("too many k-mers for one launch"); return DBTK_ERR_ARG; }
+    const uint32_t gy = (uint32_t)std::min<uint64_t>((n + PT_S - 1) / PT_S, 64);
+    hipLaunchKernelGGL(k_pred_load, dim3((uint32_t)kt, gy), dim3(64), 0, p->stream, d_counts, p->d_depth2, p->d_G, p->nk, p->ns, first_sample, (uint32_t)n);
+    PCHK(hipGetLastError());
+    return DBTK_OK;
+}
+
+dbtk_status_t dbtk_pred_load_device(dbtk_pred_t* p, uint64_t first_sample, uint64_t n, const uint64_t* d_counts, const float* read_depth) {
+    if (!p || !d_counts || !read_depth) { set_error("null argument"); return DBTK_ERR_ARG; }
+    if (first_sample > p->ns || n > p->ns - first_sample || n > 0xFFFFFFFFull) { set_error("sample range outside the cohort"); return DBTK_ERR_ARG; }
+    if (!n) return DBTK_OK;
+    PCHK(hipSetDevice(p->device));
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, d_counts) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != p->device) {
+        (void)hipGetLastError();
+        set_error("dbtk_pred_load_device: d_counts is not device memory of the handle's device");
+        return DBTK_ERR_ARG;
+    }
+    const dbtk_status_t st = pred_load_device_async(p, first_sample, n, d_counts, read_depth);
+    if (st) return st;
+    PCHK(hipStreamSynchronize(p->stream));  // (d_counts is no longer being read)
+    return DBTK_OK;
+}
+
+dbtk_status_t dbtk_pred_load_ctx(dbtk_pred_t* p, uint64_t sample, dbtk_ctx_t* ctx, float read_depth) {
+    if (!p || !ctx) { set_error("null argument"); return DBTK_ERR_ARG; }
+    CtxFacts f;
+    { const dbtk_status_t st = ctx_facts(ctx, &f); if (st) return st; }
+    if (sample >= p->ns) { set_error("sample outside the cohort"); return DBTK_ERR_ARG; }
+    if (f.ntrkmers != p->nk) { set_error("the context counts " + std::to_string(f.ntrkmers) + " TR k-mers, ikmer.meta has " + std::to_string(p->nk) + ": not the same RPGG build"); return DBTK_ERR_ARG; }
+    if (f.device != p->device) { set_error("the context is on device " + std::to_string(f.device) + ", the matrix on device " + std::to_string(p->device)); return DBTK_ERR_ARG; }
+    if (f.unflushed_pairs) {
+        set_error(std::to_string(f.unflushed_pairs) + " pairs appended by dbtk_ingest_align_merged are not aligned yet: flush them first (slot = ~0u, flush = 1)");
+        return DBTK_ERR_ARG;
+    }
+    // every batch done, the counter replicas folded, and a pending sticky error word reported instead of a tainted column
+    { const dbtk_status_t st = dbtk_ctx_synchronize(ctx); if (st) return st; }
+    void* base = nullptr; uint64_t n64 = 0;
+    { const dbtk_status_t st = dbtk_ctx_accum_buffer(ctx, &base, &n64); if (st) return st; }
+    if (!base || n64 < p->nk) { set_error("the context has no accumulators"); return DBTK_ERR_ARG; }
+    PCHK(hipSetDevice(p->device));
+    const dbtk_status_t st = pred_load_device_async(p, sample, 1, (const uint64_t*)base, &read_depth);
+    if (st) return st;
+    PCHK(hipStreamSynchronize(p->stream));  // (d_accum is no longer being read: dbtk_ctx_reset may follow)
     return DBTK_OK;
 }
 

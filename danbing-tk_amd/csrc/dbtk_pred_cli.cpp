@@ -11,18 +11,14 @@
 #include <vector>
 
 #include "../../include/dbtk_pred.h"
+#include "dbtk_pred_io.h"
 
 static void die(const std::string& m, int code = 1) { fprintf(stderr, "%s\n", m.c_str()); exit(code); }
 
-// save_matrix (pred.h:236-249): the low 4 bytes of rows and columns, then the column-major float32 data
+// the two file layouts live in dbtk_pred_io.h (shared with `danbing-tk --cohort --pred`); a failure ends the process here
 static void save_matrix(const std::string& fn, const float* d, uint64_t nrow, uint64_t ncol) {
-    printf("saving matrix to %s\n", fn.c_str());
-    FILE* f = fopen(fn.c_str(), "wb");
-    if (!f) die("cannot create " + fn);
-    const uint32_t r = (uint32_t)nrow, c = (uint32_t)ncol;
-    bool ok = fwrite(&r, 4, 1, f) == 1 && fwrite(&c, 4, 1, f) == 1 && fwrite(d, 4, nrow * ncol, f) == nrow * ncol;
-    if (fclose(f) || !ok) die("write error on " + fn);
-    printf("matrix dim: (%llu,%llu) size: %llu bytes\n", (unsigned long long)nrow, (unsigned long long)ncol, (unsigned long long)(nrow * ncol * 4));
+    std::string err;
+    if (!dbtk_pred_io::save_matrix(fn, d, nrow, ncol, stdout, &err)) die(err);
 }
 
 int main(int argc, char** argv) {
@@ -94,23 +90,9 @@ int main(int argc, char** argv) {
     save_matrix(fout, mat.data(), ns, nk);
     std::vector<float> bias(ns * ntr);
     if (dbtk_pred_bias(P, bias.data())) die(dbtk_last_error());
-    {   // save_matrix with the tsv format (pred.cpp:51, pred.h:251-258): rows = samples, tab-separated, default stream precision, no final newline
-        printf("saving matrix to %s\n", foutBias.c_str());
-        FILE* f = fopen(foutBias.c_str(), "w");
-        if (!f) die("cannot create " + foutBias);
-        std::string line;
-        char num[64];
-        for (uint64_t s = 0; s < ns; ++s) {
-            line.clear();
-            for (uint64_t t = 0; t < ntr; ++t) {
-                snprintf(num, sizeof num, "%g", (double)bias[t * ns + s]);
-                if (t) line += '\t';
-                line += num;
-            }
-            if (s + 1 < ns) line += '\n';
-            fwrite(line.data(), 1, line.size(), f);
-        }
-        if (fclose(f)) die("write error on " + foutBias);
+    {
+        std::string err;
+        if (!dbtk_pred_io::save_bias_tsv(foutBias, bias.data(), ns, ntr, stdout, &err)) die(err);
     }
     dbtk_pred_free(P);
     return 0;

@@ -34,7 +34,8 @@ typedef struct dbtk_pred dbtk_pred_t;
 /* The invariant-k-mer metadata of an RPGG build (read_ikmer, pred.h:64-126: `ikmer.meta`): per locus the CUMULATIVE number
  * of k-mers (nk_cum[ntr], nk_cum[ntr-1] == nk) and of invariant k-mers (nik_cum[ntr], nik_cum[ntr-1] == nik); per invariant
  * k-mer its column (iki[nik] < nk) and its expected count (ikmc[nik]).  The matrix G[nk][ns] (float32, 4*nk*ns bytes) lives
- * in HBM. */
+ * in HBM.  DBTK_ERR_NOMEM (ABI v9; DBTK_ERR_HIP before) when the matrix does not fit into the device's free HBM: the message
+ * holds its size and the free and total bytes of the device; every other failed HIP call stays DBTK_ERR_HIP. */
 dbtk_status_t dbtk_pred_create(int device_id, uint64_t ns, uint64_t nk, uint64_t ntr, const uint32_t* nk_cum, const uint32_t* nik_cum,
                                uint64_t nik, const uint32_t* iki, const uint8_t* ikmc, dbtk_pred_t** out);
 void dbtk_pred_free(dbtk_pred_t* p);
@@ -48,6 +49,25 @@ uint64_t dbtk_pred_ntr(const dbtk_pred_t* p);
 /* Samples first_sample .. first_sample + n - 1: counts[i * nk + k] = count of k-mer k in sample i (the body of its
  * OUT.trkmc.ar), read_depth[i] its depth.  load_eachBinGT + norm_rd for these columns: G[k][s] = (float)count / depth. */
 dbtk_status_t dbtk_pred_load_samples(dbtk_pred_t* p, uint64_t first_sample, uint64_t n, const uint64_t* counts, const float* read_depth);
+
+/* The same for counts that are already in DEVICE memory of the handle's device (ABI v9): d_counts[i * nk + k], sample-major like
+ * the host form; read_depth[n] is HOST memory.  Bit-identical to dbtk_pred_load_samples fed the same counts.  Samples may be
+ * loaded in any order and a column may be loaded again (the later load wins).  n == 1 takes the column kernel (nk 4-byte stores
+ * at a stride of 4 * ns bytes), n > 1 the LDS-turned tiles of dbtk_pred_load_samples; nothing is staged inside the handle, so
+ * dbtk_pred_correct / _matrix / _bias always see every load that has returned.
+ * Stream ordering: the kernel runs on the handle's own stream, which is NOT ordered against the stream that produced d_counts:
+ * the counts must be complete before the call.  The call returns when d_counts is no longer being read. */
+dbtk_status_t dbtk_pred_load_device(dbtk_pred_t* p, uint64_t first_sample, uint64_t n, const uint64_t* d_counts, const float* read_depth);
+/* Column `sample` of G from the context's accumulated counts — what dbtk_ctx_counts would copy to the host, in OUT.trkmc.ar
+ * order — divided by read_depth, without the counts leaving HBM.  Goes through dbtk_ctx_synchronize and dbtk_ctx_accum_buffer:
+ * every batch launched on the context is waited for; a pending sticky error word (DBTK_ERR_READ_TOO_LONG, ...) is returned, once,
+ * INSTEAD of loading the tainted counts.  DBTK_ERR_ARG when the context's ntrkmers differs from the handle's nk, when the two are
+ * on different devices, when sample >= ns — and when pairs appended by dbtk_ingest_align_merged have not been aligned yet: the
+ * call REFUSES rather than flushes them (the flush belongs to the ingest that holds the blocks; dbtk_ctx_synchronize does not
+ * see those pairs): call dbtk_ingest_align_merged(ing, ~0u, ctx, 0, 1) first.  The column is not touched by a refused call.
+ * Returns when the context's accumulators are no longer being read: a dbtk_ctx_reset right after it is safe.  Like every call
+ * on a context, it must come from the one thread that owns the context at the time. */
+dbtk_status_t dbtk_pred_load_ctx(dbtk_pred_t* p, uint64_t sample, dbtk_ctx_t* ctx, float read_depth);
 
 /* bias_correction (pred.h:212-233) on the loaded matrix, in place; fills the bias matrix.  A locus without k-mers or
  * without invariant k-mers is left alone (the reference `continue`s and leaves its Bias column uninitialised: 0 here). */
