@@ -435,6 +435,13 @@ EXPORTS_PRED = [
     "dbtk_pred_correct", "dbtk_pred_matrix", "dbtk_pred_bias", "dbtk_pred_times",
 ]
 
+# ... and its dosage tables (ABI v10)
+EXPORTS_DOSAGE = [
+    "dbtk_dosage_create", "dbtk_dosage_create_from_file", "dbtk_dosage_create_from_rpgg", "dbtk_dosage_free", "dbtk_dosage_nk", "dbtk_dosage_ntr",
+    "dbtk_dosage_bytes", "dbtk_dosage_load_ctx", "dbtk_dosage_load_device", "dbtk_dosage_load_samples", "dbtk_dosage_finish", "dbtk_dosage_kms",
+    "dbtk_dosage_bias", "dbtk_dosage_values", "dbtk_dosage_times",
+]
+
 
 class Pred:
     """include/dbtk_pred.h through ctypes: the cohort matrix in HBM, normalisation and bias correction on the GPU."""
@@ -499,6 +506,93 @@ class Pred:
     def close(self):
         if self.h:
             self._lib.L.dbtk_pred_free(self.h)
+            self.h = None
+
+
+class Dosage:
+    """The dosage tables of include/dbtk_pred.h through ctypes: per sample and locus the exact k-mer sum (kms), the bias and the
+    bias-corrected dosage, without the cohort matrix.  Built from metadata arrays, from an ikmer.meta file (ikmer_meta=) or from a
+    loaded Rpgg (rpgg=: no invariant k-mers, every locus uncorrected)."""
+
+    def __init__(self, lib, ns, nk_cum=None, nik_cum=None, iki=None, ikmc=None, nk=None, device=0, ikmer_meta=None, rpgg=None):
+        self._lib = lib
+        L = lib.L
+        fp = C.POINTER(C.c_float)
+        L.dbtk_dosage_create.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, u32p, u32p, C.c_uint64, u32p, u8p, C.POINTER(C.c_void_p)]
+        L.dbtk_dosage_create_from_file.argtypes = [C.c_int, C.c_uint64, C.c_char_p, C.POINTER(C.c_void_p)]
+        L.dbtk_dosage_create_from_rpgg.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]
+        L.dbtk_dosage_free.argtypes = [C.c_void_p]
+        L.dbtk_dosage_free.restype = None
+        for f in (L.dbtk_dosage_nk, L.dbtk_dosage_ntr, L.dbtk_dosage_bytes):
+            f.argtypes = [C.c_void_p]
+            f.restype = C.c_uint64
+        L.dbtk_dosage_load_samples.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, u64p, fp]
+        L.dbtk_dosage_load_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, fp]
+        L.dbtk_dosage_load_ctx.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_float]
+        L.dbtk_dosage_finish.argtypes = [C.c_void_p]
+        L.dbtk_dosage_kms.argtypes = [C.c_void_p, u64p]
+        L.dbtk_dosage_bias.argtypes = [C.c_void_p, fp]
+        L.dbtk_dosage_values.argtypes = [C.c_void_p, fp]
+        L.dbtk_dosage_times.argtypes = [C.c_void_p, fp]
+        self.ns = int(ns)
+        self.h = C.c_void_p()
+        if rpgg is not None:
+            lib._chk(L.dbtk_dosage_create_from_rpgg(rpgg.h, device, self.ns, C.byref(self.h)))
+        elif ikmer_meta is not None:
+            lib._chk(L.dbtk_dosage_create_from_file(device, self.ns, os.fsencode(ikmer_meta), C.byref(self.h)))
+        else:
+            nk_cum = np.ascontiguousarray(nk_cum, np.uint32)
+            nik_cum = np.ascontiguousarray(nik_cum, np.uint32)
+            iki = np.ascontiguousarray(iki, np.uint32)
+            ikmc = np.ascontiguousarray(ikmc, np.uint8)
+            nk = int(nk if nk is not None else (nk_cum[-1] if len(nk_cum) else 0))
+            lib._chk(L.dbtk_dosage_create(device, self.ns, nk, len(nk_cum), _ptr(nk_cum, u32p), _ptr(nik_cum, u32p), len(iki), _ptr(iki, u32p), _ptr(ikmc, u8p),
+                                          C.byref(self.h)))
+        self.nk, self.ntr = int(L.dbtk_dosage_nk(self.h)), int(L.dbtk_dosage_ntr(self.h))
+
+    def nbytes(self):
+        return int(self._lib.L.dbtk_dosage_bytes(self.h))
+
+    def load(self, first, counts, depths):
+        counts = np.ascontiguousarray(counts, np.uint64)
+        depths = np.ascontiguousarray(depths, np.float32)
+        self._lib._chk(self._lib.L.dbtk_dosage_load_samples(self.h, first, counts.shape[0], _ptr(counts, u64p), depths.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def load_device(self, first, n, d_counts, depths):
+        depths = np.ascontiguousarray(depths, np.float32)
+        ptr = d_counts.data_ptr() if hasattr(d_counts, "data_ptr") else int(d_counts)
+        self._lib._chk(self._lib.L.dbtk_dosage_load_device(self.h, first, n, C.c_void_p(ptr), depths.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def load_ctx(self, sample, ctx, depth):
+        self._lib._chk(self._lib.L.dbtk_dosage_load_ctx(self.h, sample, ctx.h, float(depth)))
+
+    def finish(self):
+        self._lib._chk(self._lib.L.dbtk_dosage_finish(self.h))
+
+    def kms(self):
+        """uint64 [ntr][ns]: entry (locus, sample)."""
+        out = np.empty((self.ntr, self.ns), np.uint64)
+        self._lib._chk(self._lib.L.dbtk_dosage_kms(self.h, _ptr(out, u64p)))
+        return out
+
+    def bias(self):
+        out = np.empty((self.ntr, self.ns), np.float32)
+        self._lib._chk(self._lib.L.dbtk_dosage_bias(self.h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def values(self):
+        out = np.empty((self.ntr, self.ns), np.float32)
+        self._lib._chk(self._lib.L.dbtk_dosage_values(self.h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def times(self):
+        ms = (C.c_float * 2)()
+        self._lib._chk(self._lib.L.dbtk_dosage_times(self.h, ms))
+        return list(ms)
+
+    def close(self):
+        if self.h:
+            self._lib.L.dbtk_dosage_free(self.h)
             self.h = None
 
 

@@ -100,6 +100,8 @@ struct Opts {
     bool cohortNames = false;          // --cohort-names: OUT.tr.kmers per sample (the -on form)
     bool noTrkmc = false;              // --no-trkmc: no per-sample files; the counts never leave HBM
     std::vector<std::string> pred;     // --pred IKMER.META RAW.gt CORRECTED.gt BIAS.tsv
+    std::string kms;                   // --kms OUT.kms: the per-locus k-mer sums of every sample (the table of `ktools sum -f`)
+    std::vector<std::string> dosage;   // --dosage IKMER.META OUT.dosage.tsv OUT.bias.tsv: the bias-corrected per-locus dosages, without the matrix
 };
 struct CohortSample { std::string reads, prefix; float depth = 0; };
 
@@ -146,7 +148,13 @@ void usage() {
             "  --pred <IKMER.META> <RAW.gt> <CORRECTED.gt> <BIAS.tsv>\n"
             "                         after the last sample, what danbing-tk-pred does with their counts and the manifest's read depths\n"
             "                         (the counts go from the aligner into the genotype matrix without leaving the GPU)\n"
-            "  --no-trkmc             with --pred: write no per-sample files at all\n"
+            "  --kms <OUT.kms>        after the last sample, the sum of every locus' k-mer counts per sample: the table `ktools sum -f` makes\n"
+            "                         from the samples' count files (a row per sample, in manifest order); needs no read depth\n"
+            "  --dosage <IKMER.META> <OUT.dosage.tsv> <OUT.bias.tsv>\n"
+            "                         after the last sample, per sample and locus: k-mer sum / read depth / bias (uncorrected where the\n"
+            "                         locus has no invariant k-mers), and the bias table of --pred; neither needs the genotype matrix,\n"
+            "                         so the cohort's size is not bounded by it\n"
+            "  --no-trkmc             with --pred, --kms or --dosage: write no per-sample files at all\n"
             "Developer:\n"
             "  -s <1|2>  -e <1|2>  -v <INT>  -g|-gc|-gcc <INT> [INT]  -a  -ae  -tb  -ik  -t <INT>  -m <FILE>  -au\n\n");
 }
@@ -387,6 +395,8 @@ int main(int argc, char* argv[]) {
         else if (a == "--cohort-names") o.cohortNames = true;
         else if (a == "--no-trkmc") o.noTrkmc = true;
         else if (a == "--pred") { o.pred.clear(); for (int i = 0; i < 4; ++i) o.pred.push_back(need(++argi)); }
+        else if (a == "--kms") o.kms = need(++argi);
+        else if (a == "--dosage") { o.dosage.clear(); for (int i = 0; i < 3; ++i) o.dosage.push_back(need(++argi)); }
         else {
             fprintf(stderr, "invalid option: %s\n", a.c_str());
             abort();  // the reference does `throw;` with no active exception -> std::terminate
@@ -402,7 +412,9 @@ int main(int argc, char* argv[]) {
     if (!cohort) {
         if (o.cohortNames) refuse("--cohort-names needs --cohort");
         if (!o.pred.empty()) refuse("--pred needs --cohort (for count files that exist already there is danbing-tk-pred)");
-        if (o.noTrkmc) refuse("--no-trkmc needs --cohort and --pred");
+        if (!o.kms.empty()) refuse("--kms needs --cohort (for count files that exist already there are ktools sum and danbing-tk-pred --dosage --kms)");
+        if (!o.dosage.empty()) refuse("--dosage needs --cohort (for count files that exist already there is danbing-tk-pred --dosage)");
+        if (o.noTrkmc) refuse("--no-trkmc needs --cohort and --pred, --kms or --dosage");
     } else {
         if (!o.fastxFname.empty()) refuse("--cohort takes the place of -fa/-fq: the reads files are in the manifest");
         if (!o.outPrefix.empty()) refuse("--cohort takes the place of -o/-on: the output prefixes are in the manifest (--cohort-names for the -on form)");
@@ -417,7 +429,7 @@ int main(int argc, char* argv[]) {
         if (o.ingestShards > 1) refuse("--cohort reads one sample at a time: --ingest-shards is not supported with it");
         if (o.parseOnly) refuse("--cohort cannot be combined with --parse-only");
         if (o.threading && !o.v13) refuse("--cohort with -g/-gc/-gcc needs --v13-threading (without it those flags leave every count at zero)");
-        if (o.noTrkmc && o.pred.empty()) refuse("--cohort with --no-trkmc needs --pred: without it the run would write nothing");
+        if (o.noTrkmc && o.pred.empty() && o.kms.empty() && o.dosage.empty()) refuse("--cohort with --no-trkmc needs --pred, --kms or --dosage: without one the run would write nothing");
         FILE* mf = fopen(o.cohortFn.c_str(), "rb");
         if (!mf) refuse("--cohort: cannot open the manifest " + o.cohortFn);
         std::string text;
@@ -434,12 +446,14 @@ int main(int argc, char* argv[]) {
             std::vector<std::string> col;
             for (size_t p = 0;;) { const size_t t = line.find('\t', p); col.push_back(line.substr(p, t == std::string::npos ? t : t - p)); if (t == std::string::npos) break; p = t + 1; }
             const std::string where = "--cohort: " + o.cohortFn + " line " + std::to_string(lineno) + ": ";
-            const size_t needc = o.pred.empty() ? 2 : 3;
+            const bool need_depth = !o.pred.empty() || !o.dosage.empty();  // (--kms alone sums integers: no depth)
+            const size_t needc = need_depth ? 3 : 2;
             if (col.size() < needc || col[0].empty() || (col[1].empty() && !o.noTrkmc))
-                refuse(where + "expected reads file <TAB> output prefix" + (o.pred.empty() ? "" : " <TAB> read depth (--pred needs the depth)") + ", found " + std::to_string(col.size()) + " column(s)");
+                refuse(where + "expected reads file <TAB> output prefix" + (need_depth ? std::string(" <TAB> read depth (") + (o.pred.empty() ? "--dosage" : "--pred") + " needs the depth)" : std::string()) +
+                       ", found " + std::to_string(col.size()) + " column(s)");
             CohortSample sm;
             sm.reads = col[0]; sm.prefix = col[1];
-            if (!o.pred.empty()) {
+            if (need_depth) {
                 char* endp = nullptr;
                 errno = 0;
                 sm.depth = strtof(col[2].c_str(), &endp);
@@ -460,6 +474,15 @@ int main(int argc, char* argv[]) {
                 (void)unlink(o.pred[i].c_str());
             }
         }
+        // ... and the files of --dosage and --kms, in the same way
+        if (!o.dosage.empty() && !readable(o.dosage[0])) refuse("--dosage: cannot open " + o.dosage[0]);
+        for (const std::string* fn : {o.dosage.empty() ? nullptr : &o.dosage[1], o.dosage.empty() ? nullptr : &o.dosage[2], o.kms.empty() ? nullptr : &o.kms}) {
+            if (!fn) continue;
+            FILE* f = fopen(fn->c_str(), "wb");
+            if (!f) refuse(std::string(fn == &o.kms ? "--kms" : "--dosage") + ": cannot create " + *fn);
+            fclose(f);
+            (void)unlink(fn->c_str());
+        }
     }
 
     fprintf(stderr,
@@ -471,7 +494,8 @@ int main(int argc, char* argv[]) {
             (unsigned long long)o.N_FILTER, (unsigned long long)o.NM_FILTER, (unsigned long long)o.Cthreshold,
             (unsigned long long)o.NM_TR, cohort ? o.cohortFn.c_str() : o.fastxFname.c_str(), o.trPrefix.c_str(), o.ngpus);
     if (cohort) {
-        fprintf(stderr, "cohort: %zu samples%s%s\n\n", samples.size(), o.pred.empty() ? "" : ", genotype matrices to ", o.pred.empty() ? "" : o.pred[1].c_str());
+        fprintf(stderr, "cohort: %zu samples%s%s%s%s%s%s\n\n", samples.size(), o.pred.empty() ? "" : ", genotype matrices to ", o.pred.empty() ? "" : o.pred[1].c_str(),
+                o.dosage.empty() ? "" : ", dosage table to ", o.dosage.empty() ? "" : o.dosage[1].c_str(), o.kms.empty() ? "" : ", kms table to ", o.kms.c_str());
         o.fastxFname = samples[0].reads;  // (what the warm-up thread sizes the pinned buffers by)
     }
 
@@ -630,6 +654,7 @@ int main(int argc, char* argv[]) {
     int cohort_nctx = 2;
     if (const char* e = getenv("DBTK_COHORT_CONTEXTS")) if (atoi(e) == 1) cohort_nctx = 1;  // (measurements: what the second context buys)
     dbtk_pred_t* pred = nullptr;
+    dbtk_dosage_t *dosage = nullptr, *kms = nullptr;  // --dosage: from IKMER.META; --kms alone: from the RPGG's own locus boundaries
     if (cohort) {
         // what the run holds in HBM from here on, for the message when it does not fit: tables, accumulators, the matrix of --pred
         // (a context's batch scratch is allocated by its first batches and is not part of this)
@@ -639,7 +664,8 @@ int main(int argc, char* argv[]) {
             for (int i = 0; i < nt; ++i) if (strcmp(nm[i], "index_images:from_cache")) tsum += tb[i];
             return "the RPGG's tables hold " + std::to_string(tsum) + " bytes, " + std::to_string(cohort_nctx) + " contexts' accumulators " +
                    std::to_string((uint64_t)cohort_nctx * 8 * (dbtk_rpgg_ntrkmers(rpgg) + 2 * nloci + DBTK_C_COUNT)) + " bytes, the genotype matrix of --pred " +
-                   std::to_string(o.pred.empty() ? 0 : 4 * dbtk_rpgg_ntrkmers(rpgg) * (uint64_t)samples.size()) + " bytes";
+                   std::to_string(o.pred.empty() ? 0 : 4 * dbtk_rpgg_ntrkmers(rpgg) * (uint64_t)samples.size()) + " bytes, the per-locus tables of --dosage / --kms " +
+                   std::to_string(dbtk_dosage_bytes(dosage) + dbtk_dosage_bytes(kms)) + " bytes (of a handle that exists)";
         };
         if (cohort_nctx == 2 && dbtk_ctx_create(rpgg, &P, dev_of(0), &cohort_ctx[1])) {
             const std::string err = dbtk_last_error();
@@ -655,6 +681,21 @@ int main(int argc, char* argv[]) {
             if (dbtk_pred_nk(pred) != dbtk_rpgg_ntrkmers(rpgg))
                 die_assert(o.pred[0] + " describes " + std::to_string(dbtk_pred_nk(pred)) + " TR k-mers, " + o.trFname + " holds " + std::to_string(dbtk_rpgg_ntrkmers(rpgg)) + ": not the same RPGG build");
         }
+        // the per-locus tables: --dosage takes its loci from IKMER.META, --kms from the RPGG itself (a handle each: beside --dosage the
+        // second pass over a sample's counts costs a tenth of a millisecond, and OUT.kms never depends on the metadata file)
+        auto made = [&](dbtk_status_t ds) {
+            if (ds == DBTK_ERR_NOMEM) {
+                const std::string err = dbtk_last_error();  // (holds the size of the tables that did not fit)
+                die_assert("not enough HBM for the cohort: " + hbm_sizes() + "; " + err);
+            }
+            if (ds) die_assert(dbtk_last_error());
+        };
+        if (!o.dosage.empty()) {
+            made(dbtk_dosage_create_from_file(dev_of(0), samples.size(), o.dosage[0].c_str(), &dosage));
+            if (dbtk_dosage_nk(dosage) != dbtk_rpgg_ntrkmers(rpgg))
+                die_assert(o.dosage[0] + " describes " + std::to_string(dbtk_dosage_nk(dosage)) + " TR k-mers, " + o.trFname + " holds " + std::to_string(dbtk_rpgg_ntrkmers(rpgg)) + ": not the same RPGG build");
+        }
+        if (!o.kms.empty()) made(dbtk_dosage_create_from_rpgg(rpgg, dev_of(0), samples.size(), &kms));
     }
     fprintf(stderr, "load: RPGG files %.2f s, tables in HBM %.2f s\n", tl1 - tl0, wall() - tl1);
     if (pin_n && getenv("DBTK_VERBOSE")) fprintf(stderr, "pinned ahead: %u chunk buffers in %.3f s (beside the RPGG files)\n", pin_n, pin_s);
@@ -1745,6 +1786,8 @@ int main(int argc, char* argv[]) {
             const CohortSample& sm = samples[d.index];
             // (a sticky device error — an over-long read the device truncated — comes out of the first of these calls: no column, no file)
             if (pred && dbtk_pred_load_ctx(pred, d.index, d.c, sm.depth)) die_assert(dbtk_last_error());
+            if (dosage && dbtk_dosage_load_ctx(dosage, d.index, d.c, sm.depth)) die_assert(dbtk_last_error());
+            if (kms && dbtk_dosage_load_ctx(kms, d.index, d.c, 1.f)) die_assert(dbtk_last_error());
             if (dbtk_ctx_counts(d.c, o.noTrkmc ? nullptr : counts.data(), o.noTrkmc ? nullptr : kmc.data(), o.noTrkmc ? nullptr : nmapread.data(), counters.data()))
                 die_assert(dbtk_last_error());
             char blk[1024];
@@ -1852,6 +1895,23 @@ int main(int argc, char* argv[]) {
             if (dbtk_pred_bias(pred, bias.data())) die_assert(dbtk_last_error());
             if (!dbtk_pred_io::save_bias_tsv(o.pred[3], bias.data(), ns, ntr, stderr, &err)) die_assert(err);
         }
+        if (dosage) {  // what `danbing-tk-pred --dosage` writes from the samples' count files
+            const uint64_t ns = samples.size(), ntr = dbtk_dosage_ntr(dosage);
+            std::vector<float> tab(ns * ntr);
+            std::string err;
+            if (dbtk_dosage_finish(dosage)) die_assert(dbtk_last_error());
+            if (dbtk_dosage_values(dosage, tab.data())) die_assert(dbtk_last_error());
+            if (!dbtk_pred_io::save_bias_tsv(o.dosage[1], tab.data(), ns, ntr, stderr, &err)) die_assert(err);
+            if (dbtk_dosage_bias(dosage, tab.data())) die_assert(dbtk_last_error());
+            if (!dbtk_pred_io::save_bias_tsv(o.dosage[2], tab.data(), ns, ntr, stderr, &err)) die_assert(err);
+        }
+        if (kms) {
+            const uint64_t ns = samples.size(), ntr = dbtk_dosage_ntr(kms);
+            std::vector<uint64_t> tab(ns * ntr);
+            std::string err;
+            if (dbtk_dosage_kms(kms, tab.data())) die_assert(dbtk_last_error());
+            if (!dbtk_pred_io::save_kms(o.kms, tab.data(), ns, ntr, stderr, &err)) die_assert(err);
+        }
         const double dt = now() - loop_t0;
         fprintf(stderr, "cohort: %zu samples in %.2f s (%.3f s per sample)\n", samples.size(), dt, dt / samples.size());
         if (getenv("DBTK_VERBOSE"))
@@ -1958,6 +2018,8 @@ int main(int argc, char* argv[]) {
     if (tidy) {
         for (auto g : spent_ingests) dbtk_ingest_free(g);
         if (pred) dbtk_pred_free(pred);
+        dbtk_dosage_free(dosage);
+        dbtk_dosage_free(kms);
         for (auto c : ctx) dbtk_ctx_free(c);
         dbtk_rpgg_free(rpgg);
     }

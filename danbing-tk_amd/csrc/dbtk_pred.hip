@@ -117,6 +117,151 @@ __global__ void __launch_bounds__(256) k_pred_correct(float* __restrict__ G, con
     }
 }
 
+// ---- the dosage tables (dbtk_pred.h, ABI v10): one sample's counts -> its kms and raw-bias entries, locus by locus, in one pass.
+// The host cuts the k-mer axis into work items at locus boundaries (dosage_items): an item is a run of whole loci of at most DS_CH
+// k-mers together, or one DS_CH-sized part of a locus larger than that.  One block per item:
+//   1. the item's counts are read coalesced (8 bytes per lane) into LDS;
+//   2. an inclusive prefix sum over them, in uint64: a thread scans DS_E consecutive values, the thread totals are scanned across
+//      the wave with shuffles and across the four waves through LDS;
+//   3. one lane per locus: sum = P[end - 1] - P[begin - 1].  Exact (integers; the differences are exact modulo 2^64 whatever the
+//      running total does), and every lane works whether the item holds one locus of 2000 k-mers or 400 loci of 5;
+//      a part of a large locus writes its total to a partial slot instead, and k_dosage_fold adds the parts up;
+//   4. the raw bias of the item's loci.  The terms ((float)count[iki[j]] / depth) / ikmc[j] of the item's invariant k-mers — one
+//      contiguous range of j, the loci being consecutive — are gathered by all lanes into LDS, DS_TB at a time; then one lane
+//      per locus adds its terms from LDS sequentially in j and divides by n: the operations and the add order of k_pred_load_col
+//      + k_pred_bias (acc = 0; acc += G / ikmc; acc / n), so the result has the same bits.  Only the adds are ordered.
+// LDS: 18 KB of prefix sums (padded by one value per DS_E: the scan's 72-byte lane stride is 2-way conflicted instead of 16-way)
+// + 4 KB of terms.  No atomics: a column loaded again is simply overwritten.
+constexpr int DS_T = 256, DS_E = 8, DS_CH = DS_T * DS_E, DS_TB = 1024;
+constexpr uint32_t NOPART = 0xFFFFFFFFu;
+struct DosItem {
+    uint32_t k0, nkm;   // the item's k-mers: [k0, k0 + nkm), nkm <= DS_CH
+    uint32_t l0, nl;    // whole loci l0 .. l0 + nl - 1 lie in that range (nl = 0: a part of locus l0)
+    uint32_t part;      // NOPART, or the partial slot the range's total goes to
+    uint32_t nlb;       // loci from l0 on whose raw bias this item makes (nl; 1 for the first part of a large locus; 0 else, or without invariant k-mers)
+};
+__device__ __forceinline__ int ds_pad(uint32_t k) { return (int)(k + (k >> 3)); }
+
+__global__ void __launch_bounds__(DS_T) k_dosage_sample(const uint64_t* __restrict__ counts, float depth, const DosItem* __restrict__ items,
+                                                        const uint32_t* __restrict__ nk_cum, const uint32_t* __restrict__ nik_cum,
+                                                        const uint32_t* __restrict__ iki, const float* __restrict__ ikmc, uint64_t* __restrict__ kms,
+                                                        float* __restrict__ raw, uint64_t* __restrict__ part, uint64_t ns, uint64_t sample) {
+    __shared__ uint64_t P[DS_CH + DS_CH / DS_E];
+    __shared__ uint64_t wtot[DS_T / 64];
+    __shared__ float terms[DS_TB];
+    const DosItem it = items[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+    if (it.nkm) {
+#pragma unroll
+        for (int i = 0; i < DS_E; ++i) {
+            const uint32_t k = (uint32_t)i * DS_T + tid;
+            P[ds_pad(k)] = k < it.nkm ? counts[(uint64_t)it.k0 + k] : 0ull;
+        }
+        __syncthreads();
+        uint64_t v[DS_E], acc = 0;
+#pragma unroll
+        for (int i = 0; i < DS_E; ++i) { acc += P[ds_pad(tid * DS_E + i)]; v[i] = acc; }
+        uint64_t sc = acc;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint64_t t = __shfl_up(sc, d);
+            if ((int)lane >= d) sc += t;
+        }
+        if (lane == 63u) wtot[w] = sc;
+        __syncthreads();
+        uint64_t off = sc - acc;
+#pragma unroll
+        for (uint32_t q = 0; q < DS_T / 64 - 1; ++q) if (q < w) off += wtot[q];
+#pragma unroll
+        for (int i = 0; i < DS_E; ++i) P[ds_pad(tid * DS_E + i)] = off + v[i];
+        __syncthreads();
+    }
+    for (uint32_t j = tid; j < it.nl; j += DS_T) {
+        const uint32_t l = it.l0 + j;
+        const uint32_t b = (l ? nk_cum[l - 1] : 0u) - it.k0, e = nk_cum[l] - it.k0;
+        kms[(uint64_t)l * ns + sample] = (e ? P[ds_pad(e - 1)] : 0ull) - (b ? P[ds_pad(b - 1)] : 0ull);
+    }
+    if (it.part != NOPART && tid == 0) part[it.part] = it.nkm ? P[ds_pad(it.nkm - 1)] : 0ull;
+    for (uint32_t lg = 0; lg < it.nlb; lg += DS_T) {  // (every bound of the loops with barriers is the same in all threads)
+        const uint32_t gl0 = it.l0 + lg, gn = it.nlb - lg < (uint32_t)DS_T ? it.nlb - lg : (uint32_t)DS_T;
+        const uint32_t J0 = gl0 ? nik_cum[gl0 - 1] : 0u, J1 = nik_cum[gl0 + gn - 1];
+        const bool on = tid < gn;
+        const uint32_t l = gl0 + (on ? tid : 0u);
+        const uint32_t isi = l ? nik_cum[l - 1] : 0u, iei = on ? nik_cum[l] : isi;
+        const bool empty = (l ? nk_cum[l - 1] : 0u) == nk_cum[l];
+        float acc = 0.f;
+        for (uint32_t jt = J0; jt < J1; jt += DS_TB) {
+            const uint32_t nt = J1 - jt < (uint32_t)DS_TB ? J1 - jt : (uint32_t)DS_TB;
+            __syncthreads();
+            for (uint32_t jj = tid; jj < nt; jj += DS_T) terms[jj] = ((float)counts[iki[jt + jj]] / depth) / ikmc[jt + jj];
+            __syncthreads();
+            const uint32_t lo = isi > jt ? isi : jt, hi = iei < jt + nt ? iei : jt + nt;
+            for (uint32_t j = lo; j < hi; ++j) acc += terms[j - jt];
+        }
+        if (on && iei > isi && !empty) raw[(uint64_t)l * ns + sample] = acc / (float)(iei - isi);
+    }
+}
+// the loci larger than DS_CH k-mers: their parts' totals (part[fbeg[q]] .. part[fbeg[q + 1] - 1]) added up, one lane per locus
+__global__ void __launch_bounds__(64) k_dosage_fold(const uint32_t* __restrict__ floc, const uint32_t* __restrict__ fbeg, const uint64_t* __restrict__ part,
+                                                    uint64_t* __restrict__ kms, uint64_t ns, uint64_t sample, uint32_t nfold) {
+    const uint32_t q = blockIdx.x * 64 + threadIdx.x;
+    if (q >= nfold) return;
+    uint64_t acc = 0;
+    for (uint32_t i = fbeg[q]; i < fbeg[q + 1]; ++i) acc += part[i];
+    kms[(uint64_t)floc[q] * ns + sample] = acc;
+}
+// values (dbtk_pred.h): v = (float)kms / depth; / Bias where the locus has k-mers and invariant k-mers; 0 without k-mers
+__global__ void __launch_bounds__(256) k_dosage_values(const uint64_t* __restrict__ kms, const float* __restrict__ bias, const float* __restrict__ depth,
+                                                       const uint32_t* __restrict__ nk_cum, const uint32_t* __restrict__ nik_cum, float* __restrict__ out, uint64_t ns) {
+    const uint32_t tri = blockIdx.x;
+    const uint64_t s = (uint64_t)blockIdx.y * 256 + threadIdx.x;
+    if (s >= ns) return;
+    const uint32_t si = tri ? nk_cum[tri - 1] : 0u, ei = nk_cum[tri], isi = tri ? nik_cum[tri - 1] : 0u, iei = nik_cum[tri];
+    const uint64_t at = (uint64_t)tri * ns + s;
+    const float v = (float)kms[at] / depth[s];
+    out[at] = si == ei ? 0.f : (isi == iei ? v : v / bias[at]);
+}
+
+// what both handles ask of their metadata arguments and of the device, before anything is allocated; leaves the device current
+static dbtk_status_t check_ikmer_meta(int device_id, uint64_t ns, uint64_t nk, uint64_t ntr, const uint32_t* nk_cum, const uint32_t* nik_cum,
+                                      uint64_t nik, const uint32_t* iki, const uint8_t* ikmc) {
+    if (!nk_cum || !nik_cum || (nik && (!iki || !ikmc))) { set_error("null argument"); return DBTK_ERR_ARG; }
+    if (!ns || !nk || !ntr) { set_error("empty cohort / RPGG"); return DBTK_ERR_ARG; }
+    if (nk > 0xFFFFFFFFull || ntr > 0xFFFFFFFFull) { set_error("ikmer.meta holds 32-bit k-mer indices"); return DBTK_ERR_ARG; }
+    for (uint64_t t = 0; t < ntr; ++t) {
+        const uint32_t a = t ? nk_cum[t - 1] : 0u, b = nk_cum[t], c = t ? nik_cum[t - 1] : 0u, d = nik_cum[t];
+        if (b < a || b > nk || d < c || d > nik) { set_error("ikmer.meta: the cumulative counts must not decrease or pass the totals"); return DBTK_ERR_FORMAT; }
+    }
+    for (uint64_t j = 0; j < nik; ++j) if (iki[j] >= nk) { set_error("ikmer.meta: invariant k-mer index out of range"); return DBTK_ERR_FORMAT; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device (the library has no CPU path)"); return DBTK_ERR_NO_DEVICE; }
+    if (device_id < 0 || device_id >= ndev) { set_error("device_id out of range"); return DBTK_ERR_ARG; }
+    PCHK(hipSetDevice(device_id));
+    return DBTK_OK;
+}
+// `ikmer.meta` (dbtk_pred.h: dbtk_pred_create_from_file) into host vectors
+struct IkmerMeta { uint64_t nk = 0, nik = 0, ntr = 0; std::vector<uint32_t> nkc, nikc, iki; std::vector<uint8_t> kc; };
+static dbtk_status_t read_ikmer_meta(const char* ikmer_meta, IkmerMeta* m) {
+    FILE* f = fopen(ikmer_meta, "rb");
+    if (!f) { set_error(std::string("cannot open ") + ikmer_meta); return DBTK_ERR_IO; }
+    uint64_t hdr[3];
+    dbtk_status_t st = DBTK_OK;
+    if (fread(hdr, 8, 3, f) != 3) { set_error(std::string("truncated ") + ikmer_meta); st = DBTK_ERR_IO; }
+    if (!st && (hdr[0] > 0xFFFFFFFFull || hdr[1] > hdr[0] || hdr[2] > 0xFFFFFFFFull)) { set_error(std::string(ikmer_meta) + ": implausible header"); st = DBTK_ERR_FORMAT; }
+    if (!st) {
+        const uint64_t nik = hdr[1], ntr = hdr[2];
+        m->nk = hdr[0]; m->nik = nik; m->ntr = ntr;
+        m->nkc.resize(ntr); m->nikc.resize(ntr); m->iki.resize(nik); m->kc.resize(nik);
+        std::vector<uint8_t> rec(nik * 5);
+        if (fread(m->nkc.data(), 4, ntr, f) != ntr || fread(m->nikc.data(), 4, ntr, f) != ntr || (nik && fread(rec.data(), 5, nik, f) != nik)) {
+            set_error(std::string("truncated ") + ikmer_meta); st = DBTK_ERR_IO;
+        }
+        for (uint64_t j = 0; j < nik && !st; ++j) { memcpy(&m->iki[j], &rec[5 * j], 4); m->kc[j] = rec[5 * j + 4]; }
+    }
+    fclose(f);
+    return st;
+}
+
 struct dbtk_pred {
     int device = 0;
     uint64_t ns = 0, nk = 0, ntr = 0, nik = 0;
@@ -135,19 +280,9 @@ extern "C" {
 
 static dbtk_status_t dbtk_pred_create_impl(int device_id, uint64_t ns, uint64_t nk, uint64_t ntr, const uint32_t* nk_cum, const uint32_t* nik_cum,
                                uint64_t nik, const uint32_t* iki, const uint8_t* ikmc, dbtk_pred_t** out) {
-    if (!out || !nk_cum || !nik_cum || (nik && (!iki || !ikmc))) { set_error("null argument"); return DBTK_ERR_ARG; }
+    if (!out) { set_error("null argument"); return DBTK_ERR_ARG; }
     *out = nullptr;
-    if (!ns || !nk || !ntr) { set_error("empty cohort / RPGG"); return DBTK_ERR_ARG; }
-    if (nk > 0xFFFFFFFFull || ntr > 0xFFFFFFFFull) { set_error("ikmer.meta holds 32-bit k-mer indices"); return DBTK_ERR_ARG; }
-    for (uint64_t t = 0; t < ntr; ++t) {
-        const uint32_t a = t ? nk_cum[t - 1] : 0u, b = nk_cum[t], c = t ? nik_cum[t - 1] : 0u, d = nik_cum[t];
-        if (b < a || b > nk || d < c || d > nik) { set_error("ikmer.meta: the cumulative counts must not decrease or pass the totals"); return DBTK_ERR_FORMAT; }
-    }
-    for (uint64_t j = 0; j < nik; ++j) if (iki[j] >= nk) { set_error("ikmer.meta: invariant k-mer index out of range"); return DBTK_ERR_FORMAT; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device (the library has no CPU path)"); return DBTK_ERR_NO_DEVICE; }
-    if (device_id < 0 || device_id >= ndev) { set_error("device_id out of range"); return DBTK_ERR_ARG; }
-    PCHK(hipSetDevice(device_id));
+    { const dbtk_status_t cs = check_ikmer_meta(device_id, ns, nk, ntr, nk_cum, nik_cum, nik, iki, ikmc); if (cs) return cs; }
     std::vector<float> kc(nik);
     for (uint64_t j = 0; j < nik; ++j) kc[j] = (float)ikmc[j];
     std::vector<uint32_t> loc(nk, NOLOC);  // (k-mers past the last locus' cumulative count belong to no locus, like in the reference's loop)
@@ -204,26 +339,9 @@ void dbtk_pred_free(dbtk_pred_t* p) {
 static dbtk_status_t dbtk_pred_create_from_file_impl(int device_id, uint64_t ns, const char* ikmer_meta, dbtk_pred_t** out) {
     if (!ikmer_meta || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
     *out = nullptr;
-    FILE* f = fopen(ikmer_meta, "rb");
-    if (!f) { set_error(std::string("cannot open ") + ikmer_meta); return DBTK_ERR_IO; }
-    uint64_t hdr[3];
-    dbtk_status_t st = DBTK_OK;
-    std::vector<uint32_t> nkc, nikc, iki;
-    std::vector<uint8_t> kc;
-    if (fread(hdr, 8, 3, f) != 3) { set_error(std::string("truncated ") + ikmer_meta); st = DBTK_ERR_IO; }
-    if (!st && (hdr[0] > 0xFFFFFFFFull || hdr[1] > hdr[0] || hdr[2] > 0xFFFFFFFFull)) { set_error(std::string(ikmer_meta) + ": implausible header"); st = DBTK_ERR_FORMAT; }
-    if (!st) {
-        const uint64_t nik = hdr[1], ntr = hdr[2];
-        nkc.resize(ntr); nikc.resize(ntr); iki.resize(nik); kc.resize(nik);
-        std::vector<uint8_t> rec(nik * 5);
-        if (fread(nkc.data(), 4, ntr, f) != ntr || fread(nikc.data(), 4, ntr, f) != ntr || (nik && fread(rec.data(), 5, nik, f) != nik)) {
-            set_error(std::string("truncated ") + ikmer_meta); st = DBTK_ERR_IO;
-        }
-        for (uint64_t j = 0; j < nik && !st; ++j) { memcpy(&iki[j], &rec[5 * j], 4); kc[j] = rec[5 * j + 4]; }
-    }
-    fclose(f);
-    if (st) return st;
-    return dbtk_pred_create(device_id, ns, hdr[0], hdr[2], nkc.data(), nikc.data(), hdr[1], iki.data(), kc.data(), out);
+    IkmerMeta m;
+    { const dbtk_status_t st = read_ikmer_meta(ikmer_meta, &m); if (st) return st; }
+    return dbtk_pred_create(device_id, ns, m.nk, m.ntr, m.nkc.data(), m.nikc.data(), m.nik, m.iki.data(), m.kc.data(), out);
 }
 
 uint64_t dbtk_pred_nk(const dbtk_pred_t* p) { return p ? p->nk : 0; }
@@ -367,6 +485,290 @@ dbtk_status_t dbtk_pred_create_from_file(int device_id, uint64_t ns, const char*
 }
 dbtk_status_t dbtk_pred_load_samples(dbtk_pred_t* p, uint64_t first_sample, uint64_t n, const uint64_t* counts, const float* read_depth) {
     return dbtk::guarded([&] { return dbtk_pred_load_samples_impl(p, first_sample, n, counts, read_depth); });
+}
+
+}  // extern "C"
+
+// ---- the dosage handle (dbtk_pred.h, ABI v10)
+struct dbtk_dosage {
+    int device = 0;
+    uint64_t ns = 0, nk = 0, ntr = 0, nik = 0;
+    uint64_t* d_kms = nullptr;                   // [ntr][ns]
+    float *d_raw = nullptr, *d_bias = nullptr;   // [ntr][ns]: the raw bias of the loads; normalised by dbtk_dosage_finish
+    float* d_values = nullptr;                   // [ntr][ns]: what dbtk_dosage_values reads back (made by the call)
+    float* d_depth = nullptr;                    // [ns]
+    uint32_t *d_nk = nullptr, *d_nik = nullptr, *d_iki = nullptr, *d_floc = nullptr, *d_fbeg = nullptr;
+    float* d_ikmc = nullptr;
+    DosItem* d_items = nullptr;
+    uint64_t* d_part = nullptr;
+    uint64_t* d_stage = nullptr;                 // 16 samples' counts of dbtk_dosage_load_samples, allocated by its first call
+    uint32_t nitems = 0, nfold = 0;
+    uint64_t bytes = 0;
+    std::vector<float> depth;                    // host copy: what the next load sends along
+    bool finished = false;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    float ms[2] = {0, 0};
+};
+constexpr uint64_t DS_STAGE = 16;  // samples per transfer of dbtk_dosage_load_samples (what danbing-tk-pred stages for the matrix, too)
+
+// the work list of k_dosage_sample: whole loci packed greedily into items of at most DS_CH k-mers, larger loci cut into parts
+static void dosage_items(uint64_t ntr, const uint32_t* nk_cum, bool with_bias, std::vector<DosItem>* items, std::vector<uint32_t>* floc, std::vector<uint32_t>* fbeg) {
+    DosItem cur{0, 0, 0, 0, NOPART, 0};
+    auto flush = [&] { if (cur.nl) { cur.nlb = with_bias ? cur.nl : 0; items->push_back(cur); } cur = DosItem{0, 0, 0, 0, NOPART, 0}; };
+    uint32_t nparts = 0;
+    fbeg->push_back(0);
+    for (uint64_t t = 0; t < ntr; ++t) {
+        const uint32_t a = t ? nk_cum[t - 1] : 0u, n = nk_cum[t] - a;
+        if (n > (uint32_t)DS_CH) {
+            flush();
+            for (uint32_t o = 0; o < n; o += DS_CH)
+                items->push_back(DosItem{a + o, std::min<uint32_t>(DS_CH, n - o), (uint32_t)t, 0, nparts++, (with_bias && !o) ? 1u : 0u});
+            floc->push_back((uint32_t)t);
+            fbeg->push_back(nparts);
+            continue;
+        }
+        if (cur.nl && cur.nkm + n > (uint32_t)DS_CH) flush();
+        if (!cur.nl) { cur.k0 = a; cur.l0 = (uint32_t)t; }
+        cur.nkm += n; ++cur.nl;
+    }
+    flush();
+}
+
+extern "C" {
+
+void dbtk_dosage_free(dbtk_dosage_t* d) {
+    if (!d) return;
+    (void)hipSetDevice(d->device);
+    void* ptrs[] = {d->d_kms, d->d_raw, d->d_bias, d->d_values, d->d_depth, d->d_nk, d->d_nik, d->d_iki, d->d_floc, d->d_fbeg, d->d_ikmc, d->d_items, d->d_part, d->d_stage};
+    for (void* q : ptrs) if (q) (void)hipFree(q);
+    for (auto& e : d->ev) if (e) (void)hipEventDestroy(e);
+    if (d->stream) (void)hipStreamDestroy(d->stream);
+    delete d;
+}
+
+static dbtk_status_t dbtk_dosage_create_impl(int device_id, uint64_t ns, uint64_t nk, uint64_t ntr, const uint32_t* nk_cum, const uint32_t* nik_cum,
+                                             uint64_t nik, const uint32_t* iki, const uint8_t* ikmc, dbtk_dosage_t** out) {
+    if (!out) { set_error("null argument"); return DBTK_ERR_ARG; }
+    *out = nullptr;
+    { const dbtk_status_t cs = check_ikmer_meta(device_id, ns, nk, ntr, nk_cum, nik_cum, nik, iki, ikmc); if (cs) return cs; }
+    std::vector<float> kc(nik);
+    for (uint64_t j = 0; j < nik; ++j) kc[j] = (float)ikmc[j];
+    std::vector<DosItem> items;
+    std::vector<uint32_t> floc, fbeg;
+    dosage_items(ntr, nk_cum, nik != 0, &items, &floc, &fbeg);
+    if (items.size() > 0x7FFFFFFFull) { set_error("too many work items for one launch"); return DBTK_ERR_ARG; }
+    dbtk_dosage* d = new dbtk_dosage;  // (after the host-side vectors, but for this one: freed below should it throw)
+    dbtk_status_t st = DBTK_OK;
+    try { d->depth.assign(ns, 1.f); } catch (...) { delete d; throw; }
+    d->device = device_id; d->ns = ns; d->nk = nk; d->ntr = ntr; d->nik = nik;
+    d->nitems = (uint32_t)items.size(); d->nfold = (uint32_t)floc.size();
+    const uint64_t cells = ntr * ns, nparts = fbeg.back();
+    const uint64_t sizes[] = {cells * 8, cells * 4, cells * 4, cells * 4, ns * 4, ntr * 4, ntr * 4, (nik + 1) * 4, (uint64_t)(floc.size() + 1) * 4, (uint64_t)fbeg.size() * 4,
+                              (nik + 1) * 4, (uint64_t)(items.size() + 1) * sizeof(DosItem), (nparts + 1) * 8};
+    void** const slots[] = {(void**)&d->d_kms, (void**)&d->d_raw, (void**)&d->d_bias, (void**)&d->d_values, (void**)&d->d_depth, (void**)&d->d_nk, (void**)&d->d_nik, (void**)&d->d_iki,
+                            (void**)&d->d_floc, (void**)&d->d_fbeg, (void**)&d->d_ikmc, (void**)&d->d_items, (void**)&d->d_part};
+    for (uint64_t b : sizes) d->bytes += b;
+    auto fail = [&](hipError_t e, const char* what) { set_error(std::string(what) + ": " + hipGetErrorString(e)); st = DBTK_ERR_HIP; };
+    hipError_t e;
+    if ((e = hipStreamCreate(&d->stream)) != hipSuccess) fail(e, "hipStreamCreate");
+    for (int i = 0; i < 4 && !st; ++i) if ((e = hipEventCreate(&d->ev[i])) != hipSuccess) fail(e, "hipEventCreate");
+    for (size_t i = 0; i < sizeof sizes / sizeof sizes[0] && !st; ++i) {
+        if ((e = hipMalloc(slots[i], sizes[i])) == hipSuccess) continue;
+        if (e == hipErrorOutOfMemory) {
+            (void)hipGetLastError();
+            size_t fr = 0, tot = 0;
+            (void)hipMemGetInfo(&fr, &tot);
+            set_error("dosage tables: " + std::to_string(d->bytes) + " bytes (20 * ntr * ns = " + std::to_string(cells * 20) + " of them) do not fit, " + std::to_string(fr) +
+                      " of " + std::to_string(tot) + " bytes of HBM are free");
+            st = DBTK_ERR_NOMEM;
+        } else fail(e, "hipMalloc (dosage tables)");
+    }
+    hipStream_t s = d->stream;
+    if (!st && (e = hipMemsetAsync(d->d_kms, 0, cells * 8, s)) != hipSuccess) fail(e, "hipMemset");
+    if (!st && (e = hipMemsetAsync(d->d_raw, 0, cells * 4, s)) != hipSuccess) fail(e, "hipMemset");
+    if (!st && (e = hipMemsetAsync(d->d_bias, 0, cells * 4, s)) != hipSuccess) fail(e, "hipMemset");
+    if (!st && (e = hipMemcpyAsync(d->d_depth, d->depth.data(), ns * 4, hipMemcpyHostToDevice, s)) != hipSuccess) fail(e, "hipMemcpy");
+    if (!st && (e = hipMemcpyAsync(d->d_nk, nk_cum, ntr * 4, hipMemcpyHostToDevice, s)) != hipSuccess) fail(e, "hipMemcpy");
+    if (!st && (e = hipMemcpyAsync(d->d_nik, nik_cum, ntr * 4, hipMemcpyHostToDevice, s)) != hipSuccess) fail(e, "hipMemcpy");
+    if (!st && nik && (e = hipMemcpyAsync(d->d_iki, iki, nik * 4, hipMemcpyHostToDevice, s)) != hipSuccess) fail(e, "hipMemcpy");
+    if (!st && nik && (e = hipMemcpyAsync(d->d_ikmc, kc.data(), nik * 4, hipMemcpyHostToDevice, s)) != hipSuccess) fail(e, "hipMemcpy");
+    if (!st && !items.empty() && (e = hipMemcpyAsync(d->d_items, items.data(), items.size() * sizeof(DosItem), hipMemcpyHostToDevice, s)) != hipSuccess) fail(e, "hipMemcpy");
+    if (!st && !floc.empty() && (e = hipMemcpyAsync(d->d_floc, floc.data(), floc.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess) fail(e, "hipMemcpy");
+    if (!st && (e = hipMemcpyAsync(d->d_fbeg, fbeg.data(), fbeg.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess) fail(e, "hipMemcpy");
+    if (!st && (e = hipStreamSynchronize(s)) != hipSuccess) fail(e, "hipStreamSynchronize");
+    if (st) { dbtk_dosage_free(d); return st; }
+    *out = d;
+    return DBTK_OK;
+}
+
+static dbtk_status_t dbtk_dosage_create_from_file_impl(int device_id, uint64_t ns, const char* ikmer_meta, dbtk_dosage_t** out) {
+    if (!ikmer_meta || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
+    *out = nullptr;
+    IkmerMeta m;
+    { const dbtk_status_t st = read_ikmer_meta(ikmer_meta, &m); if (st) return st; }
+    return dbtk_dosage_create_impl(device_id, ns, m.nk, m.ntr, m.nkc.data(), m.nikc.data(), m.nik, m.iki.data(), m.kc.data(), out);
+}
+
+static dbtk_status_t dbtk_dosage_create_from_rpgg_impl(const dbtk_rpgg_t* g, int device_id, uint64_t ns, dbtk_dosage_t** out) {
+    if (!g || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
+    *out = nullptr;
+    if (!g->order_done || g->out_beg.size() != g->nloci + 1) { set_error("the RPGG handle has no output order"); return DBTK_ERR_ARG; }
+    std::vector<uint32_t> nkc(g->nloci), nikc(g->nloci, 0u);
+    for (uint64_t l = 0; l < g->nloci; ++l) nkc[l] = (uint32_t)g->out_beg[l + 1];  // (finish_order: below 2^32)
+    return dbtk_dosage_create_impl(device_id, ns, g->out_kmer.size(), g->nloci, nkc.data(), nikc.data(), 0, nullptr, nullptr, out);
+}
+
+uint64_t dbtk_dosage_nk(const dbtk_dosage_t* d) { return d ? d->nk : 0; }
+uint64_t dbtk_dosage_ntr(const dbtk_dosage_t* d) { return d ? d->ntr : 0; }
+uint64_t dbtk_dosage_bytes(const dbtk_dosage_t* d) { return d ? d->bytes : 0; }
+
+// n samples' counts in device memory -> their kms and raw entries; asynchronous on d->stream, between ev[0] and ev[1]
+static dbtk_status_t dosage_load_async(dbtk_dosage_t* d, uint64_t first, uint64_t n, const uint64_t* d_counts, const float* read_depth) {
+    hipStream_t s = d->stream;
+    for (uint64_t i = 0; i < n; ++i) d->depth[first + i] = read_depth[i];
+    d->finished = false;
+    PCHK(hipMemcpyAsync(d->d_depth + first, d->depth.data() + first, n * 4, hipMemcpyHostToDevice, s));
+    PCHK(hipEventRecord(d->ev[0], s));
+    for (uint64_t i = 0; i < n && d->nitems; ++i) {
+        hipLaunchKernelGGL(k_dosage_sample, dim3(d->nitems), dim3(DS_T), 0, s, d_counts + i * d->nk, read_depth[i], d->d_items, d->d_nk, d->d_nik, d->d_iki, d->d_ikmc,
+                           d->d_kms, d->d_raw, d->d_part, d->ns, first + i);
+        PCHK(hipGetLastError());
+        if (d->nfold) {
+            hipLaunchKernelGGL(k_dosage_fold, dim3((d->nfold + 63) / 64), dim3(64), 0, s, d->d_floc, d->d_fbeg, d->d_part, d->d_kms, d->ns, first + i, d->nfold);
+            PCHK(hipGetLastError());
+        }
+    }
+    PCHK(hipEventRecord(d->ev[1], s));
+    return DBTK_OK;
+}
+static dbtk_status_t dosage_load_wait(dbtk_dosage_t* d, float* ms_sum) {
+    PCHK(hipStreamSynchronize(d->stream));
+    float ms = 0;
+    PCHK(hipEventElapsedTime(&ms, d->ev[0], d->ev[1]));
+    *ms_sum += ms;
+    return DBTK_OK;
+}
+
+dbtk_status_t dbtk_dosage_load_device(dbtk_dosage_t* d, uint64_t first_sample, uint64_t n, const uint64_t* d_counts, const float* read_depth) {
+    if (!d || !d_counts || !read_depth) { set_error("null argument"); return DBTK_ERR_ARG; }
+    if (first_sample > d->ns || n > d->ns - first_sample || n > 0xFFFFFFFFull) { set_error("sample range outside the cohort"); return DBTK_ERR_ARG; }
+    if (!n) return DBTK_OK;
+    PCHK(hipSetDevice(d->device));
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, d_counts) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != d->device) {
+        (void)hipGetLastError();
+        set_error("dbtk_dosage_load_device: d_counts is not device memory of the handle's device");
+        return DBTK_ERR_ARG;
+    }
+    { const dbtk_status_t st = dosage_load_async(d, first_sample, n, d_counts, read_depth); if (st) return st; }
+    float ms = 0;
+    { const dbtk_status_t st = dosage_load_wait(d, &ms); if (st) return st; }  // (d_counts is no longer being read)
+    d->ms[0] = ms;
+    return DBTK_OK;
+}
+
+dbtk_status_t dbtk_dosage_load_ctx(dbtk_dosage_t* d, uint64_t sample, dbtk_ctx_t* ctx, float read_depth) {
+    if (!d || !ctx) { set_error("null argument"); return DBTK_ERR_ARG; }
+    CtxFacts f;
+    { const dbtk_status_t st = ctx_facts(ctx, &f); if (st) return st; }
+    if (sample >= d->ns) { set_error("sample outside the cohort"); return DBTK_ERR_ARG; }
+    if (f.ntrkmers != d->nk) { set_error("the context counts " + std::to_string(f.ntrkmers) + " TR k-mers, the dosage handle " + std::to_string(d->nk) + ": not the same RPGG build"); return DBTK_ERR_ARG; }
+    if (f.device != d->device) { set_error("the context is on device " + std::to_string(f.device) + ", the dosage tables on device " + std::to_string(d->device)); return DBTK_ERR_ARG; }
+    if (f.unflushed_pairs) {
+        set_error(std::to_string(f.unflushed_pairs) + " pairs appended by dbtk_ingest_align_merged are not aligned yet: flush them first (slot = ~0u, flush = 1)");
+        return DBTK_ERR_ARG;
+    }
+    // every batch done, the counter replicas folded, and a pending sticky error word reported instead of tainted sums
+    { const dbtk_status_t st = dbtk_ctx_synchronize(ctx); if (st) return st; }
+    void* base = nullptr; uint64_t n64 = 0;
+    { const dbtk_status_t st = dbtk_ctx_accum_buffer(ctx, &base, &n64); if (st) return st; }
+    if (!base || n64 < d->nk) { set_error("the context has no accumulators"); return DBTK_ERR_ARG; }
+    PCHK(hipSetDevice(d->device));
+    { const dbtk_status_t st = dosage_load_async(d, sample, 1, (const uint64_t*)base, &read_depth); if (st) return st; }
+    float ms = 0;
+    { const dbtk_status_t st = dosage_load_wait(d, &ms); if (st) return st; }  // (d_accum is no longer being read: dbtk_ctx_reset may follow)
+    d->ms[0] = ms;
+    return DBTK_OK;
+}
+
+static dbtk_status_t dbtk_dosage_load_samples_impl(dbtk_dosage_t* d, uint64_t first_sample, uint64_t n, const uint64_t* counts, const float* read_depth) {
+    if (!d || !counts || !read_depth) { set_error("null argument"); return DBTK_ERR_ARG; }
+    if (first_sample > d->ns || n > d->ns - first_sample || n > 0xFFFFFFFFull) { set_error("sample range outside the cohort"); return DBTK_ERR_ARG; }
+    if (!n) return DBTK_OK;
+    PCHK(hipSetDevice(d->device));
+    if (!d->d_stage) {
+        PCHK(hipMalloc(&d->d_stage, DS_STAGE * d->nk * 8));
+        d->bytes += DS_STAGE * d->nk * 8;
+    }
+    float ms = 0;
+    for (uint64_t i0 = 0; i0 < n; i0 += DS_STAGE) {
+        const uint64_t ni = std::min<uint64_t>(DS_STAGE, n - i0);
+        PCHK(hipMemcpyAsync(d->d_stage, counts + i0 * d->nk, ni * d->nk * 8, hipMemcpyHostToDevice, d->stream));
+        { const dbtk_status_t st = dosage_load_async(d, first_sample + i0, ni, d->d_stage, read_depth + i0); if (st) return st; }
+        { const dbtk_status_t st = dosage_load_wait(d, &ms); if (st) return st; }  // (the staging buffer is free again)
+    }
+    d->ms[0] = ms;
+    return DBTK_OK;
+}
+
+dbtk_status_t dbtk_dosage_finish(dbtk_dosage_t* d) {
+    if (!d) { set_error("null argument"); return DBTK_ERR_ARG; }
+    PCHK(hipSetDevice(d->device));
+    hipStream_t s = d->stream;
+    PCHK(hipEventRecord(d->ev[2], s));
+    PCHK(hipMemcpyAsync(d->d_bias, d->d_raw, d->ntr * d->ns * sizeof(float), hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(k_pred_bias_norm, dim3((uint32_t)d->ntr), dim3(256), 0, s, d->d_nk, d->d_nik, d->d_bias, d->ns);
+    PCHK(hipGetLastError());
+    PCHK(hipEventRecord(d->ev[3], s));
+    PCHK(hipStreamSynchronize(s));
+    PCHK(hipEventElapsedTime(&d->ms[1], d->ev[2], d->ev[3]));
+    d->finished = true;
+    return DBTK_OK;
+}
+
+dbtk_status_t dbtk_dosage_kms(dbtk_dosage_t* d, uint64_t* out) {
+    if (!d || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
+    PCHK(hipSetDevice(d->device));
+    PCHK(hipMemcpy(out, d->d_kms, d->ntr * d->ns * 8, hipMemcpyDeviceToHost));
+    return DBTK_OK;
+}
+dbtk_status_t dbtk_dosage_bias(dbtk_dosage_t* d, float* out) {
+    if (!d || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
+    if (!d->finished) { set_error("dbtk_dosage_bias: samples were loaded since the last dbtk_dosage_finish (or it was never called)"); return DBTK_ERR_ARG; }
+    PCHK(hipSetDevice(d->device));
+    PCHK(hipMemcpy(out, d->d_bias, d->ntr * d->ns * sizeof(float), hipMemcpyDeviceToHost));
+    return DBTK_OK;
+}
+dbtk_status_t dbtk_dosage_values(dbtk_dosage_t* d, float* out) {
+    if (!d || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
+    if (!d->finished) { set_error("dbtk_dosage_values: samples were loaded since the last dbtk_dosage_finish (or it was never called)"); return DBTK_ERR_ARG; }
+    PCHK(hipSetDevice(d->device));
+    hipLaunchKernelGGL(k_dosage_values, dim3((uint32_t)d->ntr, (uint32_t)((d->ns + 255) / 256)), dim3(256), 0, d->stream, d->d_kms, d->d_bias, d->d_depth, d->d_nk, d->d_nik, d->d_values, d->ns);
+    PCHK(hipGetLastError());
+    PCHK(hipMemcpyAsync(out, d->d_values, d->ntr * d->ns * sizeof(float), hipMemcpyDeviceToHost, d->stream));
+    PCHK(hipStreamSynchronize(d->stream));
+    return DBTK_OK;
+}
+dbtk_status_t dbtk_dosage_times(dbtk_dosage_t* d, float ms[2]) {
+    if (!d || !ms) { set_error("null argument"); return DBTK_ERR_ARG; }
+    ms[0] = d->ms[0]; ms[1] = d->ms[1];
+    return DBTK_OK;
+}
+
+// ---- behind the exception barrier (dbtk_internal.h: guarded), like their dbtk_pred_* twins
+dbtk_status_t dbtk_dosage_create(int device_id, uint64_t ns, uint64_t nk, uint64_t ntr, const uint32_t* nk_cum, const uint32_t* nik_cum,
+                                 uint64_t nik, const uint32_t* iki, const uint8_t* ikmc, dbtk_dosage_t** out) {
+    return dbtk::guarded([&] { return dbtk_dosage_create_impl(device_id, ns, nk, ntr, nk_cum, nik_cum, nik, iki, ikmc, out); });
+}
+dbtk_status_t dbtk_dosage_create_from_file(int device_id, uint64_t ns, const char* ikmer_meta, dbtk_dosage_t** out) {
+    return dbtk::guarded([&] { return dbtk_dosage_create_from_file_impl(device_id, ns, ikmer_meta, out); });
+}
+dbtk_status_t dbtk_dosage_create_from_rpgg(const dbtk_rpgg_t* rpgg, int device_id, uint64_t ns, dbtk_dosage_t** out) {
+    return dbtk::guarded([&] { return dbtk_dosage_create_from_rpgg_impl(rpgg, device_id, ns, out); });
+}
+dbtk_status_t dbtk_dosage_load_samples(dbtk_dosage_t* d, uint64_t first_sample, uint64_t n, const uint64_t* counts, const float* read_depth) {
+    return dbtk::guarded([&] { return dbtk_dosage_load_samples_impl(d, first_sample, n, counts, read_depth); });
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// dbtk_pred_io.h — the output files of the `danbing-tk-pred` step (src/pred.h:236-258 of the reference), shared by the two command
+// dbtk_pred_io.h — the output files of the `danbing-tk-pred` step (src/pred.h:236-258 of the reference) and of the dosage tables, shared by the two command
 // lines that write them: danbing-tk-pred (dbtk_pred_cli.cpp) and `danbing-tk --cohort ... --pred` (dbtk_cli.cpp).  Host only.
 // Both return false (with *err set) instead of ending the process: the callers end differently.
 #ifndef DBTK_PRED_IO_H_
@@ -41,6 +41,23 @@ inline bool save_bias_tsv(const std::string& fn, const float* bias, uint64_t ns,
             line += num;
         }
         if (s + 1 < ns) line += '\n';
+        ok = fwrite(line.data(), 1, line.size(), f) == line.size() && ok;
+    }
+    if (fclose(f) || !ok) { *err = "write error on " + fn; return false; }
+    return true;
+}
+
+// a .kms table in the layout of the reference's `ktools sum -f` (kmertools.cpp:92-106): a row per sample, the loci tab-separated, every
+// row ended by a newline.  kms is ns x ntr column-major (entry (s, tri) at tri * ns + s), as dbtk_dosage_kms hands it out.
+inline bool save_kms(const std::string& fn, const uint64_t* kms, uint64_t ns, uint64_t ntr, FILE* log, std::string* err) {
+    fprintf(log, "saving kms table to %s\n", fn.c_str());
+    FILE* f = fopen(fn.c_str(), "w");
+    if (!f) { *err = "cannot create " + fn; return false; }
+    std::string line;
+    bool ok = true;
+    for (uint64_t s = 0; s < ns; ++s) {
+        line.clear();
+        for (uint64_t t = 0; t < ntr; ++t) { line += std::to_string(kms[t * ns + s]); line += t + 1 < ntr ? '\t' : '\n'; }
         ok = fwrite(line.data(), 1, line.size(), f) == line.size() && ok;
     }
     if (fclose(f) || !ok) { *err = "write error on " + fn; return false; }

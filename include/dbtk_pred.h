@@ -82,6 +82,62 @@ dbtk_status_t dbtk_pred_bias(dbtk_pred_t* p, float* out);
 /* Kernel times of the last dbtk_pred_correct in milliseconds: bias sums, bias normalisation, the correcting pass. */
 dbtk_status_t dbtk_pred_times(dbtk_pred_t* p, float ms[3]);
 
+/* ---- Per-locus dosage tables without the matrix (ABI v10).
+ *
+ * What most users take from the matrix is one number per sample and locus: "the sum of k-mer counts normalised to VNTR dosage"
+ * (the reference's README; the `.kms` table of `ktools sum`, read by script/kmc2length.py).  A dbtk_dosage_t holds exactly that for
+ * ns samples and ntr loci, in HBM:
+ *   kms   u64 [ntr][ns]   the exact sum of the locus' counts (what `ktools sum` writes)
+ *   raw   f32 [ntr][ns]   the raw bias of bias_correction's first half: sum_j ((float)count[iki[j]] / depth) / ikmc[j], in j order, / n
+ *   Bias  f32 [ntr][ns]   raw divided by its mean over the samples (dbtk_dosage_finish)
+ * plus a buffer of that size for dbtk_dosage_values, the depths, the invariant-k-mer tables and a work list of a few bytes per
+ * locus: 20 * ntr * ns bytes and nothing of size
+ * nk * ns, so the cohort's size is not bounded by the matrix.  DBTK_ERR_NOMEM when the tables do not fit; the message holds their
+ * size and the free and total bytes of the device.
+ *
+ * Arithmetic.  kms is integer and exact.  raw takes the operations of the matrix path one by one — (float)count / depth (the
+ * column loaders), / ikmc[j], the adds sequential in j, / (float)n (the bias sums) — and dbtk_dosage_finish runs the matrix path's
+ * own normalisation kernel, so dbtk_dosage_bias is BIT-IDENTICAL to dbtk_pred_bias after dbtk_pred_correct on the same counts and
+ * depths.  values(s, l) = v = (float)kms / depth (one conversion, one division); where the locus has k-mers and invariant k-mers
+ * v / Bias(s, l), otherwise v stays uncorrected (as bias_correction leaves such a locus' columns); 0 for a locus without k-mers.
+ * A Bias of exactly 0 (every invariant k-mer of the locus uncounted in that sample) gives what IEEE division gives: +inf, or NaN
+ * for 0 / 0.  The reference has the same caveat one step earlier: it divides the k-mer columns by biases near zero without a guard.
+ * A sample that was never loaded reads as all-zero counts at depth 1, like the zeroed column of the matrix handle. */
+typedef struct dbtk_dosage dbtk_dosage_t;
+
+/* The metadata arguments of dbtk_pred_create, with the same checks. */
+dbtk_status_t dbtk_dosage_create(int device_id, uint64_t ns, uint64_t nk, uint64_t ntr, const uint32_t* nk_cum, const uint32_t* nik_cum,
+                                 uint64_t nik, const uint32_t* iki, const uint8_t* ikmc, dbtk_dosage_t** out);
+dbtk_status_t dbtk_dosage_create_from_file(int device_id, uint64_t ns, const char* ikmer_meta, dbtk_dosage_t** out);
+/* Locus boundaries from a loaded RPGG (its OUT.trkmc.ar order), no invariant k-mers: every locus counts as "skipped", so kms is
+ * complete, Bias is 0 and values is kms / depth.  What `danbing-tk --cohort --kms` uses: it needs no ikmer.meta and no depths. */
+dbtk_status_t dbtk_dosage_create_from_rpgg(const dbtk_rpgg_t* rpgg, int device_id, uint64_t ns, dbtk_dosage_t** out);
+void dbtk_dosage_free(dbtk_dosage_t* d);
+uint64_t dbtk_dosage_nk(const dbtk_dosage_t* d);
+uint64_t dbtk_dosage_ntr(const dbtk_dosage_t* d);
+/* Bytes of HBM the handle holds (tables, metadata, work list; the staging of dbtk_dosage_load_samples once it was used). */
+uint64_t dbtk_dosage_bytes(const dbtk_dosage_t* d);
+
+/* The three loaders keep the contracts of their dbtk_pred_load_* twins above, word for word: the refusals (DBTK_ERR_ARG for another
+ * nk, another device, sample >= ns, pairs of dbtk_ingest_align_merged not flushed; a pending sticky error word returned once INSTEAD
+ * of loading), "the tables are not touched by a refused call", the handle's own stream that is not ordered against the producer of
+ * d_counts, the return once the counts are no longer read, any order of samples, and "loaded twice: the later load wins".
+ * One kernel pass over a sample's 8 * nk bytes of counts makes its kms and raw entries; dbtk_dosage_load_samples stages the host
+ * counts 16 samples at a time. */
+dbtk_status_t dbtk_dosage_load_ctx(dbtk_dosage_t* d, uint64_t sample, dbtk_ctx_t* ctx, float read_depth);
+dbtk_status_t dbtk_dosage_load_device(dbtk_dosage_t* d, uint64_t first_sample, uint64_t n, const uint64_t* d_counts, const float* read_depth);
+dbtk_status_t dbtk_dosage_load_samples(dbtk_dosage_t* d, uint64_t first_sample, uint64_t n, const uint64_t* counts, const float* read_depth);
+
+/* Bias = raw normalised over the samples (raw itself is kept: the call may be repeated, and samples may be loaded after it; a load
+ * makes the handle "unfinished" again).  dbtk_dosage_bias and dbtk_dosage_values return DBTK_ERR_ARG on an unfinished handle. */
+dbtk_status_t dbtk_dosage_finish(dbtk_dosage_t* d);
+/* ns x ntr column-major, the layout of dbtk_pred_bias: entry (s, tri) at tri * ns + s. */
+dbtk_status_t dbtk_dosage_kms(dbtk_dosage_t* d, uint64_t* out);
+dbtk_status_t dbtk_dosage_bias(dbtk_dosage_t* d, float* out);
+dbtk_status_t dbtk_dosage_values(dbtk_dosage_t* d, float* out);
+/* Kernel times in milliseconds: ms[0] the kernels of the last load call (all of its samples), ms[1] the last dbtk_dosage_finish. */
+dbtk_status_t dbtk_dosage_times(dbtk_dosage_t* d, float ms[2]);
+
 #ifdef __cplusplus
 }
 #endif

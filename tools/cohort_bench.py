@@ -5,6 +5,9 @@
 Each leg runs twice and the second is reported (the first pass over freshly written tmpfs files is bound by the first touch of their
 pages).  Checks that both legs wrote the same bytes (every OUT.trkmc.ar, RAW.gt), then prints one JSON line.
     python tools/cohort_bench.py [--samples 16] [--reads 8000000] [--distinct D] [--nloci 80000] [--parent DIR]
+--dosage: only the two cohort legs that differ in what they keep in HBM — `--cohort --pred` of --parent (the matrix) and `--cohort
+--dosage --no-trkmc` of this tree (the per-locus tables) — twice each; prints both passes of both, and whether the two bias tables
+are the same bytes.
 --distinct D: only D different reads files are generated, the samples cycle through them (less tmpfs, the same work per sample)."""
 import argparse
 import ctypes as C
@@ -44,6 +47,7 @@ def main():
     ap.add_argument("--reads", type=int, default=8_000_000)
     ap.add_argument("--distinct", type=int, default=0)
     ap.add_argument("--nloci", type=int, default=80000)
+    ap.add_argument("--dosage", action="store_true", help="only `--cohort --pred` (of --parent) against `--cohort --dosage --no-trkmc` (of this tree)")
     ap.add_argument("--parent", default=None, help="tree holding danbing-tk_amd/bin of the commit before cohort mode [this tree]")
     a = ap.parse_args()
     S, D = a.samples, a.distinct or a.samples
@@ -74,6 +78,20 @@ def main():
                 f.write(f"r{i % D}.fa\tc{i}\t{depths[i]!r}\n")
                 g.write(f"s{i}.trkmc.ar\t{depths[i]!r}\n")
         res = dict(samples=S, reads=a.reads, distinct=D, nk=int(nk_cum[-1]))
+        if a.dosage:
+            legs = dict(pred=[os.path.join(par, "danbing-tk")] + FLAGS + ["--cohort", "m.tsv", "--pred", "ikmer.meta", "coh.raw.gt", "coh.cor.gt", "coh.bias.tsv"],
+                        dosage=[os.path.join(here, "danbing-tk")] + FLAGS + ["--cohort", "m.tsv", "--dosage", "ikmer.meta", "dos.tsv", "dos.bias.tsv", "--kms", "dos.kms", "--no-trkmc"])
+            for name, argv in legs.items():
+                for rep in range(2):
+                    dt, _ = timed(argv, d)
+                    res[f"{name}_pass{rep}_s"] = dt
+                    print(f"# --cohort --{name} pass {rep}: {dt:.2f} s", flush=True)
+            res.update(same_bias=open(os.path.join(d, "coh.bias.tsv"), "rb").read() == open(os.path.join(d, "dos.bias.tsv"), "rb").read(),
+                       parent_spread_s=abs(res["pred_pass0_s"] - res["pred_pass1_s"]), dosage_minus_pred_s=res["dosage_pass1_s"] - res["pred_pass1_s"])
+            print(json.dumps(res))
+            if not res["same_bias"]:
+                sys.exit("bias tables differ")
+            return
         for rep in range(2):                                      # (i)
             t_runs = 0.0
             for i in range(S):
