@@ -222,6 +222,21 @@ class Context:
     def write_bubbles(self, out_prefix):
         self._lib._chk(self._lib.L.dbtk_ctx_write_bubbles(self.h, out_prefix.encode()))
 
+    def bubbles(self, th=0):
+        """dbtk_ctx_bubbles (params.bubbles = abi.BUBBLES_TABLE): (loci uint32, edges uint64, counts uint32) of the novel edges
+        seen at least th times, sorted by (locus, edge)."""
+        L = self._lib.L
+        n = C.c_uint64(0)
+        self._lib._chk(L.dbtk_ctx_bubbles(self.h, int(th), C.byref(n), None, None, None, 0))
+        m = int(n.value)
+        loci, edges, counts = np.zeros(m, np.uint32), np.zeros(m, np.uint64), np.zeros(m, np.uint32)
+        if m:
+            self._lib._chk(L.dbtk_ctx_bubbles(self.h, int(th), C.byref(n), _ptr(loci, u32p), _ptr(edges, u64p), _ptr(counts, u32p), m))
+        return loci, edges, counts
+
+    def merge_bubbles(self, src):
+        self._lib._chk(self._lib.L.dbtk_ctx_merge_bubbles(self.h, src.h))
+
     def synchronize(self):
         self._lib._chk(self._lib.L.dbtk_ctx_synchronize(self.h))
 
@@ -326,6 +341,8 @@ class Dbtk(_HostSide):
         L.dbtk_ctx_write_bubbles.argtypes = [C.c_void_p, C.c_char_p]
         L.dbtk_ctx_merge_bubbles.restype = C.c_int
         L.dbtk_ctx_merge_bubbles.argtypes = [C.c_void_p, C.c_void_p]
+        L.dbtk_ctx_bubbles.restype = C.c_int
+        L.dbtk_ctx_bubbles.argtypes = [C.c_void_p, C.c_uint32, u64p, u32p, u64p, u32p, C.c_uint64]
         L.dbtk_ctx_write_bait_hits.restype = C.c_int
         L.dbtk_ctx_write_bait_hits.argtypes = [C.c_void_p, C.c_char_p]
         L.dbtk_ctx_merge_bait_hits.restype = C.c_int
@@ -422,7 +439,7 @@ EXPORTS = [
     "dbtk_rpgg_load", "dbtk_rpgg_load_tr", "dbtk_rpgg_uid", "dbtk_rpgg_from_arrays", "dbtk_rpgg_free", "dbtk_rpgg_nloci", "dbtk_rpgg_ntrkmers", "dbtk_rpgg_nkeys",
     "dbtk_rpgg_view", "dbtk_rpgg_output_order", "dbtk_params_default", "dbtk_device_warmup", "dbtk_ctx_create", "dbtk_ctx_free", "dbtk_align_batch",
     "dbtk_align_batch_device", "dbtk_ctx_synchronize", "dbtk_ctx_counts", "dbtk_ctx_accum_buffer", "dbtk_ctx_reset",
-    "dbtk_allreduce", "dbtk_rpgg_set_index_cache", "dbtk_ctx_table_bytes", "dbtk_ctx_path_stats", "dbtk_ctx_kernel_times", "dbtk_ctx_timers_reset", "dbtk_ctx_timers_enable", "dbtk_ctx_aln_text", "dbtk_ctx_write_bubbles", "dbtk_ctx_merge_bubbles", "dbtk_ctx_write_bait_hits", "dbtk_ctx_merge_bait_hits", "dbtk_write_outputs", "dbtk_rpgg_serialize", "dbtk_last_error", "dbtk_abi_version",
+    "dbtk_allreduce", "dbtk_rpgg_set_index_cache", "dbtk_ctx_table_bytes", "dbtk_ctx_path_stats", "dbtk_ctx_kernel_times", "dbtk_ctx_timers_reset", "dbtk_ctx_timers_enable", "dbtk_ctx_aln_text", "dbtk_ctx_write_bubbles", "dbtk_ctx_merge_bubbles", "dbtk_ctx_bubbles", "dbtk_ctx_write_bait_hits", "dbtk_ctx_merge_bait_hits", "dbtk_write_outputs", "dbtk_rpgg_serialize", "dbtk_last_error", "dbtk_abi_version",
     "dbtk_thread_batch", "dbtk_ctx_walk_results", "dbtk_ctx_aln_records", "dbtk_aln_format",
     "dbtk_ingest_reserve_host", "dbtk_ingest_create", "dbtk_ingest_free", "dbtk_ingest_chunk_buffer", "dbtk_ingest_block", "dbtk_ingest_submit", "dbtk_ingest_wait",
     "dbtk_ingest_align", "dbtk_ingest_align_merged", "dbtk_ingest_spans", "dbtk_ingest_aln_lines",

@@ -4,7 +4,8 @@ import ctypes as C
 MAX_READ_LEN = 256
 NAN64 = 0xFFFFFFFFFFFFFFFF
 NAN32 = 0xFFFFFFFF
-ABI_VERSION = 10
+ABI_VERSION = 11
+BUBBLES_LOG, BUBBLES_TABLE = 1, 2  # params.bubbles: event log replayed on the host (reference order) | counts in a device table
 ALN_TEXT = 4  # params.aln | ALN_TEXT: alignment records in text form (dbtk_ctx_aln_text)
 THREAD_CAP = 384
 ING_DIRTY, ING_LINES, ING_CARRY, ING_TAIL = 1, 2, 4, 8  # dbtk_ingest_info.flags

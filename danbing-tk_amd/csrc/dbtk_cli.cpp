@@ -99,6 +99,7 @@ struct Opts {
     std::string cohortFn;              // --cohort MANIFEST
     bool cohortNames = false;          // --cohort-names: OUT.tr.kmers per sample (the -on form)
     bool noTrkmc = false;              // --no-trkmc: no per-sample files; the counts never leave HBM
+    bool buTable = false;              // --bu-table: -bu counted in a table in HBM (params.bubbles = DBTK_BUBBLES_TABLE); the only -bu of --cohort
     std::vector<std::string> pred;     // --pred IKMER.META RAW.gt CORRECTED.gt BIAS.tsv
     std::string kms;                   // --kms OUT.kms: the per-locus k-mer sums of every sample (the table of `ktools sum -f`)
     std::vector<std::string> dosage;   // --dosage IKMER.META OUT.dosage.tsv OUT.bias.tsv: the bias-corrected per-locus dosages, without the matrix
@@ -123,6 +124,8 @@ void usage() {
             "  -o <STR> | -on <STR>   output prefix (OUT.trkmc.ar + OUT.tr.summary.txt | OUT.tr.kmers with names)\n"
             "  -ka                    no k-mer assignment (kam) records on stdout\n"
             "  -bu                    write read (k+1)-mers absent from the graph\n"
+            "  --bu-table             with -bu: count them in a table in HBM (no host step per batch; OUT.bub.kmdb then holds every locus'\n"
+            "                         entries in ascending order of the edge: the same set, a defined order).  With --cohort: PREFIX.bub.kmdb per sample\n"
             "Algorithm:\n"
             "  -k <INT> [21]  -kf <N> <M> [4 1]  -cth <INT> [10]  -c <INT> [40]  -qth <INT> [20]  -qc <FILE>  -b [FILE]\n"
             "Execution:\n"
@@ -394,6 +397,7 @@ int main(int argc, char* argv[]) {
         else if (a == "--cohort") o.cohortFn = need(++argi);
         else if (a == "--cohort-names") o.cohortNames = true;
         else if (a == "--no-trkmc") o.noTrkmc = true;
+        else if (a == "--bu-table") o.buTable = true;
         else if (a == "--pred") { o.pred.clear(); for (int i = 0; i < 4; ++i) o.pred.push_back(need(++argi)); }
         else if (a == "--kms") o.kms = need(++argi);
         else if (a == "--dosage") { o.dosage.clear(); for (int i = 0; i < 3; ++i) o.dosage.push_back(need(++argi)); }
@@ -409,6 +413,13 @@ int main(int argc, char* argv[]) {
     // ---- cohort mode: what it refuses, and its manifest — all of it before the GPU is asked for anything
     const bool cohort = !o.cohortFn.empty();
     std::vector<CohortSample> samples;
+    if (o.buTable && !o.outputBubbles) refuse("--bu-table needs -bu");
+    if (o.buTable && (o.extractFastX || o.threading)) refuse("--bu-table: with -e or -g/-gc/-gcc -bu does nothing (novel edges are counted on the assignment path only)");
+    // (cohort mode has no place for the event log's host replay after every batch: -bu there is the table's, and is asked for as such)
+    if (cohort && o.outputBubbles && !o.buTable) refuse("--cohort cannot be combined with -bu alone: add --bu-table (the novel edges are then counted in a table in HBM, and PREFIX.bub.kmdb holds every locus' entries in ascending order of the edge)");
+    if (cohort && o.outputBubbles) {
+        if (!readable(o.trPrefix + ".tre.kdb")) refuse("--cohort -bu --bu-table: cannot open " + o.trPrefix + ".tre.kdb (the TR edges -bu compares the reads with)");
+    }
     if (!cohort) {
         if (o.cohortNames) refuse("--cohort-names needs --cohort");
         if (!o.pred.empty()) refuse("--pred needs --cohort (for count files that exist already there is danbing-tk-pred)");
@@ -424,7 +435,6 @@ int main(int argc, char* argv[]) {
         if (o.aln) refuse("--cohort cannot be combined with -a/-ae");
         if (o.bait) refuse("--cohort cannot be combined with -b");
         if (o.trackBait) refuse("--cohort cannot be combined with -tb");
-        if (o.outputBubbles) refuse("--cohort cannot be combined with -bu");
         if (o.ngpus > 1) refuse("--cohort runs on one GPU: --gpus > 1 is not supported with it");
         if (o.ingestShards > 1) refuse("--cohort reads one sample at a time: --ingest-shards is not supported with it");
         if (o.parseOnly) refuse("--cohort cannot be combined with --parse-only");
@@ -448,7 +458,7 @@ int main(int argc, char* argv[]) {
             const std::string where = "--cohort: " + o.cohortFn + " line " + std::to_string(lineno) + ": ";
             const bool need_depth = !o.pred.empty() || !o.dosage.empty();  // (--kms alone sums integers: no depth)
             const size_t needc = need_depth ? 3 : 2;
-            if (col.size() < needc || col[0].empty() || (col[1].empty() && !o.noTrkmc))
+            if (col.size() < needc || col[0].empty() || (col[1].empty() && (!o.noTrkmc || o.outputBubbles)))
                 refuse(where + "expected reads file <TAB> output prefix" + (need_depth ? std::string(" <TAB> read depth (") + (o.pred.empty() ? "--dosage" : "--pred") + " needs the depth)" : std::string()) +
                        ", found " + std::to_string(col.size()) + " column(s)");
             CohortSample sm;
@@ -616,6 +626,7 @@ int main(int argc, char* argv[]) {
     P.trackbait = (o.trackBait && use_bait) ? 1 : 0;  // -tb only does something inside the bait filter (AQ.cpp:2111-2119)
     P.bait = use_bait;
     P.bubbles = o.outputBubbles && !o.extractFastX && !o.threading;  // countNovelEdges only runs on the assignment path
+    if (P.bubbles && o.buTable) P.bubbles = DBTK_BUBBLES_TABLE;
     if (o.ngpus < 1) o.ngpus = 1;
     // DBTK_DEVICE_MAP=a,b,...: logical GPU i runs on device map[i % n] (tests: `--gpus 2` on a one-GPU box, DBTK_DEVICE_MAP=0,0 — two
     // contexts, two sharded readers, the cross-range pairing and the host merge all execute)
@@ -661,8 +672,12 @@ int main(int argc, char* argv[]) {
         auto hbm_sizes = [&] {
             const char* nm[16]; uint64_t tb[16], tsum = 0;
             const int nt = dbtk_ctx_table_bytes(ctx[0], nm, tb, 16);
-            for (int i = 0; i < nt; ++i) if (strcmp(nm[i], "index_images:from_cache")) tsum += tb[i];
-            return "the RPGG's tables hold " + std::to_string(tsum) + " bytes, " + std::to_string(cohort_nctx) + " contexts' accumulators " +
+            uint64_t bub = 0;  // (-bu: every context's own table of novel edges, at the size it starts with)
+            for (int i = 0; i < nt; ++i) {
+                if (!strcmp(nm[i], "bubble_table")) bub = tb[i] * (uint64_t)cohort_nctx;
+                else if (strcmp(nm[i], "index_images:from_cache")) tsum += tb[i];
+            }
+            return "the RPGG's tables hold " + std::to_string(tsum) + " bytes, the tables of -bu " + std::to_string(bub) + " bytes, " + std::to_string(cohort_nctx) + " contexts' accumulators " +
                    std::to_string((uint64_t)cohort_nctx * 8 * (dbtk_rpgg_ntrkmers(rpgg) + 2 * nloci + DBTK_C_COUNT)) + " bytes, the genotype matrix of --pred " +
                    std::to_string(o.pred.empty() ? 0 : 4 * dbtk_rpgg_ntrkmers(rpgg) * (uint64_t)samples.size()) + " bytes, the per-locus tables of --dosage / --kms " +
                    std::to_string(dbtk_dosage_bytes(dosage) + dbtk_dosage_bytes(kms)) + " bytes (of a handle that exists)";
@@ -1477,7 +1492,7 @@ int main(int argc, char* argv[]) {
         *resume = hi;
         bool handed = false;   // the host reader takes over
         uint32_t hslot = 0;
-        const bool sync = want_out || P.bubbles;  // (-bu replays every batch's novel edges on the host)
+        const bool sync = want_out || P.bubbles == 1;  // (-bu replays every batch's novel edges on the host — not with --bu-table)
         // (merging pays when the input is long — a pipe, or a file of at least 2 GB: below that the loop is bound by reading the file, every
         // block's kernels hide under the next block's bytes, and a merged batch's kernels would only start late.  DBTK_MERGE_PAIRS forces it.)
         const bool long_input = piped || total >= (2ull << 30) || getenv("DBTK_MERGE_PAIRS");
@@ -1808,6 +1823,11 @@ int main(int argc, char* argv[]) {
                 for (const char* ext : {".trkmc.ar", ".tr.summary.txt", ".tr.kmers"}) (void)unlink((sm.prefix + ext).c_str());
                 die_assert(err);
             }
+            if (P.bubbles && dbtk_ctx_write_bubbles(d.c, sm.prefix.c_str())) {  // PREFIX.bub.kmdb from the context's table (--no-trkmc does not suppress it)
+                const std::string err = dbtk_last_error();
+                (void)unlink((sm.prefix + ".bub.kmdb").c_str());
+                die_assert(err);
+            }
             if (dbtk_ctx_reset(d.c)) die_assert(dbtk_last_error());
             tl_cohort_sample.clear();
             cohort_finish_s += now() - t0;
@@ -2000,8 +2020,23 @@ int main(int argc, char* argv[]) {
             if (o.outputBubbles) {  // dumpBubbles, AQ.cpp:2648-2651
                 fprintf(stderr, "writing bubbles...\n");
                 if (P.bubbles) {
+                    const double tb0 = wall();
                     for (int d = 1; d < nctx; ++d) if (dbtk_ctx_merge_bubbles(ctx[0], ctx[d])) die_assert(dbtk_last_error());
                     if (dbtk_ctx_write_bubbles(ctx[0], o.outPrefix.c_str())) die_assert(dbtk_last_error());
+                    if (getenv("DBTK_VERBOSE")) {
+                        fprintf(stderr, "bubbles: merged and written in %.3f s\n", wall() - tb0);
+                        if (P.bubbles == DBTK_BUBBLES_TABLE) {  // (tools/bu_bench.py: what the table holds at the end)
+                            uint64_t n = 0, events = 0;
+                            if (dbtk_ctx_bubbles(ctx[0], 0, &n, nullptr, nullptr, nullptr, 0)) die_assert(dbtk_last_error());
+                            std::vector<uint32_t> cnt(n);
+                            if (n && dbtk_ctx_bubbles(ctx[0], 0, &n, nullptr, nullptr, cnt.data(), n)) die_assert(dbtk_last_error());
+                            for (uint32_t v : cnt) events += v;
+                            const char* nm[16]; uint64_t tb[16], slots = 0;
+                            const int nt = dbtk_ctx_table_bytes(ctx[0], nm, tb, 16);
+                            for (int i = 0; i < nt; ++i) if (!strcmp(nm[i], "bubble_table")) slots = tb[i] / 16;
+                            fprintf(stderr, "bubble table: %llu entries in %llu slots, %llu events\n", (unsigned long long)n, (unsigned long long)slots, (unsigned long long)events);
+                        }
+                    }
                 }
             }
         }

@@ -122,6 +122,69 @@ template <int NS, bool RECS> __global__ void __launch_bounds__(64, NS <= 3 ? 2 :
     DevX x{&sm};
     body_pair<NS, RECS>(x, a);
 }
+// ... and its form that counts the novel edges of -bu in the device table (params.bubbles = DBTK_BUBBLES_TABLE, dbtk_bubtab.h): a
+// kernel of its own, so that k_pair stays what it is
+template <int NS, bool RECS> __global__ void __launch_bounds__(64, NS <= 3 ? 2 : 1) k_pair_bub(BatchArgs a) {
+    __shared__ __attribute__((aligned(16))) PairSmemT<NS> sm;
+    DevX x{&sm};
+    body_pair<NS, RECS, true>(x, a);
+}
+// the table's own kernels.  `words`: BUB_W_* (dbtk_bubtab.h)
+__global__ void __launch_bounds__(256) k_bub_fill(BubSlot* t, uint64_t nslots) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nslots; i += (uint64_t)gridDim.x * blockDim.x) t[i] = BubSlot{NAN64, 0u, 0u};
+}
+// every entry of the old table into the new one (growth by doubling); the new table's occupancy is counted again, per wave
+__global__ void __launch_bounds__(256) k_bub_rehash(const BubSlot* old, uint64_t nold, BubSlot* t, uint64_t mask, uint32_t shift, uint32_t* words) {
+    DevX x{nullptr};
+    uint32_t took = 0, failed = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nold; i += (uint64_t)gridDim.x * blockDim.x) {
+        const BubSlot s = old[i];
+        if (s.edge == NAN64 || s.locus1 == 0 || s.count == 0) continue;
+        if (!bub_insert(x, t, mask, shift, s.edge, s.locus1 - 1, s.count, took)) ++failed;
+    }
+    took = x.wave_sum(took); failed = x.wave_sum(failed);
+    if (x.lane() == 0) {
+        if (took) atomicAdd(words + BUB_W_OCC, took);
+        if (failed) atomicAdd(words + BUB_W_FAIL, failed);
+    }
+}
+// a list of (locus, edge, count in `pair`) into the table: the spill log after a growth, the entries of another context (merge)
+__global__ void __launch_bounds__(256) k_bub_add(const BubEvent* ev, uint64_t n, BubSlot* t, uint64_t mask, uint32_t shift, uint32_t* words) {
+    DevX x{nullptr};
+    uint32_t took = 0, failed = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const BubEvent e = ev[i];
+        if (!bub_insert(x, t, mask, shift, e.edge, e.locus, e.pair, took)) ++failed;
+    }
+    took = x.wave_sum(took); failed = x.wave_sum(failed);
+    if (x.lane() == 0) {
+        if (took) atomicAdd(words + BUB_W_OCC, took);
+        if (failed) atomicAdd(words + BUB_W_FAIL, failed);
+    }
+}
+// the entries with count >= th, appended to `out` one list per wave (out = nullptr: counted only).  nslots is a multiple of 64:
+// the lanes of a wave stay together.
+__global__ void __launch_bounds__(256) k_bub_compact(const BubSlot* t, uint64_t nslots, uint32_t th, BubSlot* out, uint64_t cap, unsigned long long* nout) {
+    const int lane = (int)(threadIdx.x & 63);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nslots; i += (uint64_t)gridDim.x * blockDim.x) {
+        const BubSlot s = t[i];
+        const bool keep = s.edge != NAN64 && s.locus1 != 0 && s.count != 0 && s.count >= th;
+        const uint64_t b = __ballot(keep);
+        if (!b) continue;
+        unsigned long long base = 0;
+        if (lane == 0) base = atomicAdd(nout, (unsigned long long)__builtin_popcountll(b));
+        const uint32_t blo = (uint32_t)__shfl((int)(uint32_t)base, 0, 64), bhi = (uint32_t)__shfl((int)(uint32_t)(base >> 32), 0, 64);
+        const uint64_t at = (((uint64_t)bhi << 32) | blo) + (uint64_t)__builtin_popcountll(b & ((1ull << lane) - 1));
+        if (keep && out && at < cap) out[at] = s;
+    }
+}
+// occupancy, spill count and the sticky word into the host's pinned words, at the end of a batch (launch_batch reads them before the next)
+__global__ void __launch_bounds__(64) k_bub_publish(const uint32_t* words, uint32_t* h) {
+    if (threadIdx.x < 3) {
+        volatile uint32_t* hv = h;
+        hv[threadIdx.x] = threadIdx.x == 0 ? words[BUB_W_OCC] : threadIdx.x == 1 ? words[BUB_W_SPILL] : words[BUB_W_OVF];
+    }
+}
 
 // per-locus images of the index and the probe kernel that keeps one in LDS (dbtk_locus.h)
 __global__ void __launch_bounds__(256) k_loc_count(LocBuildArgs a) { DevX x{nullptr}; body_loc_count(x, a); }
@@ -362,6 +425,12 @@ struct dbtk_ctx {
     uint64_t* d_qmask = nullptr; uint64_t qmask_cap = 0;
     BubEvent* d_events = nullptr; uint64_t events_cap = 0;
     uint32_t* d_nevents = nullptr;
+    // params.bubbles = DBTK_BUBBLES_TABLE (dbtk_bubtab.h): the table, and the host's pinned copy of occupancy | spill count | sticky word
+    // (d_events is then the spill log, d_nevents the BUB_W_* words)
+    BubSlot* d_bub = nullptr; uint64_t bub_slots = 0;
+    uint32_t* h_bub = nullptr;
+    uint64_t bub_seen = 0, bub_rate = 0;  // occupancy at the last reading; the largest rise between two readings
+    uint64_t bub_grown = 0;               // growths since creation
     // bubbleDB (bubble_db_t: per locus unordered_map<size_t, uint32_t>, src/aQueryFasta_thread.h:41), filled batch by
     // batch exactly like accumBubbles (AQ.cpp:1599-1606) so that the dump order matches the reference's
     std::vector<std::unordered_map<size_t, uint32_t>> bubbleDB;
@@ -395,6 +464,7 @@ struct dbtk_ctx {
         uint32_t* d_walk = nullptr; uint64_t walk_cap = 0;
         uint64_t* d_vote = nullptr;
         uint32_t* d_epoch = nullptr;
+        uint64_t* d_edge = nullptr; uint64_t edge_cap = 0;  // -bu with the device table: every lane its own K2 -> K3 edge buffer
         // blocks of the device reader merged into one batch (dbtk_ingest_align_merged): reads back to back, offsets
         uint8_t* m_flat = nullptr; uint64_t m_flat_cap = 0;
         uint64_t* m_off = nullptr; uint64_t m_off_cap = 0;
@@ -442,14 +512,15 @@ void free_ctx(dbtk_ctx* c) {
         }
     void* ptrs[] = {c->m_flat, c->m_off, c->d_ctr, c->d_pstats, c->d_accum, c->d_small ? c->d_small - TK_INLINE : nullptr, c->d_surv,
                     c->d_seq, c->d_off, c->d_recs, c->d_vote, c->d_epoch, c->d_hitva, c->d_hitnk, c->d_hitoff, c->d_gen, c->d_tickets,
-                    c->d_qual, c->d_edge, c->d_qmask, c->d_events, c->d_nevents, c->d_walk, c->d_trecs, c->d_loci, c->d_aln, c->d_txt, c->d_txtidx};
+                    c->d_qual, c->d_edge, c->d_qmask, c->d_events, c->d_nevents, c->d_walk, c->d_trecs, c->d_loci, c->d_aln, c->d_txt, c->d_txtidx, c->d_bub};
     for (void* p : ptrs) if (p) (void)hipFree(p);
+    if (c->h_bub) (void)hipHostFree(c->h_bub);
     if (c->h_aln) (void)hipHostFree(c->h_aln);
     if (c->h_sortflag) (void)hipHostFree(c->h_sortflag);
     std::vector<dbtk_ctx::Lane*> others{&c->alt};
     for (auto& l : c->parked) others.push_back(&l);
     for (dbtk_ctx::Lane* l : others) {
-        void* aptrs[] = {l->d_small ? l->d_small - TK_INLINE : nullptr, l->d_surv, l->d_hitva, l->d_hitnk, l->d_hitoff, l->d_gen, l->d_tickets, l->d_vote, l->d_epoch, l->d_walk, l->m_flat, l->m_off};
+        void* aptrs[] = {l->d_small ? l->d_small - TK_INLINE : nullptr, l->d_surv, l->d_hitva, l->d_hitnk, l->d_hitoff, l->d_gen, l->d_tickets, l->d_vote, l->d_epoch, l->d_walk, l->m_flat, l->m_off, l->d_edge};
         for (void* p : aptrs) if (p) (void)hipFree(p);
         if (l != &c->alt && l->stream) (void)hipStreamDestroy(l->stream);
     }
@@ -1079,6 +1150,7 @@ void switch_lane(dbtk_ctx* c) {
     std::swap(c->d_tickets, c->alt.d_tickets); std::swap(c->tickets_cap, c->alt.tickets_cap);
     std::swap(c->d_walk, c->alt.d_walk); std::swap(c->walk_cap, c->alt.walk_cap);
     std::swap(c->d_vote, c->alt.d_vote); std::swap(c->d_epoch, c->alt.d_epoch);
+    std::swap(c->d_edge, c->alt.d_edge); std::swap(c->edge_cap, c->alt.edge_cap);
     std::swap(c->m_flat, c->alt.m_flat); std::swap(c->m_flat_cap, c->alt.m_flat_cap); std::swap(c->m_off, c->alt.m_off); std::swap(c->m_off_cap, c->alt.m_off_cap);
     std::swap(c->m_bytes, c->alt.m_bytes); std::swap(c->m_pairs, c->alt.m_pairs); std::swap(c->m_maxlen, c->alt.m_maxlen);
     if (!c->parked.empty()) {  // round robin: the lane just left goes to the back of the queue, the longest-parked one is next
@@ -1112,6 +1184,73 @@ dbtk_status_t timed_slot(dbtk_ctx* c, int k, int* slot) {
     return DBTK_OK;
 }
 
+// ---- the device table of -bu (params.bubbles = DBTK_BUBBLES_TABLE, dbtk_bubtab.h)
+constexpr uint64_t BUB_SLOTS_DEFAULT = 1ull << 24;  // 256 MB per context (DBTK_BUB_SLOTS); grows by doubling
+constexpr uint64_t BUB_SPILL_CAP = 1ull << 20;      // entries of the spill log (24 MB): inserts that found no slot between two growths
+dbtk_status_t bub_new_table(dbtk_ctx* c, uint64_t slots, BubSlot** out) {
+    *out = nullptr;
+    if (hipMalloc(out, slots * sizeof(BubSlot)) != hipSuccess) {
+        (void)hipGetLastError();
+        *out = nullptr;
+        set_error("bubble table: no device memory for " + std::to_string(slots) + " slots (" + std::to_string(slots * sizeof(BubSlot)) + " bytes)");
+        return DBTK_ERR_NOMEM;
+    }
+    LAUNCH(k_bub_fill, dim3((uint32_t)std::min<uint64_t>((slots + 255) / 256, 4096)), dim3(256), c->stream, *out, slots);
+    return DBTK_OK;
+}
+// A new table of twice the slots or more, the old entries and the spill log (and `extra`, a list of n_extra further entries: merge)
+// inserted into it.  Every lane of the context must be drained (sync_all) before the call; it returns with the stream idle.  An
+// attempt that leaves an entry without a slot is thrown away whole and repeated with twice the slots, so nothing is counted twice.
+dbtk_status_t bub_grow(dbtk_ctx* c, uint64_t room, const BubEvent* d_extra = nullptr, uint64_t n_extra = 0) {
+    // (a merge that fits under half of the slots there are gets a table of the same size: eight contexts merged must not be eight doublings)
+    hipStream_t s = c->stream;
+    uint32_t w[BUB_WORDS];
+    HIPCHK(hipMemcpy(w, c->d_nevents, sizeof(w), hipMemcpyDeviceToHost));
+    const uint64_t nsp = std::min<uint64_t>(w[BUB_W_SPILL], c->events_cap);
+    uint64_t cap = d_extra ? c->bub_slots : c->bub_slots * 2;
+    while (2 * ((uint64_t)w[BUB_W_OCC] + nsp + n_extra + room) > cap) cap <<= 1;
+    for (;;) {
+        BubSlot* nt = nullptr;
+        dbtk_status_t st = bub_new_table(c, cap, &nt);
+        if (st) return st;
+        HIPCHK(hipMemsetAsync(c->d_nevents + BUB_W_OCC, 0, 4, s));
+        HIPCHK(hipMemsetAsync(c->d_nevents + BUB_W_FAIL, 0, 4, s));
+        const uint64_t mask = cap - 1;
+        const uint32_t shift = 64 - log2u(cap);
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((c->bub_slots + 255) / 256, (uint64_t)c->num_cu * 8);
+        LAUNCH(k_bub_rehash, dim3(grid), dim3(256), s, c->d_bub, c->bub_slots, nt, mask, shift, c->d_nevents);
+        if (nsp) LAUNCH(k_bub_add, dim3((uint32_t)std::min<uint64_t>((nsp + 255) / 256, (uint64_t)c->num_cu * 8)), dim3(256), s, c->d_events, nsp, nt, mask, shift, c->d_nevents);
+        if (n_extra) LAUNCH(k_bub_add, dim3((uint32_t)std::min<uint64_t>((n_extra + 255) / 256, (uint64_t)c->num_cu * 8)), dim3(256), s, d_extra, n_extra, nt, mask, shift, c->d_nevents);
+        HIPCHK(hipMemcpyAsync(w, c->d_nevents, sizeof(w), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (w[BUB_W_FAIL] == 0) {
+            HIPCHK(hipFree(c->d_bub));
+            c->d_bub = nt; c->bub_slots = cap;
+            break;
+        }
+        HIPCHK(hipFree(nt));
+        if (cap >= (1ull << 40)) { set_error("bubble table: cannot place every entry"); return DBTK_ERR_OVERFLOW; }
+        cap <<= 1;
+    }
+    HIPCHK(hipMemset(c->d_nevents + BUB_W_SPILL, 0, 4));
+    HIPCHK(hipMemset(c->d_nevents + BUB_W_FAIL, 0, 4));
+    c->h_bub[0] = w[BUB_W_OCC]; c->h_bub[1] = 0;
+    c->bub_seen = w[BUB_W_OCC];
+    ++c->bub_grown;
+    if (getenv("DBTK_VERBOSE")) fprintf(stderr, "bubble table: grown to %llu slots, %u taken\n", (unsigned long long)cap, w[BUB_W_OCC]);
+    return DBTK_OK;
+}
+// Before a batch is enqueued: the occupancy the batch before published (a batch or two old with two lanes, hence the margin of twice
+// the largest rise seen) against half of the capacity; anything in the spill log goes back into a larger table as well.
+dbtk_status_t bub_before_batch(dbtk_ctx* c) {
+    volatile uint32_t* hb = c->h_bub;
+    const uint64_t occ = hb[0], spilled = hb[1];
+    if (occ > c->bub_seen) { c->bub_rate = std::max(c->bub_rate, occ - c->bub_seen); c->bub_seen = occ; }
+    if (!spilled && 2 * (occ + 2 * c->bub_rate) <= c->bub_slots) return DBTK_OK;
+    HIPCHK(sync_all(c));
+    return bub_grow(c, 2 * c->bub_rate);
+}
+
 // K1 over the whole batch, then K2 -> K3 over chunks of the survivor list (the K2 -> K3 hit
 // buffer holds SURV_CAP pairs).  How many survivors there are is known only on the device, so
 // ceil(npairs / SURV_CAP) chunk iterations are enqueued and the kernels of a chunk past the end
@@ -1125,6 +1264,8 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
     hipStream_t s = c->stream;
     if (npairs >= 0xFFFFFFFFull) { set_error("batch too large (pair index is 32-bit)"); return DBTK_ERR_ARG; }
     if (npairs == 0) return DBTK_OK;
+    const bool bub_table = c->P.bubbles == DBTK_BUBBLES_TABLE;
+    if (bub_table) { const dbtk_status_t bs = bub_before_batch(c); if (bs) return bs; }
     const uint32_t k = c->g->ksize;
     const uint32_t nkmax = max_read_len >= k ? max_read_len - k + 1 : 1;
     const uint32_t nkp = 64 * ((nkmax + 63) / 64);
@@ -1175,10 +1316,12 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
     }
     if (c->P.bubbles) {
         if ((st = ensure(&c->d_edge, &c->edge_cap, tcap * 2 * nkp))) return st;
-        // every position of every kept mate could be novel; bounded so that the log stays < 6.4 GB
-        const uint64_t ecap = std::min<uint64_t>(npairs * 2 * nkmax, 1ull << 28);
-        if ((st = ensure(&c->d_events, &c->events_cap, ecap))) return st;
-        HIPCHK(hipMemsetAsync(c->d_nevents, 0, sizeof(uint32_t), s));
+        if (!bub_table) {
+            // every position of every kept mate could be novel; bounded so that the log stays < 6.4 GB
+            const uint64_t ecap = std::min<uint64_t>(npairs * 2 * nkmax, 1ull << 28);
+            if ((st = ensure(&c->d_events, &c->events_cap, ecap))) return st;
+            HIPCHK(hipMemsetAsync(c->d_nevents, 0, sizeof(uint32_t), s));
+        }
     }
     if (c->P.bait && d_qual && (st = ensure(&c->d_qmask, &c->qmask_cap, tcap * 2 * 4))) return st;
     BatchArgs a;
@@ -1209,6 +1352,7 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
     const bool fuse = usual && !d_recs && (fuse_on & 1);
     const bool fuse_lean = usual && !d_recs && (fuse_on & 2);
     if (c->P.bubbles) { a.edgebuf = c->d_edge; a.events = c->d_events; a.nevents = c->d_nevents; a.events_cap = (uint32_t)std::min<uint64_t>(c->events_cap, 0xFFFFFFFFull); }
+    if (bub_table) { a.bub = c->d_bub; a.bub_mask = c->bub_slots - 1; a.bub_shift = 64 - log2u(c->bub_slots); }
     if (c->P.bait && d_qual) { a.qual = d_qual; a.qmaskbuf = c->d_qmask; }
 #ifdef DBTK_STAMPS
     a.dbg = reinterpret_cast<uint64_t*>(c->d_small + 32);
@@ -1388,7 +1532,17 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
         }
         if (tm) { if ((st = timed_slot(c, 3, &e))) return st; HIPCHK(hipEventRecord(c->timed[3].beg[e], s)); }
         const dim3 gp(c->pair_blocks[nsi]);
-        if (d_recs) {
+        if (bub_table) {
+            if (d_recs) {
+                if (nsi == 0) LAUNCH((k_pair_bub<2, true>), gp, dim3(64), s, a);
+                else if (nsi == 1) LAUNCH((k_pair_bub<3, true>), gp, dim3(64), s, a);
+                else LAUNCH((k_pair_bub<4, true>), gp, dim3(64), s, a);
+            } else {
+                if (nsi == 0) LAUNCH((k_pair_bub<2, false>), gp, dim3(64), s, a);
+                else if (nsi == 1) LAUNCH((k_pair_bub<3, false>), gp, dim3(64), s, a);
+                else LAUNCH((k_pair_bub<4, false>), gp, dim3(64), s, a);
+            }
+        } else if (d_recs) {
             if (nsi == 0) LAUNCH((k_pair<2, true>), gp, dim3(64), s, a);
             else if (nsi == 1) LAUNCH((k_pair<3, true>), gp, dim3(64), s, a);
             else LAUNCH((k_pair<4, true>), gp, dim3(64), s, a);
@@ -1399,6 +1553,7 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
         }
         if (tm) HIPCHK(hipEventRecord(c->timed[3].end[e], s));
     }
+    if (bub_table) LAUNCH(k_bub_publish, dim3(1), dim3(64), s, c->d_nevents, c->h_bub);
     if (walking) {  // the graph walk over every pair that reached threading, both mates (AQ.cpp:2072-2088), exact counting (:2189-2194)
         WalkArgs w;
         memset(&w, 0, sizeof(w));
@@ -1537,6 +1692,8 @@ int dbtk_ctx_table_bytes(dbtk_ctx_t* c, const char** names, uint64_t* bytes, int
                                  "index_images", "index_images:from_cache", "vv+qc+perm+trbeg", "gates(tre,bait)", "total", "graph_images"};
     int n = 0;
     for (int i = 0; i < 13 && n < cap; ++i) { names[n] = nm[i]; bytes[n] = c->share->bytes[i]; ++n; }
+    // the context's own table of novel edges (params.bubbles = DBTK_BUBBLES_TABLE): not one of the shared tables, not in "total"
+    if (c->d_bub && n < cap) { names[n] = "bubble_table"; bytes[n] = c->bub_slots * sizeof(BubSlot); ++n; }
     return n;
 }
 
@@ -1548,6 +1705,15 @@ static dbtk_status_t dbtk_ctx_create_impl(const dbtk_rpgg_t* h, const dbtk_param
     if (p->n_filter > 32) { set_error("-kf N: N > 32 unsupported"); return DBTK_ERR_UNSUPPORTED; }
     if (p->bait && h->bt_cnt.empty()) { set_error("params.bait set but the RPGG handle has no bait DB"); return DBTK_ERR_ARG; }
     if (p->trackbait && !p->bait) { set_error("params.trackbait needs params.bait"); return DBTK_ERR_ARG; }
+    if (p->bubbles > DBTK_BUBBLES_TABLE) { set_error("params.bubbles: 0, 1 (event log, reference order) or 2 (DBTK_BUBBLES_TABLE)"); return DBTK_ERR_ARG; }
+    uint64_t bub_slots0 = BUB_SLOTS_DEFAULT;
+    if (p->bubbles == DBTK_BUBBLES_TABLE) {
+        if (const char* e = getenv("DBTK_BUB_SLOTS")) {
+            const unsigned long long v = strtoull(e, nullptr, 10);
+            if (v < 64 || v > (1ull << 36) || (v & (v - 1))) { set_error("DBTK_BUB_SLOTS: a power of two from 64 to 2^36"); return DBTK_ERR_ARG; }
+            bub_slots0 = v;
+        }
+    }
     if (p->bubbles && (h->tre_cnt.empty() || p->extract)) { set_error("params.bubbles needs PREF.tre.kdb (and is not an extract-mode flag)"); return DBTK_ERR_ARG; }
     if (p->qc && h->qc.empty()) { set_error("params.qc set but the RPGG handle has no QC mask"); return DBTK_ERR_ARG; }
     if ((p->aln & 3u) == 3u || (p->aln & ~7u)) { set_error("params.aln: 0, 1 (-a) or 2 (-ae), optionally | DBTK_ALN_TEXT"); return DBTK_ERR_ARG; }
@@ -1684,7 +1850,16 @@ static dbtk_status_t dbtk_ctx_create_impl(const dbtk_rpgg_t* h, const dbtk_param
         }
         if (p->bubbles) {
             c->bubbleDB.resize(h->nloci);
-            if (hipMalloc(&c->d_nevents, 4) != hipSuccess) { set_error("hipMalloc nevents"); st = DBTK_ERR_HIP; break; }
+            if (hipMalloc(&c->d_nevents, 4 * BUB_WORDS) != hipSuccess) { set_error("hipMalloc nevents"); st = DBTK_ERR_HIP; break; }
+            if (hipMemsetAsync(c->d_nevents, 0, 4 * BUB_WORDS, c->stream) != hipSuccess) { set_error("memset nevents"); st = DBTK_ERR_HIP; break; }
+        }
+        if (p->bubbles == DBTK_BUBBLES_TABLE) {  // the table, its spill log (fixed size) and the host's pinned words
+            if ((st = bub_new_table(c, bub_slots0, &c->d_bub))) break;
+            c->bub_slots = bub_slots0;
+            if (hipMalloc(&c->d_events, BUB_SPILL_CAP * sizeof(BubEvent)) != hipSuccess) { (void)hipGetLastError(); set_error("bubble table: no device memory for the spill log"); st = DBTK_ERR_NOMEM; break; }
+            c->events_cap = BUB_SPILL_CAP;
+            if (hipHostMalloc((void**)&c->h_bub, 64, hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc"); st = DBTK_ERR_HIP; break; }
+            memset(c->h_bub, 0, 64);
         }
         c->ntr = h->out_kmer.size();
         c->n_accum = c->ntr + 2 * h->nloci + DBTK_C_COUNT;
@@ -1707,13 +1882,13 @@ static dbtk_status_t dbtk_ctx_create_impl(const dbtk_rpgg_t* h, const dbtk_param
         chk(hipMemsetAsync(c->d_accum, 0, c->n_accum * 8, c->stream), "memset");
         chk(hipMemsetAsync(c->d_vote, 0, (size_t)c->vote_rows * (h->nloci + 1) * 8, c->stream), "memset");
         chk(hipMemsetAsync(c->d_epoch, 0, (size_t)c->vote_rows * 16, c->stream), "memset");
-        // further lanes (not with -bu: its event log is replayed batch by batch on the host; not in the stamps build)
+        // further lanes (not with the event log of -bu, params.bubbles = 1: it is replayed batch by batch on the host; not in the stamps build)
         int nlanes = 1;
 #ifndef DBTK_STAMPS
         {   // DBTK_LANES=1..3 (default 2; a third lane gains another 2 %, a fourth fell apart: 25 ms/step)
             const char* e = getenv("DBTK_LANES");
             nlanes = (e && atoi(e) >= 1 && atoi(e) <= 3) ? atoi(e) : 2;
-            if (p->bubbles) nlanes = 1;
+            if (p->bubbles == 1) nlanes = 1;  // (the device table takes inserts from every lane: atomics)
             c->two_lanes = nlanes > 1;
         }
 #endif
@@ -1823,7 +1998,7 @@ static dbtk_status_t run_batch_sync(dbtk_ctx_t* c, const uint8_t* d_seq, const u
         set_error("device reported an over-long read");
         return (dbtk_status_t)small[3];
     }
-    if (c->P.bubbles) {
+    if (c->P.bubbles == 1) {
         // Replay the batch's novel edges the way the reference accumulates them: the worker's per-batch
         // `bubbles[destLocus][edge]` is filled in pair order, mate 1 before mate 2, positions ascending
         // (AQ.cpp:2161-2166), then merged map by map into bubbleDB (accumBubbles, AQ.cpp:1599-1606).
@@ -2107,6 +2282,16 @@ static dbtk_status_t take_error_words(dbtk_ctx_t* c) {
                                               : "device reported an error during the batch");
         return (dbtk_status_t)e;
     }
+    if (c->d_bub) {  // the edge table's sticky word: inserts were lost, the table is short from then on
+        uint32_t ovf = 0;
+        HIPCHK(hipMemcpy(&ovf, c->d_nevents + BUB_W_OVF, 4, hipMemcpyDeviceToHost));
+        if (ovf) {
+            (void)hipMemset(c->d_nevents + BUB_W_OVF, 0, 4);
+            set_error("bubble table overflow: " + std::to_string(c->bub_slots) + " slots filled up inside a batch and the spill log of " + std::to_string(c->events_cap) +
+                      " entries with them; start with more slots (DBTK_BUB_SLOTS, a power of two)");
+            return DBTK_ERR_OVERFLOW;
+        }
+    }
     return DBTK_OK;
 }
 
@@ -2155,7 +2340,91 @@ dbtk_status_t dbtk_ctx_reset(dbtk_ctx_t* c) {
     c->m_bytes = 0; c->m_pairs = 0; c->m_maxlen = 0;
     c->alt.m_bytes = 0; c->alt.m_pairs = 0; c->alt.m_maxlen = 0;
     for (auto& l : c->parked) { l.m_bytes = 0; l.m_pairs = 0; l.m_maxlen = 0; }
+    if (c->d_bub) {  // the edge table: empty, at the capacity it has grown to
+        LAUNCH(k_bub_fill, dim3((uint32_t)std::min<uint64_t>((c->bub_slots + 255) / 256, 4096)), dim3(256), c->stream, c->d_bub, c->bub_slots);
+        HIPCHK(hipMemsetAsync(c->d_nevents, 0, 4 * BUB_WORDS, c->stream));
+        c->h_bub[0] = c->h_bub[1] = c->h_bub[2] = 0;
+        c->bub_seen = 0;
+    }
     HIPCHK(sync_all(c));
+    return DBTK_OK;
+}
+
+// The entries of the device table with count >= th, sorted by (locus, edge).  Waits for the context's batches, reports the sticky
+// words, and first puts whatever sits in the spill log back into a larger table.
+static dbtk_status_t bub_read(dbtk_ctx_t* c, uint32_t th, std::vector<BubSlot>& out, bool count_only = false, uint64_t* n_only = nullptr) {
+    out.clear();
+    if (!c->d_bub) { set_error("the context has no bubble table (params.bubbles = DBTK_BUBBLES_TABLE)"); return DBTK_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(sync_all(c));
+    { const dbtk_status_t es = take_error_words(c); if (es) return es; }
+    uint32_t nsp = 0;
+    HIPCHK(hipMemcpy(&nsp, c->d_nevents + BUB_W_SPILL, 4, hipMemcpyDeviceToHost));
+    if (nsp) { const dbtk_status_t st = bub_grow(c, 0); if (st) return st; }
+    hipStream_t s = c->stream;
+    unsigned long long* d_n = nullptr;
+    HIPCHK(hipMalloc(&d_n, 8));
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((c->bub_slots + 255) / 256, (uint64_t)c->num_cu * 8);
+    unsigned long long n = 0;
+    BubSlot* d_out = nullptr;
+    dbtk_status_t st = [&]() -> dbtk_status_t {
+        HIPCHK(hipMemsetAsync(d_n, 0, 8, s));
+        LAUNCH(k_bub_compact, dim3(grid), dim3(256), s, c->d_bub, c->bub_slots, th, (BubSlot*)nullptr, 0ull, d_n);
+        HIPCHK(hipMemcpyAsync(&n, d_n, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (n_only) *n_only = n;
+        if (count_only || !n) return DBTK_OK;
+        HIPCHK(hipMalloc(&d_out, n * sizeof(BubSlot)));
+        HIPCHK(hipMemsetAsync(d_n, 0, 8, s));
+        LAUNCH(k_bub_compact, dim3(grid), dim3(256), s, c->d_bub, c->bub_slots, th, d_out, (uint64_t)n, d_n);
+        out.resize(n);
+        HIPCHK(hipMemcpyAsync(out.data(), d_out, n * sizeof(BubSlot), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return DBTK_OK;
+    }();
+    (void)hipFree(d_n);
+    if (d_out) (void)hipFree(d_out);
+    if (st) { out.clear(); return st; }
+    std::sort(out.begin(), out.end(), [](const BubSlot& x, const BubSlot& y) { return x.locus1 != y.locus1 ? x.locus1 < y.locus1 : x.edge < y.edge; });
+    return DBTK_OK;
+}
+// dst's table += src's: src read out whole, uploaded as a list and inserted into a table of dst grown to hold both
+static dbtk_status_t bub_merge(dbtk_ctx_t* dst, dbtk_ctx_t* src) {
+    std::vector<BubSlot> ent;
+    dbtk_status_t st = bub_read(src, 0, ent);
+    if (st) return st;
+    HIPCHK(hipSetDevice(dst->device));
+    HIPCHK(sync_all(dst));
+    if ((st = take_error_words(dst))) return st;
+    if (ent.empty()) return DBTK_OK;
+    std::vector<BubEvent> ev(ent.size());
+    for (size_t i = 0; i < ent.size(); ++i) ev[i] = BubEvent{ent[i].count, 0u, 0u, ent[i].locus1 - 1, ent[i].edge};
+    BubEvent* d_ev = nullptr;
+    HIPCHK(hipMalloc(&d_ev, ev.size() * sizeof(BubEvent)));
+    st = [&]() -> dbtk_status_t {
+        HIPCHK(hipMemcpy(d_ev, ev.data(), ev.size() * sizeof(BubEvent), hipMemcpyHostToDevice));
+        return bub_grow(dst, 0, d_ev, ev.size());
+    }();
+    (void)hipFree(d_ev);
+    return st;
+}
+static dbtk_status_t dbtk_ctx_bubbles_impl(dbtk_ctx_t* c, uint32_t th, uint64_t* n, uint32_t* loci, uint64_t* edges, uint32_t* counts, uint64_t cap) {
+    if (!c || !n) { set_error("null argument"); return DBTK_ERR_ARG; }
+    *n = 0;
+    if (c->P.bubbles != DBTK_BUBBLES_TABLE) { set_error("dbtk_ctx_bubbles: the context was not created with params.bubbles = DBTK_BUBBLES_TABLE"); return DBTK_ERR_ARG; }
+    std::vector<BubSlot> ent;
+    const bool count_only = !loci && !edges && !counts;
+    uint64_t cnt = 0;
+    dbtk_status_t st = bub_read(c, th, ent, count_only, &cnt);
+    if (st) return st;
+    *n = cnt;
+    if (count_only) return DBTK_OK;
+    if (cnt > cap) { set_error("dbtk_ctx_bubbles: the arrays are too small (n is what is needed)"); return DBTK_ERR_OVERFLOW; }
+    for (uint64_t i = 0; i < cnt; ++i) {
+        if (loci) loci[i] = ent[i].locus1 - 1;
+        if (edges) edges[i] = ent[i].edge;
+        if (counts) counts[i] = ent[i].count;
+    }
     return DBTK_OK;
 }
 
@@ -2167,6 +2436,14 @@ static dbtk_status_t dbtk_ctx_write_bubbles_impl(dbtk_ctx_t* c, const char* out_
     if (!c->P.bubbles) { set_error("context was not created with params.bubbles"); return DBTK_ERR_ARG; }
     const uint64_t nloci = c->g->nloci;
     std::vector<uint64_t> index(nloci), ks, vs;
+    if (c->P.bubbles == DBTK_BUBBLES_TABLE) {
+        // the device table: the same container, the same threshold, the entries of a locus ascending by edge (the reference's order
+        // within a locus is its hash map's, and with -p > 1 whatever the threads' interleaving made it: as a set per locus the same file)
+        std::vector<BubSlot> ent;
+        const dbtk_status_t st = bub_read(c, 5, ent);
+        if (st) return st;
+        for (const BubSlot& e : ent) { ks.push_back(e.edge); vs.push_back(e.count); ++index[e.locus1 - 1]; }
+    } else
     for (uint64_t l = 0; l < nloci; ++l) {
         uint64_t kept = 0;
         for (auto& p : c->bubbleDB[l])
@@ -2215,6 +2492,8 @@ dbtk_status_t dbtk_ctx_merge_bait_hits(dbtk_ctx_t* dst, dbtk_ctx_t* src) {
 // Multi-GPU: fold src's bubble DB into dst's (after the run; the reference's order is unspecified for -p > 1).
 dbtk_status_t dbtk_ctx_merge_bubbles(dbtk_ctx_t* dst, dbtk_ctx_t* src) {
     if (!dst || !src || dst->bubbleDB.size() != src->bubbleDB.size()) { set_error("bad argument"); return DBTK_ERR_ARG; }
+    if (dst->P.bubbles != src->P.bubbles) { set_error("dbtk_ctx_merge_bubbles: one context keeps the event log's map, the other the device table (params.bubbles 1 and 2)"); return DBTK_ERR_ARG; }
+    if (dst->P.bubbles == DBTK_BUBBLES_TABLE) return dbtk::guarded([&] { return bub_merge(dst, src); });
     for (size_t l = 0; l < src->bubbleDB.size(); ++l)
         for (auto& q : src->bubbleDB[l]) dst->bubbleDB[l][q.first] += q.second;
     return DBTK_OK;
@@ -2596,7 +2875,7 @@ static dbtk_status_t dbtk_ingest_align_impl(dbtk_ingest_t* g, uint32_t slot, dbt
     { const dbtk_status_t sc = ingest_ctx(g, cx, &c); if (sc) return sc; }
     HIPCHK(hipSetDevice(c->device));
     if (sync) return run_batch_sync(c, S.d_flat, S.d_off, S.d_qual, ~0ull, h.nkept, (uint32_t)h.maxlen, nullptr, nullptr, nullptr, recs, rec_cap, nrec);
-    if (c->P.bubbles) { set_error("dbtk_ingest_align: -bu is replayed batch by batch on the host: sync = 1"); return DBTK_ERR_ARG; }
+    if (c->P.bubbles == 1) { set_error("dbtk_ingest_align: -bu is replayed batch by batch on the host: sync = 1"); return DBTK_ERR_ARG; }
     if (c->two_lanes) switch_lane(c);
     const dbtk_status_t st = launch_batch(c, S.d_flat, S.d_off, ~0ull, h.nkept, (uint32_t)h.maxlen, nullptr, 0, S.d_qual);
     if (st) return st;
@@ -2616,7 +2895,7 @@ static dbtk_status_t dbtk_ingest_align_merged_impl(dbtk_ingest_t* g, uint32_t sl
     dbtk_ctx* c = nullptr;
     { const dbtk_status_t sc = ingest_ctx(g, cx, &c); if (sc) return sc; }
     HIPCHK(hipSetDevice(c->device));
-    if (c->P.bubbles || c->P.trace || (c->P.bait && g->with_qual)) { set_error("dbtk_ingest_align_merged: records, -bu and -b with qualities go block by block (dbtk_ingest_align)"); return DBTK_ERR_ARG; }
+    if (c->P.bubbles == 1 || c->P.trace || (c->P.bait && g->with_qual)) { set_error("dbtk_ingest_align_merged: records, -bu and -b with qualities go block by block (dbtk_ingest_align)"); return DBTK_ERR_ARG; }
     hipStream_t s = c->stream;
     if (slot != ~0u) {
         dbtk_ingest::Slot& S = g->slots[slot];
@@ -2831,6 +3110,9 @@ dbtk_status_t dbtk_ctx_aln_records(dbtk_ctx_t* c, void* buf, uint64_t buf_bytes,
 }
 dbtk_status_t dbtk_ctx_aln_text(dbtk_ctx_t* c, uint32_t* idx, uint64_t idx_cap, void* arena, uint64_t arena_cap, uint64_t* arena_used) {
     return dbtk::guarded([&] { return dbtk_ctx_aln_text_impl(c, idx, idx_cap, arena, arena_cap, arena_used); });
+}
+dbtk_status_t dbtk_ctx_bubbles(dbtk_ctx_t* c, uint32_t th, uint64_t* n, uint32_t* loci, uint64_t* edges, uint32_t* counts, uint64_t cap) {
+    return dbtk::guarded([&] { return dbtk_ctx_bubbles_impl(c, th, n, loci, edges, counts, cap); });
 }
 dbtk_status_t dbtk_ctx_write_bubbles(dbtk_ctx_t* c, const char* out_prefix) {
     return dbtk::guarded([&] { return dbtk_ctx_write_bubbles_impl(c, out_prefix); });

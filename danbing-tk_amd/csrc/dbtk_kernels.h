@@ -30,6 +30,7 @@
 #include "dbtk_sort.h"
 #include "dbtk_tables.h"
 #include "dbtk_walk.h"
+#include "dbtk_bubtab.h"
 
 namespace dbtk {
 
@@ -220,6 +221,11 @@ struct BatchArgs {
     uint32_t k1_xcd;         // the encode stage cuts its tiles into one contiguous range per XCD (body_encode_subfilter); 0 = plain stride (DBTK_K1_XCD=0, the emulator)
     uint32_t vzero;          // always 0: `lane * vzero` makes an address look lane-dependent, so that a load whose value is only
                              // needed an iteration later is not turned into scalars (and waited for) right where it is issued
+    // -bu with the device table (P.bubbles = DBTK_BUBBLES_TABLE, dbtk_bubtab.h; behind everything else, so that no other field moves):
+    // the novel edges are counted here; `events` is then the spill log, `nevents` the BUB_W_* words
+    BubSlot* bub;
+    uint64_t bub_mask;
+    uint32_t bub_shift;
 };
 
 // Thousands of waves each flush a handful of counters at their end; atomics on ONE address serialize at the memory side
@@ -1726,7 +1732,8 @@ DBTK_HD void body_pair_usual(X& x, const BatchArgs& a) {
 }
 
 // ====================================================================== K3b =
-template <int NS, bool RECS, class X>
+// TAB: the novel edges of -bu go into the device table (dbtk_bubtab.h) instead of the event log
+template <int NS, bool RECS, bool TAB = false, class X>
 DBTK_HD void body_pair(X& x, const BatchArgs& a) {
     uint64_t* const ctr = counters_of(x, a);
     typedef PairSmemT<NS> Smem;
@@ -1740,6 +1747,7 @@ DBTK_HD void body_pair(X& x, const BatchArgs& a) {
     // per-block counters, flushed once at the end
     uint64_t c_kf = 0, c_hf = 0, c_qc = 0, c_thr = 0, c_feas = 0, c_asgn = 0, c_nhash1 = 0, c_vv = 0, c_cls = 0, c_inc = 0, c_bait = 0;
     uint64_t c_vote = 0;  // vv words the vote read (a path statistic, DBTK_PS_VOTE_VV: which pairs are voted on at all depends on the path)
+    uint32_t c_bubnew = 0;  // TAB: slots of the edge table this lane took (summed per wave at the end: the table's occupancy)
     DBTK_STAMP_DECL
     const uint32_t nsurv = *a.nsurv;
     const uint32_t nslp = a.nkp >> 6;  // slots the hit buffers reserve per read
@@ -2394,8 +2402,17 @@ DBTK_HD void body_pair(X& x, const BatchArgs& a) {
                                     if (i >= lo && i < hi) {
                                         const uint64_t e = ein[i];
                                         if (e != NAN64 && kl_lookup(T.tre, T.tre_mask, T.tre_shift, e, dst) == CLS_NONE) {
+                                            if constexpr (TAB) {
+                                                // (an insert that finds no slot goes to the spill log — count in `pair` — and into the table after its next growth)
+                                                if (!bub_insert(x, a.bub, a.bub_mask, a.bub_shift, e, dst, 1u, c_bubnew)) {
+                                                    const uint32_t at = x.atomic_add(a.nevents + BUB_W_SPILL, 1u);
+                                                    if (at < a.events_cap) a.events[at] = BubEvent{1u, 0u, 0u, dst, e};
+                                                    else a.nevents[BUB_W_OVF] = 1u;
+                                                }
+                                            } else {
                                             const uint32_t at = x.atomic_add(a.nevents, 1u);
                                             if (at < a.events_cap) a.events[at] = BubEvent{pair, (uint32_t)m, (uint32_t)i, dst, e};
+                                            }
                                         }
                                     }
                                 }
@@ -2433,6 +2450,10 @@ DBTK_HD void body_pair(X& x, const BatchArgs& a) {
         t = tnext;
     }
     DBTK_STAMP_FLUSH;
+    if constexpr (TAB) {  // one add per wave: the occupancy the host's growth rule reads
+        const uint32_t took = x.wave_sum(c_bubnew);
+        if (lane == 0 && took) x.atomic_add(a.nevents + BUB_W_OCC, took);
+    }
     if (lane == 0) {
         if (c_kf) x.atomic_add(&ctr[DBTK_C_KMERFILTERED], c_kf);
         if (c_hf) x.atomic_add(&ctr[DBTK_C_LOCUSFILTERED], c_hf);

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define DBTK_ABI_VERSION 10u  /* v10: dbtk_pred.h gains the dosage tables (dbtk_dosage_*); v9: dbtk_pred.h gains dbtk_pred_load_device and dbtk_pred_load_ctx; v8: dbtk_ingest_reserve_host; v7: DBTK_C_ALGO_VV = the vv words fillstats reads (the vote's words: DBTK_PS_VOTE_VV); DBTK_PS_PAIR_VV */
+#define DBTK_ABI_VERSION 11u  /* v11: params.bubbles = DBTK_BUBBLES_TABLE, dbtk_ctx_bubbles; v10: dbtk_pred.h gains the dosage tables (dbtk_dosage_*); v9: dbtk_pred.h gains dbtk_pred_load_device and dbtk_pred_load_ctx; v8: dbtk_ingest_reserve_host; v7: DBTK_C_ALGO_VV = the vv words fillstats reads (the vote's words: DBTK_PS_VOTE_VV); DBTK_PS_PAIR_VV */
 
 /* Reads longer than this are rejected (DBTK_ERR_READ_TOO_LONG).  The
  * reference's per-read k-mer multiplicity is a uint8_t pair (`PE_KMC`,
@@ -64,7 +64,8 @@ typedef struct dbtk_params {
     uint32_t okam;         /* !-ka [1]   emit kmer-assignment records */
     uint32_t qc;           /* -qc        per-locus QC mask present in the RPGG handle */
     uint32_t bait;         /* -b         bait filter (FPSv1); needs the bait DB in the RPGG handle */
-    uint32_t bubbles;      /* -bu        count novel (k+1)-mers; needs PREF.tre.kdb; host-buffer batches only */
+    uint32_t bubbles;      /* -bu        count novel (k+1)-mers; needs PREF.tre.kdb.  1: event log replayed on the host after every batch
+                            *             (the reference's -p 1 file order; host-buffer batches only, one lane); 2 = DBTK_BUBBLES_TABLE */
     uint32_t extract;      /* -e 1|2     extract mode: locus assignment only */
     uint32_t trace;        /* test hook: emit a record for EVERY pair, not only kam ones */
     uint32_t threading;    /* 0 off.  1 = -g/-gc/-gcc as the mounted HEAD runs them: the call sites are commented out
@@ -451,6 +452,20 @@ dbtk_status_t dbtk_ctx_merge_bait_hits(dbtk_ctx_t* dst, dbtk_ctx_t* src);
  * (dumpBubbles, src/aQueryFasta_thread.h:1006-1008: entries with count >= 5).  merge: fold another GPU's DB in. */
 dbtk_status_t dbtk_ctx_write_bubbles(dbtk_ctx_t* ctx, const char* out_prefix);
 dbtk_status_t dbtk_ctx_merge_bubbles(dbtk_ctx_t* dst, dbtk_ctx_t* src);
+
+/* params.bubbles = DBTK_BUBBLES_TABLE (ABI v11): the counts live in a table (locus, edge) -> uint32 in device memory that the resolve
+ * kernel adds to.  No host step per batch: such a context runs on both lanes and takes dbtk_align_batch_device,
+ * dbtk_ingest_align(sync = 0) and dbtk_ingest_align_merged.  The table starts with DBTK_BUB_SLOTS slots of 16 bytes (environment, a power
+ * of two, default 2^24 = 256 MB) and doubles, between batches, when it is more than half full; inserts that find no slot inside a batch wait
+ * in a spill log for the next growth, and only when that overflows too is DBTK_ERR_OVERFLOW reported (sticky: dbtk_ctx_synchronize,
+ * dbtk_ctx_counts, dbtk_ctx_bubbles).  dbtk_ctx_reset empties the table; dbtk_ctx_table_bytes reports it ("bubble_table").
+ * dbtk_ctx_write_bubbles writes the same container as for params.bubbles = 1, threshold 5, the entries of a locus ascending by edge: the
+ * reference's file as a set per locus (its own order inside a locus is a hash map's, and with -p > 1 depends on the threads).
+ * dbtk_ctx_merge_bubbles takes two such contexts (a pair of different kinds: DBTK_ERR_ARG).
+ * dbtk_ctx_bubbles: waits for the context's batches; the entries with count >= th sorted by (locus, edge) into the arrays (each may be
+ * null), *n = how many; all three arrays null: *n only; DBTK_ERR_OVERFLOW (nothing copied, *n set) when cap is smaller. */
+#define DBTK_BUBBLES_TABLE 2u
+dbtk_status_t dbtk_ctx_bubbles(dbtk_ctx_t* ctx, uint32_t th, uint64_t* n, uint32_t* loci, uint64_t* edges, uint32_t* counts, uint64_t cap);
 
 /* ---- dumps: src/aQueryFasta_thread.cpp:2631-2641 --------------------------*/
 /* `ktools serialize PREF` (src/kmertools.cpp:221-345): PREF.tr.kmers + PREF.fl.kmers
