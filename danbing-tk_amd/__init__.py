@@ -450,6 +450,8 @@ EXPORTS_PRED = [
     "dbtk_pred_create", "dbtk_pred_free", "dbtk_pred_create_from_file", "dbtk_pred_nk", "dbtk_pred_ntr", "dbtk_pred_load_samples",
     "dbtk_pred_load_device", "dbtk_pred_load_ctx",
     "dbtk_pred_correct", "dbtk_pred_matrix", "dbtk_pred_bias", "dbtk_pred_times",
+    "dbtk_pred_create_windowed", "dbtk_pred_create_windowed_from_file", "dbtk_pred_max_rows", "dbtk_pred_window", "dbtk_pred_window_submit",
+    "dbtk_pred_window_outputs", "dbtk_pred_window_outputs_pinned", "dbtk_pred_window_stage",
 ]
 
 # ... and its dosage tables (ABI v10)
@@ -483,8 +485,9 @@ class Pred:
         self.ns, self.ntr = int(ns), len(self.nk_cum)
         self.nk = int(nk if nk is not None else (self.nk_cum[-1] if self.ntr else 0))
         self.h = C.c_void_p()
-        lib._chk(L.dbtk_pred_create(device, self.ns, self.nk, self.ntr, _ptr(self.nk_cum, u32p), _ptr(self.nik_cum, u32p), len(self.iki),
-                                    _ptr(self.iki, u32p), _ptr(self.ikmc, u8p), C.byref(self.h)))
+        create = getattr(self, "_create", L.dbtk_pred_create)  # (PredWindowed: dbtk_pred_create_windowed with its max_rows)
+        lib._chk(create(device, self.ns, self.nk, self.ntr, _ptr(self.nk_cum, u32p), _ptr(self.nik_cum, u32p), len(self.iki),
+                        _ptr(self.iki, u32p), _ptr(self.ikmc, u8p), C.byref(self.h)))
 
     def load(self, first, counts, depths):
         counts = np.ascontiguousarray(counts, np.uint64)
@@ -524,6 +527,61 @@ class Pred:
         if self.h:
             self._lib.L.dbtk_pred_free(self.h)
             self.h = None
+
+
+class PredWindowed(Pred):
+    """A windowed dbtk_pred_t (include/dbtk_pred.h, "Windows"): G holds at most max_rows k-mer columns, whole loci at a time.  load /
+    load_device take the current window's counts (n x rows); matrix() returns rows x ns; bias() the whole table."""
+
+    def __init__(self, lib, ns, nk_cum, nik_cum, iki, ikmc, max_rows, nk=None, device=0, ikmer_meta=None):
+        L = lib.L
+        fp = C.POINTER(C.c_float)
+        L.dbtk_pred_create_windowed.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, u32p, u32p, C.c_uint64, u32p, u8p, C.c_uint64, C.POINTER(C.c_void_p)]
+        L.dbtk_pred_create_windowed_from_file.argtypes = [C.c_int, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p)]
+        L.dbtk_pred_max_rows.argtypes = [C.c_void_p]
+        L.dbtk_pred_max_rows.restype = C.c_uint64
+        for f in (L.dbtk_pred_nk, L.dbtk_pred_ntr):
+            f.argtypes = [C.c_void_p]
+            f.restype = C.c_uint64
+        L.dbtk_pred_window.argtypes = [C.c_void_p, C.c_uint64, u64p, u64p, u64p]
+        L.dbtk_pred_window_submit.argtypes = [C.c_void_p]
+        L.dbtk_pred_window_outputs.argtypes = [C.c_void_p, fp, fp]
+        L.dbtk_pred_window_outputs_pinned.argtypes = [C.c_void_p, C.POINTER(fp), C.POINTER(fp), u64p]
+        L.dbtk_pred_window_stage.argtypes = [C.c_void_p, C.POINTER(u64p), u64p]
+        self._create = lambda device, ns, nk, ntr, a, b, nik, c, d, out: (
+            L.dbtk_pred_create_windowed_from_file(device, ns, os.fsencode(ikmer_meta), int(max_rows), out) if ikmer_meta is not None
+            else L.dbtk_pred_create_windowed(device, ns, nk, ntr, a, b, nik, c, d, int(max_rows), out))
+        if ikmer_meta is not None:
+            nk_cum = nik_cum = iki = ikmc = []
+        super().__init__(lib, ns, nk_cum, nik_cum, iki, ikmc, nk=nk, device=device)
+        self.nk, self.ntr = int(L.dbtk_pred_nk(self.h)), int(L.dbtk_pred_ntr(self.h))
+        self.max_rows = int(L.dbtk_pred_max_rows(self.h))
+        self.first, self.end, self.row0, self.rows = 0, 0, 0, 0
+        self.window(0)
+
+    def window(self, first_locus):
+        """dbtk_pred_window: (end_locus, first_row, rows) of the window that starts at first_locus; it becomes the current one."""
+        e, r0, r = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._lib._chk(self._lib.L.dbtk_pred_window(self.h, int(first_locus), C.byref(e), C.byref(r0), C.byref(r)))
+        self.first, self.end, self.row0, self.rows = int(first_locus), int(e.value), int(r0.value), int(r.value)
+        return self.end, self.row0, self.rows
+
+    def matrix(self):
+        out = np.empty((self.rows, self.ns), np.float32)
+        self._lib._chk(self._lib.L.dbtk_pred_matrix(self.h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def submit(self):
+        self._lib._chk(self._lib.L.dbtk_pred_window_submit(self.h))
+        self._sub_rows = self.rows
+
+    def outputs(self):
+        """dbtk_pred_window_outputs: (raw, corrected) of the submitted window — or of the current one —, rows x ns each."""
+        rows = self.__dict__.pop("_sub_rows", self.rows)
+        raw, cor = np.empty((rows, self.ns), np.float32), np.empty((rows, self.ns), np.float32)
+        fp = C.POINTER(C.c_float)
+        self._lib._chk(self._lib.L.dbtk_pred_window_outputs(self.h, raw.ctypes.data_as(fp), cor.ctypes.data_as(fp)))
+        return raw, cor
 
 
 class Dosage:

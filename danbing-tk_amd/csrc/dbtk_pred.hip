@@ -12,6 +12,7 @@
 
 #include "../../include/dbtk_pred.h"
 #include "dbtk_internal.h"
+#include "dbtk_pred_plan.h"
 
 using namespace dbtk;
 
@@ -65,19 +66,21 @@ __global__ void __launch_bounds__(256) k_pred_load_col(const uint64_t* __restric
 // over the locus' invariant k-mers in their order, per sample, then / n.  One lane per sample: row iki[j] of G is read
 // coalesced, the adds of a lane are sequential (the order Eigen's scalar reduction takes).
 __global__ void __launch_bounds__(64) k_pred_bias(const float* __restrict__ G, const uint32_t* __restrict__ nk_cum, const uint32_t* __restrict__ nik_cum,
-                                                  const uint32_t* __restrict__ iki, const float* __restrict__ ikmc, float* __restrict__ bias, uint64_t ns) {
-    const uint32_t tri = blockIdx.x;
+                                                  const uint32_t* __restrict__ iki, const float* __restrict__ ikmc, float* __restrict__ bias, uint64_t ns,
+                                                  uint32_t tri0, uint32_t row0) {
+    const uint32_t tri = tri0 + blockIdx.x;
     const uint64_t s = (uint64_t)blockIdx.y * 64 + threadIdx.x;
     const uint32_t si = tri ? nk_cum[tri - 1] : 0u, ei = nk_cum[tri], isi = tri ? nik_cum[tri - 1] : 0u, iei = nik_cum[tri];
     if (si == ei || isi == iei || s >= ns) return;
     float acc = 0.f;
-    for (uint32_t j = isi; j < iei; ++j) acc += G[(uint64_t)iki[j] * ns + s] / ikmc[j];
+    for (uint32_t j = isi; j < iei; ++j) acc += G[(uint64_t)(iki[j] - row0) * ns + s] / ikmc[j];
     bias[(uint64_t)tri * ns + s] = acc / (float)(iei - isi);
 }
 // second half (pred.h:229-231): bias /= bias.mean() over the samples.  One block per locus; the mean is a pairwise tree.
-__global__ void __launch_bounds__(256) k_pred_bias_norm(const uint32_t* __restrict__ nk_cum, const uint32_t* __restrict__ nik_cum, float* __restrict__ bias, uint64_t ns) {
+__global__ void __launch_bounds__(256) k_pred_bias_norm(const uint32_t* __restrict__ nk_cum, const uint32_t* __restrict__ nik_cum, float* __restrict__ bias, uint64_t ns,
+                                                        uint32_t tri0) {
     __shared__ float part[256];
-    const uint32_t tri = blockIdx.x;
+    const uint32_t tri = tri0 + blockIdx.x;
     const uint32_t si = tri ? nk_cum[tri - 1] : 0u, ei = nk_cum[tri], isi = tri ? nik_cum[tri - 1] : 0u, iei = nik_cum[tri];
     if (si == ei || isi == iei) return;
     float* b = bias + (uint64_t)tri * ns;
@@ -114,6 +117,74 @@ __global__ void __launch_bounds__(256) k_pred_correct(float* __restrict__ G, con
         }
 #pragma unroll
         for (int r = 0; r < PR_ROWS; ++r) if (tri[r] != NOLOC) G[(r0 + r) * ns + s] = g[r] / b[r];
+    }
+}
+
+// ---- a window's fused pass (dbtk_pred.h: dbtk_pred_window_submit).  The window's counts of ALL samples are staged in HBM,
+// sample-major: wc[s * rows + r] = count of k-mer row0 + r in sample s.  Two kernels and k_pred_bias_norm between them make the raw
+// window, the corrected window and the window's Bias rows without G: 8 bytes read and 8 written per entry, once.
+//
+// The raw bias sums from the counts: k_pred_bias with G(k, s) replaced by the expression that made it, (float)count / depth — then
+// / ikmc[j], the adds sequential in j from 0.f, / (float)n: the same operations on the same values, so the same bits.  One wave per
+// locus and 64 samples.  A lane of k_pred_bias reads G along the samples; here the samples are the slow axis, so the wave reads a
+// sample's counts along j (lane = invariant k-mer: neighbours in iki are neighbours in the file), turns the terms in LDS, and lane s
+// then adds its column in j order.  WB_J invariant k-mers per turn; the running sum stays in the lane's register across turns.
+constexpr int WB_J = 64, WB_S = 64;
+__global__ void __launch_bounds__(64) k_pred_wbias(const uint64_t* __restrict__ wc, const float* __restrict__ depth, const uint32_t* __restrict__ nk_cum,
+                                                   const uint32_t* __restrict__ nik_cum, const uint32_t* __restrict__ iki, const float* __restrict__ ikmc,
+                                                   float* __restrict__ bias, uint64_t ns, uint64_t rows, uint32_t tri0, uint32_t row0) {
+    __shared__ float terms[WB_J][WB_S + 1];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t tri = tri0 + blockIdx.x;
+    const uint64_t s0 = (uint64_t)blockIdx.y * WB_S;
+    const uint32_t si = tri ? nk_cum[tri - 1] : 0u, ei = nk_cum[tri], isi = tri ? nik_cum[tri - 1] : 0u, iei = nik_cum[tri];
+    if (si == ei || isi == iei || s0 >= ns) return;  // (uniform in the wave)
+    const uint32_t nsl = ns - s0 < (uint64_t)WB_S ? (uint32_t)(ns - s0) : (uint32_t)WB_S;
+    float acc = 0.f;
+    for (uint32_t j0 = isi; j0 < iei; j0 += WB_J) {
+        const uint32_t nj = iei - j0 < (uint32_t)WB_J ? iei - j0 : (uint32_t)WB_J;
+        if (lane < nj) {
+            const uint64_t r = (uint64_t)(iki[j0 + lane] - row0);  // (create_windowed: an invariant k-mer lies inside its locus, so 0 <= r < rows)
+            const float kc = ikmc[j0 + lane];
+            for (uint32_t i = 0; i < nsl; ++i) terms[lane][i] = ((float)wc[(s0 + i) * rows + r] / depth[s0 + i]) / kc;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (lane < nsl) for (uint32_t j = 0; j < nj; ++j) acc += terms[j][lane];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (lane < nsl) bias[(uint64_t)tri * ns + s0 + lane] = acc / (float)(iei - isi);
+}
+// Both matrices of the window from one pass over its counts: k_pred_load's tile (64 k-mers x 32 samples, read along k, turned in LDS,
+// written along the samples), and where it stores G the raw value goes to raw[r][s] and raw / Bias(locus of r, s) to cor[r][s] — the
+// division of k_pred_correct on the value k_pred_load would have stored.  A row of no corrected locus (loc = NOLOC) is copied.
+// loc = d_loc + row0 (the window's rows), bias the whole [ntr][ns] table after k_pred_bias_norm.
+__global__ void __launch_bounds__(64) k_pred_wfused(const uint64_t* __restrict__ wc, const float* __restrict__ depth, const uint32_t* __restrict__ loc,
+                                                    const float* __restrict__ bias, float* __restrict__ raw, float* __restrict__ cor, uint64_t rows, uint64_t ns) {
+    __shared__ float tile[PT_K][PT_S + 1];
+    const int lane = threadIdx.x;
+    const uint64_t k0 = (uint64_t)blockIdx.x * PT_K;
+    for (uint64_t i0 = (uint64_t)blockIdx.y * PT_S; i0 < ns; i0 += (uint64_t)gridDim.y * PT_S) {
+        const uint32_t ni = ns - i0 < (uint64_t)PT_S ? (uint32_t)(ns - i0) : (uint32_t)PT_S;
+        for (uint32_t i = 0; i < ni; ++i) {
+            const uint64_t k = k0 + lane;
+            tile[lane][i] = k < rows ? (float)wc[(i0 + i) * rows + k] / depth[i0 + i] : 0.f;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        for (int r = lane / PT_S; r < PT_K; r += 64 / PT_S) {
+            const uint32_t i = lane % PT_S;
+            if (k0 + r < rows && i < ni) {
+                const uint32_t tri = loc[k0 + r];
+                const float g = tile[r][i];
+                const uint64_t at = (k0 + r) * ns + i0 + i;
+                raw[at] = g;
+                cor[at] = tri != NOLOC ? g / bias[(uint64_t)tri * ns + i0 + i] : g;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
     }
 }
 
@@ -274,15 +345,107 @@ struct dbtk_pred {
     hipStream_t stream = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     float ms[3] = {0, 0, 0};
+    // ---- a windowed handle (dbtk_pred_create_windowed): d_G holds max_rows x ns floats, the rows of the current window
+    bool windowed = false;
+    uint64_t max_rows = 0;
+    std::vector<uint32_t> nkc;                       // host copy of nk_cum: the window planning
+    uint64_t w_first = 0, w_end = 0, w_row0 = 0, w_rows = 0;  // the current window: loci [w_first, w_end), k-mers [w_row0, w_row0 + w_rows)
+    int cur = 0;                                     // its buffer: d_wc[cur], ws[cur]
+    uint64_t* d_wc[2] = {nullptr, nullptr};          // the window's staged counts, [ns][w_rows] u64 (sample-major like the files)
+    float* d_wdepth[2] = {nullptr, nullptr};         // [ns]
+    float* h_depth[2] = {nullptr, nullptr};          // pinned [ns]: 1 until the sample is loaded into the window
+    float *d_raw = nullptr, *d_cor = nullptr;        // what the fused pass writes, [w_rows][ns] each (one set: one window's outputs are in flight at a time)
+    uint64_t* h_stage = nullptr;                     // pinned, PW_STAGE x max_rows counts: what dbtk_pred_load_samples sends from
+    float *h_raw = nullptr, *h_cor = nullptr;        // pinned, max_rows x ns: where the fused pass' outputs land
+    hipStream_t stream2 = nullptr;                   // ws[1] (ws[0] = stream): a window's copies and kernels run on its buffer's stream
+    std::vector<uint8_t> dirty;                      // [ns]: staged into the window since d_G was last made from the staged counts
+    int pending = -1;                                // the buffer whose fused pass was submitted and not collected yet
+    uint64_t pend_rows = 0;
+    hipStream_t ws(int slot) const { return slot ? stream2 : stream; }
 };
+constexpr uint64_t PW_STAGE = 4;  // samples per transfer of dbtk_pred_load_samples on a windowed handle (host memory is what windows are for)
+
+// the window that starts at locus `first` becomes the current one, on the buffer that holds no submitted window; its staged counts,
+// its depths and its part of G are zeroed.  Returns with the buffer's stream idle.
+static dbtk_status_t pred_open_window(dbtk_pred* p, uint64_t first) {
+    uint64_t end = 0, row0 = 0, rows = 0;
+    if (first >= p->ntr) { set_error("dbtk_pred_window: first_locus " + std::to_string(first) + " >= ntr " + std::to_string(p->ntr)); return DBTK_ERR_ARG; }
+    if (!dbtk_pred_plan::window(p->nkc.data(), p->ntr, p->nk, p->max_rows, first, &end, &row0, &rows)) { set_error("dbtk_pred_window: locus does not fit"); return DBTK_ERR_ARG; }
+    PCHK(hipSetDevice(p->device));
+    const int slot = p->pending == (p->cur ^ 1) ? p->cur : p->cur ^ 1;
+    hipStream_t s = p->ws(slot);
+    if (rows) {
+        PCHK(hipMemsetAsync(p->d_wc[slot], 0, p->ns * rows * 8, s));
+        PCHK(hipMemsetAsync(p->d_G, 0, p->ns * rows * sizeof(float), s));
+    }
+    for (uint64_t i = 0; i < p->ns; ++i) p->h_depth[slot][i] = 1.f;
+    std::fill(p->dirty.begin(), p->dirty.end(), (uint8_t)0);
+    PCHK(hipStreamSynchronize(s));
+    p->cur = slot; p->w_first = first; p->w_end = end; p->w_row0 = row0; p->w_rows = rows;
+    return DBTK_OK;
+}
+// a windowed handle's d_G is made from the staged counts when somebody asks for it (dbtk_pred_matrix, dbtk_pred_correct): the columns
+// staged since the last time, run by run, through the whole-matrix handle's tile kernel.  Asynchronous on the window's stream.
+static dbtk_status_t pred_window_materialize(dbtk_pred* p) {
+    hipStream_t s = p->ws(p->cur);
+    const uint64_t rows = p->w_rows, ns = p->ns;
+    bool sent = false;
+    for (uint64_t a = 0; a < ns;) {
+        if (!p->dirty[a]) { ++a; continue; }
+        uint64_t b = a;
+        while (b < ns && p->dirty[b]) p->dirty[b++] = 0;
+        if (rows) {
+            if (!sent) { PCHK(hipMemcpyAsync(p->d_wdepth[p->cur], p->h_depth[p->cur], ns * 4, hipMemcpyHostToDevice, s)); sent = true; }
+            const uint64_t kt = (rows + PT_K - 1) / PT_K, n = b - a;
+            const uint32_t gy = (uint32_t)std::min<uint64_t>((n + PT_S - 1) / PT_S, 64);
+            hipLaunchKernelGGL(k_pred_load, dim3((uint32_t)kt, gy), dim3(64), 0, s, p->d_wc[p->cur] + a * rows, p->d_wdepth[p->cur] + a, p->d_G, rows, ns, a, (uint32_t)n);
+            PCHK(hipGetLastError());
+        }
+        a = b;
+    }
+    if (sent) PCHK(hipStreamSynchronize(s));  // (h_depth may change with the next load)
+    return DBTK_OK;
+}
+// host counts into the current window: counts[i * rows + r].  Sent PW_STAGE samples at a time from the pinned staging buffer; a caller
+// that filled that buffer itself (dbtk_pred_window_stage) skips the copy into it.
+static dbtk_status_t pred_window_load_host(dbtk_pred* p, uint64_t first, uint64_t n, const uint64_t* counts, const float* read_depth) {
+    hipStream_t s = p->ws(p->cur);
+    const uint64_t rows = p->w_rows;
+    for (uint64_t i0 = 0; i0 < n && rows; i0 += PW_STAGE) {
+        const uint64_t ni = std::min<uint64_t>(PW_STAGE, n - i0);
+        const uint64_t* src = counts + i0 * rows;
+        if (src != p->h_stage) memcpy(p->h_stage, src, ni * rows * 8);
+        PCHK(hipMemcpyAsync(p->d_wc[p->cur] + (first + i0) * rows, p->h_stage, ni * rows * 8, hipMemcpyHostToDevice, s));
+        PCHK(hipStreamSynchronize(s));  // (the staging buffer is free again)
+    }
+    for (uint64_t i = 0; i < n; ++i) { p->h_depth[p->cur][first + i] = read_depth[i]; p->dirty[first + i] = 1; }
+    return DBTK_OK;
+}
 
 extern "C" {
 
 static dbtk_status_t dbtk_pred_create_impl(int device_id, uint64_t ns, uint64_t nk, uint64_t ntr, const uint32_t* nk_cum, const uint32_t* nik_cum,
-                               uint64_t nik, const uint32_t* iki, const uint8_t* ikmc, dbtk_pred_t** out) {
+                               uint64_t nik, const uint32_t* iki, const uint8_t* ikmc, bool windowed, uint64_t max_rows, dbtk_pred_t** out) {
     if (!out) { set_error("null argument"); return DBTK_ERR_ARG; }
     *out = nullptr;
     { const dbtk_status_t cs = check_ikmer_meta(device_id, ns, nk, ntr, nk_cum, nik_cum, nik, iki, ikmc); if (cs) return cs; }
+    if (windowed) {
+        if (!max_rows) { set_error("max_rows must be positive"); return DBTK_ERR_ARG; }
+        if (max_rows > nk) max_rows = nk;
+        uint64_t size = 0;
+        const uint64_t big = dbtk_pred_plan::first_oversized(nk_cum, ntr, nk, max_rows, &size);
+        if (big < ntr) {
+            set_error("locus " + std::to_string(big) + " has " + std::to_string(size) + " k-mers, a window holds max_rows = " + std::to_string(max_rows));
+            return DBTK_ERR_ARG;
+        }
+        // a window holds whole loci and nothing else: the bias of a locus may read that locus' columns only (as every ikmer.meta has it)
+        for (uint64_t t = 0; t < ntr; ++t) {
+            const uint32_t a = t ? nk_cum[t - 1] : 0u, b = nk_cum[t];
+            for (uint32_t j = t ? nik_cum[t - 1] : 0u; j < nik_cum[t]; ++j)
+                if (iki[j] < a || iki[j] >= b) { set_error("ikmer.meta: invariant k-mer " + std::to_string(j) + " lies outside its locus " + std::to_string(t) + ": no windows over this build"); return DBTK_ERR_FORMAT; }
+        }
+    }
+    const uint64_t grows = windowed ? max_rows : nk;  // rows of d_G
     std::vector<float> kc(nik);
     for (uint64_t j = 0; j < nik; ++j) kc[j] = (float)ikmc[j];
     std::vector<uint32_t> loc(nk, NOLOC);  // (k-mers past the last locus' cumulative count belong to no locus, like in the reference's loop)
@@ -291,21 +454,51 @@ static dbtk_status_t dbtk_pred_create_impl(int device_id, uint64_t ns, uint64_t 
         if (a == b || c == d) continue;
         for (uint32_t k = a; k < b; ++k) loc[k] = (uint32_t)t;
     }
+    std::vector<uint32_t> nkc;
+    std::vector<uint8_t> dirty;
+    if (windowed) { nkc.assign(nk_cum, nk_cum + ntr); dirty.assign(ns, 0); }
     dbtk_pred* p = new dbtk_pred;  // (after the host-side vectors: nothing below throws)
     p->device = device_id; p->ns = ns; p->nk = nk; p->ntr = ntr; p->nik = nik;
+    p->windowed = windowed; p->max_rows = windowed ? max_rows : 0; p->nkc.swap(nkc); p->dirty.swap(dirty);
     dbtk_status_t st = DBTK_OK;
     auto fail = [&](hipError_t e, const char* what) { set_error(std::string(what) + ": " + hipGetErrorString(e)); st = DBTK_ERR_HIP; };
     hipError_t e;
     if ((e = hipStreamCreate(&p->stream)) != hipSuccess) fail(e, "hipStreamCreate");
     for (int i = 0; i < 4 && !st; ++i) if ((e = hipEventCreate(&p->ev[i])) != hipSuccess) fail(e, "hipEventCreate");
-    if (!st && (e = hipMalloc(&p->d_G, nk * ns * sizeof(float))) != hipSuccess) {
+    if (!st && (e = hipMalloc(&p->d_G, grows * ns * sizeof(float))) != hipSuccess) {
         if (e == hipErrorOutOfMemory) {  // the one allocation of this handle that competes with an aligner's tables for the HBM
             (void)hipGetLastError();
             size_t fr = 0, tot = 0;
             (void)hipMemGetInfo(&fr, &tot);
-            set_error("genotype matrix: 4 * nk * ns = " + std::to_string(nk * ns * sizeof(float)) + " bytes do not fit, " + std::to_string(fr) + " of " + std::to_string(tot) + " bytes of HBM are free");
+            set_error(std::string("genotype matrix: 4 * ") + (windowed ? "max_rows" : "nk") + " * ns = " + std::to_string(grows * ns * sizeof(float)) + " bytes do not fit, " + std::to_string(fr) + " of " + std::to_string(tot) + " bytes of HBM are free");
             st = DBTK_ERR_NOMEM;
         } else fail(e, "hipMalloc (genotype matrix)");
+    }
+    if (windowed) {  // the window buffers, device and pinned host, sized once: 24 * max_rows * ns bytes of HBM beside the matrix' 4
+        auto take = [&](hipError_t er, const char* what) {
+            if (er == hipSuccess) return;
+            if (er == hipErrorOutOfMemory) {
+                (void)hipGetLastError();
+                size_t fr = 0, tot = 0;
+                (void)hipMemGetInfo(&fr, &tot);
+                set_error(std::string(what) + " of a window of max_rows = " + std::to_string(max_rows) + " x ns = " + std::to_string(ns) + " do not fit, " + std::to_string(fr) + " of " +
+                          std::to_string(tot) + " bytes of HBM are free");
+                st = DBTK_ERR_NOMEM;
+            } else fail(er, what);
+        };
+        const uint64_t cells = max_rows * ns;
+        if (!st) take(hipStreamCreate(&p->stream2), "hipStreamCreate");
+        for (int i = 0; i < 2; ++i) {
+            if (!st) take(hipMalloc(&p->d_wc[i], cells * 8), "hipMalloc (staged counts)");
+            if (!st) take(hipMalloc(&p->d_wdepth[i], ns * 4), "hipMalloc (depths)");
+            if (!st) take(hipHostMalloc(&p->h_depth[i], ns * 4), "hipHostMalloc (depths)");
+            for (uint64_t s = 0; s < ns && !st; ++s) p->h_depth[i][s] = 1.f;
+        }
+        if (!st) take(hipMalloc(&p->d_raw, cells * 4), "hipMalloc (raw window)");
+        if (!st) take(hipMalloc(&p->d_cor, cells * 4), "hipMalloc (corrected window)");
+        if (!st) take(hipHostMalloc(&p->h_stage, PW_STAGE * max_rows * 8), "hipHostMalloc (count staging)");
+        if (!st) take(hipHostMalloc(&p->h_raw, cells * 4), "hipHostMalloc (raw window)");
+        if (!st) take(hipHostMalloc(&p->h_cor, cells * 4), "hipHostMalloc (corrected window)");
     }
     if (!st && (e = hipMalloc(&p->d_bias, ntr * ns * sizeof(float))) != hipSuccess) fail(e, "hipMalloc (bias matrix)");
     if (!st && (e = hipMalloc(&p->d_nk, ntr * 4)) != hipSuccess) fail(e, "hipMalloc");
@@ -314,13 +507,14 @@ static dbtk_status_t dbtk_pred_create_impl(int device_id, uint64_t ns, uint64_t 
     if (!st && (e = hipMalloc(&p->d_loc, nk * 4)) != hipSuccess) fail(e, "hipMalloc");
     if (!st && (e = hipMemcpyAsync(p->d_loc, loc.data(), nk * 4, hipMemcpyHostToDevice, p->stream)) != hipSuccess) fail(e, "hipMemcpy");
     if (!st && (e = hipMalloc(&p->d_ikmc, (nik + 1) * 4)) != hipSuccess) fail(e, "hipMalloc");
-    if (!st && (e = hipMemsetAsync(p->d_G, 0, nk * ns * sizeof(float), p->stream)) != hipSuccess) fail(e, "hipMemset");
+    if (!st && (e = hipMemsetAsync(p->d_G, 0, grows * ns * sizeof(float), p->stream)) != hipSuccess) fail(e, "hipMemset");
     if (!st && (e = hipMemsetAsync(p->d_bias, 0, ntr * ns * sizeof(float), p->stream)) != hipSuccess) fail(e, "hipMemset");
     if (!st && (e = hipMemcpyAsync(p->d_nk, nk_cum, ntr * 4, hipMemcpyHostToDevice, p->stream)) != hipSuccess) fail(e, "hipMemcpy");
     if (!st && (e = hipMemcpyAsync(p->d_nik, nik_cum, ntr * 4, hipMemcpyHostToDevice, p->stream)) != hipSuccess) fail(e, "hipMemcpy");
     if (!st && nik && (e = hipMemcpyAsync(p->d_iki, iki, nik * 4, hipMemcpyHostToDevice, p->stream)) != hipSuccess) fail(e, "hipMemcpy");
     if (!st && nik && (e = hipMemcpyAsync(p->d_ikmc, kc.data(), nik * 4, hipMemcpyHostToDevice, p->stream)) != hipSuccess) fail(e, "hipMemcpy");
     if (!st && (e = hipStreamSynchronize(p->stream)) != hipSuccess) fail(e, "hipStreamSynchronize");
+    if (!st && windowed) st = pred_open_window(p, 0);  // a windowed handle always has a current window
     if (st) { dbtk_pred_free(p); return st; }
     *out = p;
     return DBTK_OK;
@@ -329,19 +523,25 @@ static dbtk_status_t dbtk_pred_create_impl(int device_id, uint64_t ns, uint64_t 
 void dbtk_pred_free(dbtk_pred_t* p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
-    void* ptrs[] = {p->d_G, p->d_bias, p->d_nk, p->d_nik, p->d_iki, p->d_loc, p->d_ikmc, p->d_counts, p->d_depth, p->d_depth2};
+    if (p->stream) (void)hipStreamSynchronize(p->stream);
+    if (p->stream2) (void)hipStreamSynchronize(p->stream2);  // (a submitted window that nobody collected)
+    void* ptrs[] = {p->d_G, p->d_bias, p->d_nk, p->d_nik, p->d_iki, p->d_loc, p->d_ikmc, p->d_counts, p->d_depth, p->d_depth2,
+                    p->d_wc[0], p->d_wc[1], p->d_wdepth[0], p->d_wdepth[1], p->d_raw, p->d_cor};
     for (void* q : ptrs) if (q) (void)hipFree(q);
+    void* pinned[] = {p->h_depth[0], p->h_depth[1], p->h_stage, p->h_raw, p->h_cor};
+    for (void* q : pinned) if (q) (void)hipHostFree(q);
     for (auto& e : p->ev) if (e) (void)hipEventDestroy(e);
     if (p->stream) (void)hipStreamDestroy(p->stream);
+    if (p->stream2) (void)hipStreamDestroy(p->stream2);
     delete p;
 }
 
-static dbtk_status_t dbtk_pred_create_from_file_impl(int device_id, uint64_t ns, const char* ikmer_meta, dbtk_pred_t** out) {
+static dbtk_status_t dbtk_pred_create_from_file_impl(int device_id, uint64_t ns, const char* ikmer_meta, bool windowed, uint64_t max_rows, dbtk_pred_t** out) {
     if (!ikmer_meta || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
     *out = nullptr;
     IkmerMeta m;
     { const dbtk_status_t st = read_ikmer_meta(ikmer_meta, &m); if (st) return st; }
-    return dbtk_pred_create(device_id, ns, m.nk, m.ntr, m.nkc.data(), m.nikc.data(), m.nik, m.iki.data(), m.kc.data(), out);
+    return dbtk_pred_create_impl(device_id, ns, m.nk, m.ntr, m.nkc.data(), m.nikc.data(), m.nik, m.iki.data(), m.kc.data(), windowed, max_rows, out);
 }
 
 uint64_t dbtk_pred_nk(const dbtk_pred_t* p) { return p ? p->nk : 0; }
@@ -352,6 +552,10 @@ static dbtk_status_t dbtk_pred_load_samples_impl(dbtk_pred_t* p, uint64_t first_
     if (first_sample + n > p->ns || n > 0xFFFFFFFFull) { set_error("sample range outside the cohort"); return DBTK_ERR_ARG; }
     if (!n) return DBTK_OK;
     PCHK(hipSetDevice(p->device));
+    if (p->windowed) {
+        if (first_sample > p->ns || n > p->ns - first_sample) { set_error("sample range outside the cohort"); return DBTK_ERR_ARG; }
+        return pred_window_load_host(p, first_sample, n, counts, read_depth);
+    }
     if (n > p->stage_cap) {
         if (p->d_counts) PCHK(hipFree(p->d_counts));
         if (p->d_depth) PCHK(hipFree(p->d_depth));
@@ -407,6 +611,13 @@ dbtk_status_t dbtk_pred_load_device(dbtk_pred_t* p, uint64_t first_sample, uint6
         set_error("dbtk_pred_load_device: d_counts is not device memory of the handle's device");
         return DBTK_ERR_ARG;
     }
+    if (p->windowed) {  // the window's counts are staged (the fused pass reads all samples at once): one copy inside HBM
+        hipStream_t s = p->ws(p->cur);
+        if (p->w_rows) PCHK(hipMemcpyAsync(p->d_wc[p->cur] + first_sample * p->w_rows, d_counts, n * p->w_rows * 8, hipMemcpyDeviceToDevice, s));
+        PCHK(hipStreamSynchronize(s));  // (d_counts is no longer being read)
+        for (uint64_t i = 0; i < n; ++i) { p->h_depth[p->cur][first_sample + i] = read_depth[i]; p->dirty[first_sample + i] = 1; }
+        return DBTK_OK;
+    }
     const dbtk_status_t st = pred_load_device_async(p, first_sample, n, d_counts, read_depth);
     if (st) return st;
     PCHK(hipStreamSynchronize(p->stream));  // (d_counts is no longer being read)
@@ -415,6 +626,7 @@ dbtk_status_t dbtk_pred_load_device(dbtk_pred_t* p, uint64_t first_sample, uint6
 
 dbtk_status_t dbtk_pred_load_ctx(dbtk_pred_t* p, uint64_t sample, dbtk_ctx_t* ctx, float read_depth) {
     if (!p || !ctx) { set_error("null argument"); return DBTK_ERR_ARG; }
+    if (p->windowed) { set_error("dbtk_pred_load_ctx: a context holds one sample's whole count vector, a windowed handle takes a window's counts of every sample: use dbtk_pred_load_device"); return DBTK_ERR_ARG; }
     CtxFacts f;
     { const dbtk_status_t st = ctx_facts(ctx, &f); if (st) return st; }
     if (sample >= p->ns) { set_error("sample outside the cohort"); return DBTK_ERR_ARG; }
@@ -439,18 +651,25 @@ dbtk_status_t dbtk_pred_load_ctx(dbtk_pred_t* p, uint64_t sample, dbtk_ctx_t* ct
 dbtk_status_t dbtk_pred_correct(dbtk_pred_t* p) {
     if (!p) { set_error("null argument"); return DBTK_ERR_ARG; }
     PCHK(hipSetDevice(p->device));
-    hipStream_t s = p->stream;
-    PCHK(hipMemsetAsync(p->d_bias, 0, p->ntr * p->ns * sizeof(float), s));
+    // the loci and rows at work: everything, or the current window (whose Bias rows alone are made again)
+    const uint64_t t0 = p->windowed ? p->w_first : 0, nl = p->windowed ? p->w_end - p->w_first : p->ntr;
+    const uint64_t row0 = p->windowed ? p->w_row0 : 0, rows = p->windowed ? p->w_rows : p->nk;
+    hipStream_t s = p->ws(p->windowed ? p->cur : 0);
+    if (p->windowed) { const dbtk_status_t st = pred_window_materialize(p); if (st) return st; }
+    PCHK(hipMemsetAsync(p->d_bias + t0 * p->ns, 0, nl * p->ns * sizeof(float), s));
     PCHK(hipEventRecord(p->ev[0], s));
-    hipLaunchKernelGGL(k_pred_bias, dim3((uint32_t)p->ntr, (uint32_t)((p->ns + 63) / 64)), dim3(64), 0, s, p->d_G, p->d_nk, p->d_nik, p->d_iki, p->d_ikmc, p->d_bias, p->ns);
+    hipLaunchKernelGGL(k_pred_bias, dim3((uint32_t)nl, (uint32_t)((p->ns + 63) / 64)), dim3(64), 0, s, p->d_G, p->d_nk, p->d_nik, p->d_iki, p->d_ikmc, p->d_bias, p->ns,
+                       (uint32_t)t0, (uint32_t)row0);
     PCHK(hipGetLastError());
     PCHK(hipEventRecord(p->ev[1], s));
-    hipLaunchKernelGGL(k_pred_bias_norm, dim3((uint32_t)p->ntr), dim3(256), 0, s, p->d_nk, p->d_nik, p->d_bias, p->ns);
+    hipLaunchKernelGGL(k_pred_bias_norm, dim3((uint32_t)nl), dim3(256), 0, s, p->d_nk, p->d_nik, p->d_bias, p->ns, (uint32_t)t0);
     PCHK(hipGetLastError());
     PCHK(hipEventRecord(p->ev[2], s));
-    const uint64_t nb = (p->nk + 4 * PR_ROWS - 1) / (4 * PR_ROWS);
-    hipLaunchKernelGGL(k_pred_correct, dim3((uint32_t)nb), dim3(256), 0, s, p->d_G, p->d_loc, p->d_bias, p->nk, p->ns);
-    PCHK(hipGetLastError());
+    if (rows) {
+        const uint64_t nb = (rows + 4 * PR_ROWS - 1) / (4 * PR_ROWS);
+        hipLaunchKernelGGL(k_pred_correct, dim3((uint32_t)nb), dim3(256), 0, s, p->d_G, p->d_loc + row0, p->d_bias, rows, p->ns);
+        PCHK(hipGetLastError());
+    }
     PCHK(hipEventRecord(p->ev[3], s));
     PCHK(hipStreamSynchronize(s));
     for (int i = 0; i < 3; ++i) PCHK(hipEventElapsedTime(&p->ms[i], p->ev[i], p->ev[i + 1]));
@@ -460,7 +679,81 @@ dbtk_status_t dbtk_pred_correct(dbtk_pred_t* p) {
 dbtk_status_t dbtk_pred_matrix(dbtk_pred_t* p, float* out) {
     if (!p || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
     PCHK(hipSetDevice(p->device));
+    if (p->windowed) {
+        { const dbtk_status_t st = pred_window_materialize(p); if (st) return st; }
+        PCHK(hipStreamSynchronize(p->ws(p->cur)));
+        if (p->w_rows) PCHK(hipMemcpy(out, p->d_G, p->w_rows * p->ns * sizeof(float), hipMemcpyDeviceToHost));
+        return DBTK_OK;
+    }
     PCHK(hipMemcpy(out, p->d_G, p->nk * p->ns * sizeof(float), hipMemcpyDeviceToHost));
+    return DBTK_OK;
+}
+
+// ---- the calls of a windowed handle alone
+static dbtk_status_t need_windowed(const dbtk_pred_t* p, const char* who) {
+    if (!p) { set_error("null argument"); return DBTK_ERR_ARG; }
+    if (!p->windowed) { set_error(std::string(who) + ": not a windowed handle (dbtk_pred_create_windowed)"); return DBTK_ERR_ARG; }
+    return DBTK_OK;
+}
+dbtk_status_t dbtk_pred_window(dbtk_pred_t* p, uint64_t first_locus, uint64_t* end_locus, uint64_t* first_row, uint64_t* rows) {
+    { const dbtk_status_t st = need_windowed(p, "dbtk_pred_window"); if (st) return st; }
+    { const dbtk_status_t st = pred_open_window(p, first_locus); if (st) return st; }
+    if (end_locus) *end_locus = p->w_end;
+    if (first_row) *first_row = p->w_row0;
+    if (rows) *rows = p->w_rows;
+    return DBTK_OK;
+}
+uint64_t dbtk_pred_max_rows(const dbtk_pred_t* p) { return p && p->windowed ? p->max_rows : 0; }
+dbtk_status_t dbtk_pred_window_stage(dbtk_pred_t* p, uint64_t** buf, uint64_t* cap_samples) {
+    { const dbtk_status_t st = need_windowed(p, "dbtk_pred_window_stage"); if (st) return st; }
+    if (!buf || !cap_samples) { set_error("null argument"); return DBTK_ERR_ARG; }
+    *buf = p->h_stage; *cap_samples = PW_STAGE;
+    return DBTK_OK;
+}
+dbtk_status_t dbtk_pred_window_submit(dbtk_pred_t* p) {
+    { const dbtk_status_t st = need_windowed(p, "dbtk_pred_window_submit"); if (st) return st; }
+    if (p->pending >= 0) { set_error("dbtk_pred_window_submit: the outputs of the window submitted before have not been taken (dbtk_pred_window_outputs)"); return DBTK_ERR_ARG; }
+    PCHK(hipSetDevice(p->device));
+    const int c = p->cur;
+    hipStream_t s = p->ws(c);
+    const uint64_t ns = p->ns, rows = p->w_rows, nl = p->w_end - p->w_first;
+    PCHK(hipMemcpyAsync(p->d_wdepth[c], p->h_depth[c], ns * 4, hipMemcpyHostToDevice, s));
+    PCHK(hipMemsetAsync(p->d_bias + p->w_first * ns, 0, nl * ns * sizeof(float), s));
+    if (rows) {
+        const uint64_t kt = (rows + PT_K - 1) / PT_K;
+        if (kt > 0x7FFFFFFFull || nl > 0x7FFFFFFFull) { set_error("window too large for one launch"); return DBTK_ERR_ARG; }
+        hipLaunchKernelGGL(k_pred_wbias, dim3((uint32_t)nl, (uint32_t)((ns + WB_S - 1) / WB_S)), dim3(64), 0, s, p->d_wc[c], p->d_wdepth[c], p->d_nk, p->d_nik, p->d_iki, p->d_ikmc,
+                           p->d_bias, ns, rows, (uint32_t)p->w_first, (uint32_t)p->w_row0);
+        PCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_pred_bias_norm, dim3((uint32_t)nl), dim3(256), 0, s, p->d_nk, p->d_nik, p->d_bias, ns, (uint32_t)p->w_first);
+        PCHK(hipGetLastError());
+        const uint32_t gy = (uint32_t)std::min<uint64_t>((ns + PT_S - 1) / PT_S, 64);
+        hipLaunchKernelGGL(k_pred_wfused, dim3((uint32_t)kt, gy), dim3(64), 0, s, p->d_wc[c], p->d_wdepth[c], p->d_loc + p->w_row0, p->d_bias, p->d_raw, p->d_cor, rows, ns);
+        PCHK(hipGetLastError());
+        PCHK(hipMemcpyAsync(p->h_raw, p->d_raw, rows * ns * sizeof(float), hipMemcpyDeviceToHost, s));
+        PCHK(hipMemcpyAsync(p->h_cor, p->d_cor, rows * ns * sizeof(float), hipMemcpyDeviceToHost, s));
+    }
+    p->pending = c; p->pend_rows = rows;
+    return DBTK_OK;
+}
+dbtk_status_t dbtk_pred_window_outputs_pinned(dbtk_pred_t* p, const float** raw, const float** corrected, uint64_t* rows) {
+    { const dbtk_status_t st = need_windowed(p, "dbtk_pred_window_outputs"); if (st) return st; }
+    if (p->pending < 0) { const dbtk_status_t st = dbtk_pred_window_submit(p); if (st) return st; }
+    PCHK(hipSetDevice(p->device));
+    const int c = p->pending;
+    p->pending = -1;  // (whatever the wait says: a failed window is not waited for twice)
+    PCHK(hipStreamSynchronize(p->ws(c)));
+    if (raw) *raw = p->h_raw;
+    if (corrected) *corrected = p->h_cor;
+    if (rows) *rows = p->pend_rows;
+    return DBTK_OK;
+}
+dbtk_status_t dbtk_pred_window_outputs(dbtk_pred_t* p, float* raw_out, float* corrected_out) {
+    const float *r = nullptr, *c = nullptr;
+    uint64_t rows = 0;
+    { const dbtk_status_t st = dbtk_pred_window_outputs_pinned(p, &r, &c, &rows); if (st) return st; }
+    if (raw_out) memcpy(raw_out, r, rows * p->ns * sizeof(float));
+    if (corrected_out) memcpy(corrected_out, c, rows * p->ns * sizeof(float));
     return DBTK_OK;
 }
 dbtk_status_t dbtk_pred_bias(dbtk_pred_t* p, float* out) {
@@ -478,10 +771,17 @@ dbtk_status_t dbtk_pred_times(dbtk_pred_t* p, float ms[3]) {
 // ---- the entry points above that parse files or allocate host memory, behind the exception barrier (dbtk_internal.h: guarded)
 dbtk_status_t dbtk_pred_create(int device_id, uint64_t ns, uint64_t nk, uint64_t ntr, const uint32_t* nk_cum, const uint32_t* nik_cum,
                                uint64_t nik, const uint32_t* iki, const uint8_t* ikmc, dbtk_pred_t** out) {
-    return dbtk::guarded([&] { return dbtk_pred_create_impl(device_id, ns, nk, ntr, nk_cum, nik_cum, nik, iki, ikmc, out); });
+    return dbtk::guarded([&] { return dbtk_pred_create_impl(device_id, ns, nk, ntr, nk_cum, nik_cum, nik, iki, ikmc, false, 0, out); });
 }
 dbtk_status_t dbtk_pred_create_from_file(int device_id, uint64_t ns, const char* ikmer_meta, dbtk_pred_t** out) {
-    return dbtk::guarded([&] { return dbtk_pred_create_from_file_impl(device_id, ns, ikmer_meta, out); });
+    return dbtk::guarded([&] { return dbtk_pred_create_from_file_impl(device_id, ns, ikmer_meta, false, 0, out); });
+}
+dbtk_status_t dbtk_pred_create_windowed(int device_id, uint64_t ns, uint64_t nk, uint64_t ntr, const uint32_t* nk_cum, const uint32_t* nik_cum,
+                                        uint64_t nik, const uint32_t* iki, const uint8_t* ikmc, uint64_t max_rows, dbtk_pred_t** out) {
+    return dbtk::guarded([&] { return dbtk_pred_create_impl(device_id, ns, nk, ntr, nk_cum, nik_cum, nik, iki, ikmc, true, max_rows, out); });
+}
+dbtk_status_t dbtk_pred_create_windowed_from_file(int device_id, uint64_t ns, const char* ikmer_meta, uint64_t max_rows, dbtk_pred_t** out) {
+    return dbtk::guarded([&] { return dbtk_pred_create_from_file_impl(device_id, ns, ikmer_meta, true, max_rows, out); });
 }
 dbtk_status_t dbtk_pred_load_samples(dbtk_pred_t* p, uint64_t first_sample, uint64_t n, const uint64_t* counts, const float* read_depth) {
     return dbtk::guarded([&] { return dbtk_pred_load_samples_impl(p, first_sample, n, counts, read_depth); });
@@ -718,7 +1018,7 @@ dbtk_status_t dbtk_dosage_finish(dbtk_dosage_t* d) {
     hipStream_t s = d->stream;
     PCHK(hipEventRecord(d->ev[2], s));
     PCHK(hipMemcpyAsync(d->d_bias, d->d_raw, d->ntr * d->ns * sizeof(float), hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(k_pred_bias_norm, dim3((uint32_t)d->ntr), dim3(256), 0, s, d->d_nk, d->d_nik, d->d_bias, d->ns);
+    hipLaunchKernelGGL(k_pred_bias_norm, dim3((uint32_t)d->ntr), dim3(256), 0, s, d->d_nk, d->d_nik, d->d_bias, d->ns, 0u);
     PCHK(hipGetLastError());
     PCHK(hipEventRecord(d->ev[3], s));
     PCHK(hipStreamSynchronize(s));

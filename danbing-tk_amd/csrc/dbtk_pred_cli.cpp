@@ -3,10 +3,14 @@
 //   danbing-tk-pred <INPUT1: trkmc.ar files + read depths> <INPUT2: ikmer.meta> <OUTPUT1: raw matrix> <OUTPUT2: corrected> <OUTPUT3: bias.tsv>
 //   danbing-tk-pred --dosage <OUT.dosage.tsv> [--kms <OUT.kms>] <INPUT1> <INPUT2> <OUTPUT3: bias.tsv>
 // The second form makes the per-locus tables alone (dbtk_dosage_*): the matrix is never allocated, in HBM or on the host.
+//   danbing-tk-pred --window-rows R | --window-bytes N <INPUT1> <INPUT2> <OUTPUT1> <OUTPUT2> <OUTPUT3>
+// The first form for a cohort whose matrix fits neither: whole loci of at most R k-mers at a time (windowed()), the same three files.
+#include <fcntl.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <unistd.h>
 
 #include <fstream>
 #include <string>
@@ -82,6 +86,88 @@ static int dosage_tables(int device, const std::string& finGtMeta, const std::st
     return 0;
 }
 
+// --window-rows / --window-bytes: the two matrices one window of loci at a time.  Every window reads its slice of every sample's
+// count file (pread), sends it a few samples at a time through the handle's pinned staging buffer, and appends the window of the raw
+// and of the corrected matrix to the two files, whose headers were written first.  While window w computes and copies, the slices of
+// window w + 1 are read and sent.  Host memory: the handle's pinned buffers (one pair of output windows, four samples' slices).
+static int windowed(int device, const std::string& finGtMeta, const std::string& finIkMeta, const std::string& foutRaw, const std::string& fout,
+                    const std::string& foutBias, const std::vector<std::string>& fns, const std::vector<float>& rds, uint64_t max_rows) {
+    const uint64_t ns = fns.size();
+    dbtk_pred_t* P = nullptr;
+    if (dbtk_pred_create_windowed_from_file(device, ns, finIkMeta.c_str(), max_rows, &P)) die(dbtk_last_error());
+    const uint64_t nk = dbtk_pred_nk(P), ntr = dbtk_pred_ntr(P);
+    printf("%llu loci in total.\n", (unsigned long long)ntr);
+    printf("reading %llu gt files in windows of at most %llu k-mers\n", (unsigned long long)ns, (unsigned long long)dbtk_pred_max_rows(P));
+    for (uint64_t s = 0; s < ns; ++s) {  // load_eachBinGT's assertion, once per file and before anything is written
+        FILE* f = fopen(fns[s].c_str(), "rb");
+        if (!f) die("cannot open " + fns[s], 134);
+        uint64_t nkf = 0;
+        if (fread(&nkf, 8, 1, f) != 1 || nkf != nk) { fprintf(stderr, "nk %llu != nk_ %llu\n", (unsigned long long)nkf, (unsigned long long)nk); exit(134); }  // the reference asserts
+        fclose(f);
+    }
+    FILE* fo[2] = {fopen(foutRaw.c_str(), "wb"), fopen(fout.c_str(), "wb")};
+    const std::string* fon[2] = {&foutRaw, &fout};
+    for (int i = 0; i < 2; ++i) {
+        if (!fo[i]) die("cannot create " + *fon[i]);
+        const uint32_t r = (uint32_t)ns, c = (uint32_t)nk;  // save_matrix' header, with the full dimensions
+        if (fwrite(&r, 4, 1, fo[i]) != 1 || fwrite(&c, 4, 1, fo[i]) != 1) die("write error on " + *fon[i]);
+    }
+    uint64_t* stage = nullptr;
+    uint64_t B = 0;
+    if (dbtk_pred_window_stage(P, &stage, &B)) die(dbtk_last_error());
+    auto take = [&] {  // the submitted window's two pieces, appended
+        const float* out[2] = {nullptr, nullptr};
+        uint64_t rows = 0;
+        if (dbtk_pred_window_outputs_pinned(P, &out[0], &out[1], &rows)) die(dbtk_last_error());
+        for (int i = 0; i < 2; ++i) if (rows && fwrite(out[i], 4, rows * ns, fo[i]) != rows * ns) die("write error on " + *fon[i]);
+    };
+    uint64_t nwin = 0;
+    for (uint64_t first = 0, end = 0; first < ntr; first = end, ++nwin) {
+        uint64_t row0 = 0, rows = 0;
+        if (dbtk_pred_window(P, first, &end, &row0, &rows)) die(dbtk_last_error());
+        for (uint64_t s0 = 0; s0 < ns && rows; s0 += B) {
+            const uint64_t n = std::min<uint64_t>(B, ns - s0);
+            for (uint64_t i = 0; i < n; ++i) {
+                const std::string& fn = fns[s0 + i];
+                const int fd = open(fn.c_str(), O_RDONLY);
+                if (fd < 0) die("cannot open " + fn, 134);
+                char* dst = (char*)(stage + i * rows);
+                for (uint64_t got = 0; got < rows * 8;) {
+                    const ssize_t k = pread(fd, dst + got, rows * 8 - got, (off_t)(8 + row0 * 8 + got));
+                    if (k <= 0) die("truncated " + fn, 134);
+                    got += (uint64_t)k;
+                }
+                close(fd);
+            }
+            if (dbtk_pred_load_samples(P, s0, n, stage, rds.data() + s0)) die(dbtk_last_error());
+        }
+        if (nwin) take();  // (window nwin - 1: it ran while this one's slices were read and sent)
+        if (dbtk_pred_window_submit(P)) die(dbtk_last_error());
+    }
+    take();
+    printf("normalizaing read depth\ncomputing/correcting bias\n%llu windows\n", (unsigned long long)nwin);
+    for (int i = 0; i < 2; ++i) {
+        printf("saving matrix to %s\n", fon[i]->c_str());
+        if (fclose(fo[i])) die("write error on " + *fon[i]);
+        printf("matrix dim: (%llu,%llu) size: %llu bytes\n", (unsigned long long)ns, (unsigned long long)nk, (unsigned long long)(ns * nk * 4));
+    }
+    std::vector<float> bias(ns * ntr);
+    if (dbtk_pred_bias(P, bias.data())) die(dbtk_last_error());
+    std::string err;
+    if (!dbtk_pred_io::save_bias_tsv(foutBias, bias.data(), ns, ntr, stdout, &err)) die(err);
+    dbtk_pred_free(P);
+    return 0;
+}
+
+// a positive integer, all of the argument
+static uint64_t positive(const std::string& flag, const char* v) {
+    char* e = nullptr;
+    const unsigned long long x = strtoull(v, &e, 10);
+    if (!*v || *v == '-' || *e) die(flag + ": not a number: " + v);
+    if (!x) die(flag + " must be positive");
+    return x;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "\nUsage: danbing-tk-pred <INPUT1> <INPUT2> <OUTPUT1> <OUTPUT2> <OUTPUT3>\n"
@@ -97,16 +183,22 @@ int main(int argc, char** argv) {
                         "  --dosage <OUT.dosage.tsv> [--kms <OUT.kms>] <INPUT1> <INPUT2> <OUTPUT3>\n"
                         "                  per-locus tables only, without the two matrices: the bias-corrected dosage\n"
                         "                  (sum of the locus' k-mer counts / read depth / bias; uncorrected where the locus has\n"
-                        "                  no invariant k-mers) in the layout of OUTPUT3, and the plain sums as `ktools sum -f` writes them\n\n");
+                        "                  no invariant k-mers) in the layout of OUTPUT3, and the plain sums as `ktools sum -f` writes them\n"
+                        "  --window-rows <INT>   the two matrices one window of whole loci at a time, at most INT k-mers each: the same\n"
+                        "                  three files from O(window) of device and host memory (no locus may have more k-mers)\n"
+                        "  --window-bytes <INT>  the same, as the size of a window's device matrix: INT / (4 * samples) k-mers\n\n");
         return 0;
     }
     int argi = 1, device = 0;
     std::string foutDosage, foutKms;
+    uint64_t winRows = 0, winBytes = 0;
     while (argi < argc && argv[argi][0] == '-') {
         const std::string a = argv[argi];
         if (a == "--device" && argi + 1 < argc) { device = atoi(argv[argi + 1]); argi += 2; }
         else if (a == "--dosage" && argi + 1 < argc) { foutDosage = argv[argi + 1]; argi += 2; }
         else if (a == "--kms" && argi + 1 < argc) { foutKms = argv[argi + 1]; argi += 2; }
+        else if (a == "--window-rows" && argi + 1 < argc) { winRows = positive(a, argv[argi + 1]); argi += 2; }
+        else if (a == "--window-bytes" && argi + 1 < argc) { winBytes = positive(a, argv[argi + 1]); argi += 2; }
         else if (a == "-f" && argi + 1 < argc) argi += 2;  // developer flag of the reference (its body is commented out there): accepted, ignored
         else die("invalid option: " + a);
     }
@@ -124,6 +216,13 @@ int main(int argc, char** argv) {
     std::vector<float> rds;
     read_gt_meta(finGtMeta, &fns, &rds);
     const uint64_t ns = fns.size();
+    if (winRows || winBytes) {
+        const uint64_t fromBytes = winBytes / (4 * ns);
+        if (winBytes && !fromBytes) die("--window-bytes " + std::to_string(winBytes) + " holds no k-mer of " + std::to_string(ns) + " samples");
+        if (winRows && winBytes && winRows != fromBytes)
+            die("--window-rows " + std::to_string(winRows) + " and --window-bytes " + std::to_string(winBytes) + " (" + std::to_string(fromBytes) + " k-mers of " + std::to_string(ns) + " samples) disagree");
+        return windowed(device, finGtMeta, finIkMeta, foutRaw, fout, foutBias, fns, rds, winRows ? winRows : fromBytes);
+    }
     dbtk_pred_t* P = nullptr;
     if (dbtk_pred_create_from_file(device, ns, finIkMeta.c_str(), &P)) die(dbtk_last_error());
     const uint64_t nk = dbtk_pred_nk(P), ntr = dbtk_pred_ntr(P);

@@ -82,6 +82,60 @@ dbtk_status_t dbtk_pred_bias(dbtk_pred_t* p, float* out);
 /* Kernel times of the last dbtk_pred_correct in milliseconds: bias sums, bias normalisation, the correcting pass. */
 dbtk_status_t dbtk_pred_times(dbtk_pred_t* p, float ms[3]);
 
+/* ---- Windows: matrices larger than HBM or the host (added within ABI v11; the version number did not move).
+ *
+ * bias_correction is independent per locus: the bias of a locus reads that locus' invariant k-mers and divides that locus' columns.
+ * A windowed handle therefore holds a run of whole loci at a time — at most max_rows k-mer columns — and makes the same bits as the
+ * whole-matrix handle, window after window.  save_matrix writes nk runs of ns floats, so a window is one contiguous piece of each
+ * output file.
+ *
+ * dbtk_pred_create_windowed is dbtk_pred_create with G[max_rows][ns] instead of G[nk][ns] (max_rows above nk is taken as nk); Bias
+ * [ntr][ns] and the metadata stay whole.  Beside G the handle holds two buffers of staged counts (8 * max_rows * ns bytes each) and
+ * one pair of output windows (2 * 4 * max_rows * ns), 28 * max_rows * ns bytes of HBM in all, and pinned host memory for one pair of
+ * output windows and PW = 4 samples' counts: (8 * ns + 32) * max_rows bytes.  Everything is sized by this call and never again.
+ * DBTK_ERR_ARG when a locus has more than max_rows k-mers (the message names the locus and its size) or max_rows is 0;
+ * DBTK_ERR_FORMAT when an invariant k-mer lies outside its locus (no ikmer.meta has that; a window could not hold what the bias
+ * reads); DBTK_ERR_NOMEM as dbtk_pred_create.  K-mers past nk_cum[ntr - 1] (they belong to no locus) travel with the last locus.
+ * The new handle's current window is the one that starts at locus 0. */
+dbtk_status_t dbtk_pred_create_windowed(int device_id, uint64_t ns, uint64_t nk, uint64_t ntr, const uint32_t* nk_cum, const uint32_t* nik_cum,
+                                        uint64_t nik, const uint32_t* iki, const uint8_t* ikmc, uint64_t max_rows, dbtk_pred_t** out);
+dbtk_status_t dbtk_pred_create_windowed_from_file(int device_id, uint64_t ns, const char* ikmer_meta, uint64_t max_rows, dbtk_pred_t** out);
+/* max_rows of a windowed handle as it was taken; 0 for a handle of dbtk_pred_create. */
+uint64_t dbtk_pred_max_rows(const dbtk_pred_t* p);
+
+/* The current window becomes the longest run of loci [first_locus, *end_locus) whose k-mers fit into max_rows.  Loci without k-mers
+ * cost nothing; a run of them at the end of the window belongs to it.  *first_row = the window's first k-mer column, *rows = their
+ * number (0: only empty loci).  The window's part of G, its staged counts and its depths (1.0) are reset: a sample that is not
+ * loaded into the window reads as all-zero counts, like the zeroed column of a new whole-matrix handle.  Bias rows of other windows
+ * are kept.  The window takes the buffer that holds no submitted window (dbtk_pred_window_submit), so the loads of window w + 1 run
+ * beside the kernels and the copies of window w.  DBTK_ERR_ARG for first_locus >= ntr and for a handle of dbtk_pred_create.
+ *
+ * On a windowed handle
+ *   dbtk_pred_load_samples / _load_device  take the window's counts only: counts[i * rows + r] = count of k-mer first_row + r in sample
+ *                            first_sample + i.  A refused call leaves the window unchanged; any order of samples; loaded twice: the later
+ *                            load wins.  The counts are staged in HBM (the fused pass needs all samples of a window at once).
+ *   dbtk_pred_load_ctx       is refused (DBTK_ERR_ARG): a context holds one sample's whole vector.
+ *   dbtk_pred_matrix         returns ns x rows floats, the save_matrix layout of the window's rows.
+ *   dbtk_pred_correct        corrects the window's loci in G and fills their Bias rows.
+ *   dbtk_pred_bias           returns the whole ns x ntr table; loci that no window has visited are 0.
+ * These separate calls give the same bits as the fused pass below; they make G from the staged counts when first asked. */
+dbtk_status_t dbtk_pred_window(dbtk_pred_t* p, uint64_t first_locus, uint64_t* end_locus, uint64_t* first_row, uint64_t* rows);
+
+/* The fused pass over the current window: the raw bias sums straight from the staged counts, the normalisation kernel of
+ * dbtk_pred_correct, then ONE kernel that reads the counts once and writes the window of the raw matrix and the window of the
+ * corrected matrix; G is neither written nor read.  Fills the window's Bias rows.
+ * dbtk_pred_window_submit starts it on the window's stream, the copies to pinned host memory included, and returns at once: the next
+ * dbtk_pred_window and its loads may follow while it runs.  One window can be submitted at a time (DBTK_ERR_ARG otherwise).
+ * dbtk_pred_window_outputs waits for the submitted window — or, when none is, submits the current one — and copies its outputs:
+ * rows * ns floats each, in the layout of dbtk_pred_matrix (either pointer may be NULL).  dbtk_pred_window_outputs_pinned hands out the
+ * pinned buffers themselves instead (valid until the next submit), with the window's rows. */
+dbtk_status_t dbtk_pred_window_submit(dbtk_pred_t* p);
+dbtk_status_t dbtk_pred_window_outputs(dbtk_pred_t* p, float* raw_out, float* corrected_out);
+dbtk_status_t dbtk_pred_window_outputs_pinned(dbtk_pred_t* p, const float** raw, const float** corrected, uint64_t* rows);
+/* The handle's pinned staging buffer: room for *cap_samples samples' counts of a window.  Counts that dbtk_pred_load_samples is given
+ * at this address are sent as they lie (no copy through the staging buffer). */
+dbtk_status_t dbtk_pred_window_stage(dbtk_pred_t* p, uint64_t** buf, uint64_t* cap_samples);
+
 /* ---- Per-locus dosage tables without the matrix (ABI v10).
  *
  * What most users take from the matrix is one number per sample and locus: "the sum of k-mer counts normalised to VNTR dosage"
