@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -25,31 +26,47 @@ using namespace dbtk;
         }                                                                                             \
     } while (0)
 
+// ---- locus t of ikmer.meta: its k-mers [si, ei) and its invariant k-mers [isi, iei).  bias_correction leaves a locus that lacks
+// either alone (pred.h:219-220): its Bias row stays 0, its columns are not divided.
+struct LocusSpan {
+    uint32_t si, ei, isi, iei;
+    __host__ __device__ bool skipped() const { return si == ei || isi == iei; }
+};
+__host__ __device__ __forceinline__ LocusSpan locus_span(const uint32_t* __restrict__ nk_cum, const uint32_t* __restrict__ nik_cum, uint64_t t) {
+    return LocusSpan{t ? nk_cum[t - 1] : 0u, nk_cum[t], t ? nik_cum[t - 1] : 0u, nik_cum[t]};
+}
+
 // ---- load_eachBinGT + norm_rd (pred.h:166-186, 204-209): counts[i][k] (u64, sample-major as the files are) ->
-// G[k][first + i] = (float)count / depth[i].  One wave per tile of 64 k-mers x 32 samples: the counts are read along k
-// (coalesced), turned in LDS, and written along the samples (runs of 128 bytes).
+// (float)count / depth[i], handed to store(k, i, value).  One wave per tile of 64 k-mers x 32 samples: the counts are read along k
+// (coalesced), turned in LDS, and stored along the samples (runs of 128 bytes); the blocks of a column of the grid stride over the
+// samples.  N: the width of the sample index (n samples, of `rows` counts each).
 constexpr int PT_K = 64, PT_S = 32;
-__global__ void __launch_bounds__(64) k_pred_load(const uint64_t* __restrict__ counts, const float* __restrict__ depth, float* __restrict__ G,
-                                                  uint64_t nk, uint64_t ns, uint64_t first, uint32_t n) {
+template <class N, class Store>
+__device__ __forceinline__ void pred_tile(const uint64_t* __restrict__ counts, const float* __restrict__ depth, uint64_t rows, N n, Store store) {
     __shared__ float tile[PT_K][PT_S + 1];
     const int lane = threadIdx.x;
     const uint64_t k0 = (uint64_t)blockIdx.x * PT_K;
-    for (uint32_t i0 = blockIdx.y * PT_S; i0 < n; i0 += gridDim.y * PT_S) {
-        const uint32_t ni = n - i0 < (uint32_t)PT_S ? n - i0 : (uint32_t)PT_S;
+    for (N i0 = (N)blockIdx.y * PT_S; i0 < n; i0 += (N)gridDim.y * PT_S) {
+        const uint32_t ni = n - i0 < (N)PT_S ? (uint32_t)(n - i0) : (uint32_t)PT_S;
         for (uint32_t i = 0; i < ni; ++i) {
             const uint64_t k = k0 + lane;
             // uint64 -> float and the division are each one correctly rounded IEEE operation, as Eigen's cast<float>() and operator/
-            tile[lane][i] = k < nk ? (float)counts[(uint64_t)(i0 + i) * nk + k] / depth[i0 + i] : 0.f;
+            tile[lane][i] = k < rows ? (float)counts[(uint64_t)(i0 + i) * rows + k] / depth[i0 + i] : 0.f;
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
         for (int r = lane / PT_S; r < PT_K; r += 64 / PT_S) {  // two rows per pass: lanes 0-31 / 32-63 along the samples
             const uint32_t i = lane % PT_S;
-            if (k0 + r < nk && i < ni) G[(k0 + r) * ns + first + i0 + i] = tile[r][i];
+            if (k0 + r < rows && i < ni) store(k0 + r, i0 + i, tile[r][i]);
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
+}
+// n samples from `first` on into the matrix: G[k][first + i]
+__global__ void __launch_bounds__(64) k_pred_load(const uint64_t* __restrict__ counts, const float* __restrict__ depth, float* __restrict__ G,
+                                                  uint64_t nk, uint64_t ns, uint64_t first, uint32_t n) {
+    pred_tile(counts, depth, nk, n, [=](uint64_t k, uint32_t i, float g) { G[k * ns + first + i] = g; });
 }
 
 // ---- one sample whose counts are already in HBM (dbtk_pred_load_ctx / dbtk_pred_load_device with n = 1): column `sample` of G.
@@ -70,19 +87,18 @@ __global__ void __launch_bounds__(64) k_pred_bias(const float* __restrict__ G, c
                                                   uint32_t tri0, uint32_t row0) {
     const uint32_t tri = tri0 + blockIdx.x;
     const uint64_t s = (uint64_t)blockIdx.y * 64 + threadIdx.x;
-    const uint32_t si = tri ? nk_cum[tri - 1] : 0u, ei = nk_cum[tri], isi = tri ? nik_cum[tri - 1] : 0u, iei = nik_cum[tri];
-    if (si == ei || isi == iei || s >= ns) return;
+    const LocusSpan L = locus_span(nk_cum, nik_cum, tri);
+    if (L.skipped() || s >= ns) return;
     float acc = 0.f;
-    for (uint32_t j = isi; j < iei; ++j) acc += G[(uint64_t)(iki[j] - row0) * ns + s] / ikmc[j];
-    bias[(uint64_t)tri * ns + s] = acc / (float)(iei - isi);
+    for (uint32_t j = L.isi; j < L.iei; ++j) acc += G[(uint64_t)(iki[j] - row0) * ns + s] / ikmc[j];
+    bias[(uint64_t)tri * ns + s] = acc / (float)(L.iei - L.isi);
 }
 // second half (pred.h:229-231): bias /= bias.mean() over the samples.  One block per locus; the mean is a pairwise tree.
 __global__ void __launch_bounds__(256) k_pred_bias_norm(const uint32_t* __restrict__ nk_cum, const uint32_t* __restrict__ nik_cum, float* __restrict__ bias, uint64_t ns,
                                                         uint32_t tri0) {
     __shared__ float part[256];
     const uint32_t tri = tri0 + blockIdx.x;
-    const uint32_t si = tri ? nk_cum[tri - 1] : 0u, ei = nk_cum[tri], isi = tri ? nik_cum[tri - 1] : 0u, iei = nik_cum[tri];
-    if (si == ei || isi == iei) return;
+    if (locus_span(nk_cum, nik_cum, tri).skipped()) return;
     float* b = bias + (uint64_t)tri * ns;
     float acc = 0.f;
     for (uint64_t s = threadIdx.x; s < ns; s += 256) acc += b[s];
@@ -137,8 +153,9 @@ __global__ void __launch_bounds__(64) k_pred_wbias(const uint64_t* __restrict__ 
     const uint32_t lane = threadIdx.x;
     const uint32_t tri = tri0 + blockIdx.x;
     const uint64_t s0 = (uint64_t)blockIdx.y * WB_S;
-    const uint32_t si = tri ? nk_cum[tri - 1] : 0u, ei = nk_cum[tri], isi = tri ? nik_cum[tri - 1] : 0u, iei = nik_cum[tri];
-    if (si == ei || isi == iei || s0 >= ns) return;  // (uniform in the wave)
+    const LocusSpan L = locus_span(nk_cum, nik_cum, tri);
+    if (L.skipped() || s0 >= ns) return;  // (uniform in the wave)
+    const uint32_t isi = L.isi, iei = L.iei;
     const uint32_t nsl = ns - s0 < (uint64_t)WB_S ? (uint32_t)(ns - s0) : (uint32_t)WB_S;
     float acc = 0.f;
     for (uint32_t j0 = isi; j0 < iei; j0 += WB_J) {
@@ -156,36 +173,18 @@ __global__ void __launch_bounds__(64) k_pred_wbias(const uint64_t* __restrict__ 
     }
     if (lane < nsl) bias[(uint64_t)tri * ns + s0 + lane] = acc / (float)(iei - isi);
 }
-// Both matrices of the window from one pass over its counts: k_pred_load's tile (64 k-mers x 32 samples, read along k, turned in LDS,
-// written along the samples), and where it stores G the raw value goes to raw[r][s] and raw / Bias(locus of r, s) to cor[r][s] — the
-// division of k_pred_correct on the value k_pred_load would have stored.  A row of no corrected locus (loc = NOLOC) is copied.
-// loc = d_loc + row0 (the window's rows), bias the whole [ntr][ns] table after k_pred_bias_norm.
+// Both matrices of the window from one pass over its counts: k_pred_load's tile, and where that stores G the raw value goes to
+// raw[r][s] and raw / Bias(locus of r, s) to cor[r][s] — the division of k_pred_correct on the value k_pred_load would have stored.
+// A row of no corrected locus (loc = NOLOC) is copied.  loc = d_loc + row0 (the window's rows), bias the whole [ntr][ns] table after
+// k_pred_bias_norm.
 __global__ void __launch_bounds__(64) k_pred_wfused(const uint64_t* __restrict__ wc, const float* __restrict__ depth, const uint32_t* __restrict__ loc,
                                                     const float* __restrict__ bias, float* __restrict__ raw, float* __restrict__ cor, uint64_t rows, uint64_t ns) {
-    __shared__ float tile[PT_K][PT_S + 1];
-    const int lane = threadIdx.x;
-    const uint64_t k0 = (uint64_t)blockIdx.x * PT_K;
-    for (uint64_t i0 = (uint64_t)blockIdx.y * PT_S; i0 < ns; i0 += (uint64_t)gridDim.y * PT_S) {
-        const uint32_t ni = ns - i0 < (uint64_t)PT_S ? (uint32_t)(ns - i0) : (uint32_t)PT_S;
-        for (uint32_t i = 0; i < ni; ++i) {
-            const uint64_t k = k0 + lane;
-            tile[lane][i] = k < rows ? (float)wc[(i0 + i) * rows + k] / depth[i0 + i] : 0.f;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (int r = lane / PT_S; r < PT_K; r += 64 / PT_S) {
-            const uint32_t i = lane % PT_S;
-            if (k0 + r < rows && i < ni) {
-                const uint32_t tri = loc[k0 + r];
-                const float g = tile[r][i];
-                const uint64_t at = (k0 + r) * ns + i0 + i;
-                raw[at] = g;
-                cor[at] = tri != NOLOC ? g / bias[(uint64_t)tri * ns + i0 + i] : g;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
+    pred_tile(wc, depth, rows, ns, [=](uint64_t r, uint64_t s, float g) {
+        const uint32_t tri = loc[r];
+        const uint64_t at = r * ns + s;
+        raw[at] = g;
+        cor[at] = tri != NOLOC ? g / bias[(uint64_t)tri * ns + s] : g;
+    });
 }
 
 // ---- the dosage tables (dbtk_pred.h, ABI v10): one sample's counts -> its kms and raw-bias entries, locus by locus, in one pass.
@@ -249,7 +248,8 @@ __global__ void __launch_bounds__(DS_T) k_dosage_sample(const uint64_t* __restri
     }
     for (uint32_t j = tid; j < it.nl; j += DS_T) {
         const uint32_t l = it.l0 + j;
-        const uint32_t b = (l ? nk_cum[l - 1] : 0u) - it.k0, e = nk_cum[l] - it.k0;
+        const LocusSpan L = locus_span(nk_cum, nik_cum, l);
+        const uint32_t b = L.si - it.k0, e = L.ei - it.k0;
         kms[(uint64_t)l * ns + sample] = (e ? P[ds_pad(e - 1)] : 0ull) - (b ? P[ds_pad(b - 1)] : 0ull);
     }
     if (it.part != NOPART && tid == 0) part[it.part] = it.nkm ? P[ds_pad(it.nkm - 1)] : 0ull;
@@ -258,8 +258,9 @@ __global__ void __launch_bounds__(DS_T) k_dosage_sample(const uint64_t* __restri
         const uint32_t J0 = gl0 ? nik_cum[gl0 - 1] : 0u, J1 = nik_cum[gl0 + gn - 1];
         const bool on = tid < gn;
         const uint32_t l = gl0 + (on ? tid : 0u);
-        const uint32_t isi = l ? nik_cum[l - 1] : 0u, iei = on ? nik_cum[l] : isi;
-        const bool empty = (l ? nk_cum[l - 1] : 0u) == nk_cum[l];
+        const LocusSpan L = locus_span(nk_cum, nik_cum, l);
+        const uint32_t isi = L.isi, iei = on ? L.iei : isi;
+        const bool empty = L.si == L.ei;
         float acc = 0.f;
         for (uint32_t jt = J0; jt < J1; jt += DS_TB) {
             const uint32_t nt = J1 - jt < (uint32_t)DS_TB ? J1 - jt : (uint32_t)DS_TB;
@@ -287,10 +288,10 @@ __global__ void __launch_bounds__(256) k_dosage_values(const uint64_t* __restric
     const uint32_t tri = blockIdx.x;
     const uint64_t s = (uint64_t)blockIdx.y * 256 + threadIdx.x;
     if (s >= ns) return;
-    const uint32_t si = tri ? nk_cum[tri - 1] : 0u, ei = nk_cum[tri], isi = tri ? nik_cum[tri - 1] : 0u, iei = nik_cum[tri];
+    const LocusSpan L = locus_span(nk_cum, nik_cum, tri);
     const uint64_t at = (uint64_t)tri * ns + s;
     const float v = (float)kms[at] / depth[s];
-    out[at] = si == ei ? 0.f : (isi == iei ? v : v / bias[at]);
+    out[at] = L.si == L.ei ? 0.f : (L.isi == L.iei ? v : v / bias[at]);
 }
 
 // what both handles ask of their metadata arguments and of the device, before anything is allocated; leaves the device current
@@ -300,8 +301,8 @@ static dbtk_status_t check_ikmer_meta(int device_id, uint64_t ns, uint64_t nk, u
     if (!ns || !nk || !ntr) { set_error("empty cohort / RPGG"); return DBTK_ERR_ARG; }
     if (nk > 0xFFFFFFFFull || ntr > 0xFFFFFFFFull) { set_error("ikmer.meta holds 32-bit k-mer indices"); return DBTK_ERR_ARG; }
     for (uint64_t t = 0; t < ntr; ++t) {
-        const uint32_t a = t ? nk_cum[t - 1] : 0u, b = nk_cum[t], c = t ? nik_cum[t - 1] : 0u, d = nik_cum[t];
-        if (b < a || b > nk || d < c || d > nik) { set_error("ikmer.meta: the cumulative counts must not decrease or pass the totals"); return DBTK_ERR_FORMAT; }
+        const LocusSpan L = locus_span(nk_cum, nik_cum, t);
+        if (L.ei < L.si || L.ei > nk || L.iei < L.isi || L.iei > nik) { set_error("ikmer.meta: the cumulative counts must not decrease or pass the totals"); return DBTK_ERR_FORMAT; }
     }
     for (uint64_t j = 0; j < nik; ++j) if (iki[j] >= nk) { set_error("ikmer.meta: invariant k-mer index out of range"); return DBTK_ERR_FORMAT; }
     int ndev = 0;
@@ -333,24 +334,120 @@ static dbtk_status_t read_ikmer_meta(const char* ikmer_meta, IkmerMeta* m) {
     return st;
 }
 
+// ---- what the two handles share
+// the steps of a handle's creation.  Once one has failed the rest are skipped (STEP), so st and dbtk_last_error() keep the first
+// failure; what was allocated is remembered, and the handle's free releases it however far the creation came.
+struct Setup {
+    dbtk_status_t st = DBTK_OK;
+    std::vector<void*> dev, pinned;  // of hipMalloc / hipHostMalloc
+    Setup() { dev.reserve(16); pinned.reserve(8); }  // (more than either handle allocates: taking one in never throws)
+    // oom: what does not fit, for DBTK_ERR_NOMEM and the state of the HBM instead of the plain error when the device is out of memory
+    bool ok(hipError_t e, const char* what, const std::string* oom = nullptr) {
+        if (e == hipSuccess) return true;
+        if (e == hipErrorOutOfMemory && oom) {
+            (void)hipGetLastError();
+            size_t fr = 0, tot = 0;
+            (void)hipMemGetInfo(&fr, &tot);
+            set_error(*oom + " do not fit, " + std::to_string(fr) + " of " + std::to_string(tot) + " bytes of HBM are free");
+            st = DBTK_ERR_NOMEM;
+        } else { set_error(std::string(what) + ": " + hipGetErrorString(e)); st = DBTK_ERR_HIP; }
+        return false;
+    }
+    template <class T> void device(T** p, uint64_t bytes, const char* what = "hipMalloc", const std::string* oom = nullptr) {
+        if (!st && ok(hipMalloc(p, bytes), what, oom)) dev.push_back(*p);
+    }
+    template <class T> void host(T** p, uint64_t bytes, const char* what, const std::string* oom) {
+        if (!st && ok(hipHostMalloc(p, bytes), what, oom)) pinned.push_back(*p);
+    }
+    void upload(void* dst, const void* src, uint64_t bytes, hipStream_t s) {
+        if (!st && bytes) ok(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s), "hipMemcpy");
+    }
+    void release() { for (void* q : dev) (void)hipFree(q); for (void* q : pinned) (void)hipHostFree(q); }
+};
+#define STEP(m, call, ...) do { if (!(m).st) (m).ok((call), __VA_ARGS__); } while (0)
+
+// ikmer.meta's four arrays in HBM, as the kernels read them (iki and ikmc padded by one entry: never empty)
+struct IkmerDev {
+    uint32_t *nk = nullptr, *nik = nullptr, *iki = nullptr;
+    float* ikmc = nullptr;  // the expected counts as floats: what the bias sums divide by
+};
+static void ikmer_upload(Setup& m, IkmerDev* d, uint64_t ntr, const uint32_t* nk_cum, const uint32_t* nik_cum, uint64_t nik, const uint32_t* iki,
+                         const uint8_t* ikmc, hipStream_t s, const char* what = "hipMalloc", const std::string* oom = nullptr) {
+    std::vector<float> kc(nik);
+    for (uint64_t j = 0; j < nik; ++j) kc[j] = (float)ikmc[j];
+    m.device(&d->nk, ntr * 4, what, oom);
+    m.device(&d->nik, ntr * 4, what, oom);
+    m.device(&d->iki, (nik + 1) * 4, what, oom);
+    m.device(&d->ikmc, (nik + 1) * 4, what, oom);
+    m.upload(d->nk, nk_cum, ntr * 4, s);
+    m.upload(d->nik, nik_cum, ntr * 4, s);
+    m.upload(d->iki, iki, nik * 4, s);
+    m.upload(d->ikmc, kc.data(), nik * 4, s);
+    STEP(m, hipStreamSynchronize(s), "hipStreamSynchronize");  // (kc ends here)
+}
+
+static dbtk_status_t check_sample_range(uint64_t first, uint64_t n, uint64_t ns) {
+    if (first > ns || n > ns - first || n > 0xFFFFFFFFull) { set_error("sample range outside the cohort"); return DBTK_ERR_ARG; }
+    return DBTK_OK;
+}
+static dbtk_status_t check_device_counts(const void* d_counts, int device, const char* who) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, d_counts) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device) {
+        (void)hipGetLastError();
+        set_error(std::string(who) + ": d_counts is not device memory of the handle's device");
+        return DBTK_ERR_ARG;
+    }
+    return DBTK_OK;
+}
+// a context's accumulated counts as one sample's count vector in HBM (*base): the context is of the handle's RPGG build (nk k-mers)
+// and device, has nothing unflushed, every batch of it is done, its counter replicas are folded, and a pending sticky error word is
+// reported instead of tainted counts.  whose[0]: who holds the nk ("ikmer.meta has"), whose[1]: what lives on the device ("the matrix").
+static dbtk_status_t ctx_counts_ready(dbtk_ctx_t* ctx, int device, uint64_t nk, const char* const whose[2], const uint64_t** base) {
+    CtxFacts f;
+    { const dbtk_status_t st = ctx_facts(ctx, &f); if (st) return st; }  // (fails on a null context alone: refused by the callers)
+    if (f.ntrkmers != nk) { set_error("the context counts " + std::to_string(f.ntrkmers) + " TR k-mers, " + whose[0] + " " + std::to_string(nk) + ": not the same RPGG build"); return DBTK_ERR_ARG; }
+    if (f.device != device) { set_error("the context is on device " + std::to_string(f.device) + ", " + whose[1] + " on device " + std::to_string(device)); return DBTK_ERR_ARG; }
+    if (f.unflushed_pairs) { set_error(std::to_string(f.unflushed_pairs) + " pairs appended by dbtk_ingest_align_merged are not aligned yet: flush them first (slot = ~0u, flush = 1)"); return DBTK_ERR_ARG; }
+    { const dbtk_status_t st = dbtk_ctx_synchronize(ctx); if (st) return st; }
+    void* b = nullptr; uint64_t n64 = 0;
+    { const dbtk_status_t st = dbtk_ctx_accum_buffer(ctx, &b, &n64); if (st) return st; }
+    if (!b || n64 < nk) { set_error("the context has no accumulators"); return DBTK_ERR_ARG; }
+    PCHK(hipSetDevice(device));
+    *base = (const uint64_t*)b;
+    return DBTK_OK;
+}
+// one launch of a tile kernel (pred_tile) over rows x n: a block per PT_K k-mers, at most 64 blocks striding the samples
+template <class... P, class... A>
+static dbtk_status_t launch_tile(void (*kernel)(P...), hipStream_t s, uint64_t rows, uint64_t n, A... args) {
+    const uint64_t kt = (rows + PT_K - 1) / PT_K;
+    if (kt > 0x7FFFFFFFull) { set_error("too many k-mers for one launch"); return DBTK_ERR_ARG; }
+    const uint32_t gy = (uint32_t)std::min<uint64_t>((n + PT_S - 1) / PT_S, 64);
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)kt, gy), dim3(64), 0, s, args...);
+    PCHK(hipGetLastError());
+    return DBTK_OK;
+}
+
 struct dbtk_pred {
     int device = 0;
     uint64_t ns = 0, nk = 0, ntr = 0, nik = 0;
     float* d_G = nullptr;
     float* d_bias = nullptr;
-    uint32_t *d_nk = nullptr, *d_nik = nullptr, *d_iki = nullptr, *d_loc = nullptr;  // d_loc[k]: locus of k-mer k, NOLOC where bias_correction skips it
-    float* d_ikmc = nullptr;
+    IkmerDev meta;
+    uint32_t* d_loc = nullptr;  // d_loc[k]: locus of k-mer k, NOLOC where bias_correction skips it
+    Setup mem;                  // the creation's allocations (the three below it are regrown by the loads)
     uint64_t* d_counts = nullptr; float* d_depth = nullptr; uint64_t stage_cap = 0;  // staging of dbtk_pred_load_samples
     float* d_depth2 = nullptr; uint64_t depth_cap = 0;                                 // the depths of dbtk_pred_load_device
     hipStream_t stream = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     float ms[3] = {0, 0, 0};
-    // ---- a windowed handle (dbtk_pred_create_windowed): d_G holds max_rows x ns floats, the rows of the current window
+    // the rows of d_G, the current window: loci [w_first, w_end), k-mers [w_row0, w_row0 + w_rows); on its stream ws(cur).  A handle of
+    // dbtk_pred_create has one window for good: everything, on `stream`
+    uint64_t w_first = 0, w_end = 0, w_row0 = 0, w_rows = 0;
+    int cur = 0;                                     // a windowed handle's buffer of the window: d_wc[cur]
+    // ---- a windowed handle (dbtk_pred_create_windowed): d_G holds max_rows x ns floats
     bool windowed = false;
     uint64_t max_rows = 0;
     std::vector<uint32_t> nkc;                       // host copy of nk_cum: the window planning
-    uint64_t w_first = 0, w_end = 0, w_row0 = 0, w_rows = 0;  // the current window: loci [w_first, w_end), k-mers [w_row0, w_row0 + w_rows)
-    int cur = 0;                                     // its buffer: d_wc[cur], ws[cur]
     uint64_t* d_wc[2] = {nullptr, nullptr};          // the window's staged counts, [ns][w_rows] u64 (sample-major like the files)
     float* d_wdepth[2] = {nullptr, nullptr};         // [ns]
     float* h_depth[2] = {nullptr, nullptr};          // pinned [ns]: 1 until the sample is loaded into the window
@@ -396,10 +493,8 @@ static dbtk_status_t pred_window_materialize(dbtk_pred* p) {
         while (b < ns && p->dirty[b]) p->dirty[b++] = 0;
         if (rows) {
             if (!sent) { PCHK(hipMemcpyAsync(p->d_wdepth[p->cur], p->h_depth[p->cur], ns * 4, hipMemcpyHostToDevice, s)); sent = true; }
-            const uint64_t kt = (rows + PT_K - 1) / PT_K, n = b - a;
-            const uint32_t gy = (uint32_t)std::min<uint64_t>((n + PT_S - 1) / PT_S, 64);
-            hipLaunchKernelGGL(k_pred_load, dim3((uint32_t)kt, gy), dim3(64), 0, s, p->d_wc[p->cur] + a * rows, p->d_wdepth[p->cur] + a, p->d_G, rows, ns, a, (uint32_t)n);
-            PCHK(hipGetLastError());
+            const dbtk_status_t st = launch_tile(k_pred_load, s, rows, b - a, p->d_wc[p->cur] + a * rows, p->d_wdepth[p->cur] + a, p->d_G, rows, ns, a, (uint32_t)(b - a));
+            if (st) return st;
         }
         a = b;
     }
@@ -440,83 +535,57 @@ static dbtk_status_t dbtk_pred_create_impl(int device_id, uint64_t ns, uint64_t 
         }
         // a window holds whole loci and nothing else: the bias of a locus may read that locus' columns only (as every ikmer.meta has it)
         for (uint64_t t = 0; t < ntr; ++t) {
-            const uint32_t a = t ? nk_cum[t - 1] : 0u, b = nk_cum[t];
-            for (uint32_t j = t ? nik_cum[t - 1] : 0u; j < nik_cum[t]; ++j)
-                if (iki[j] < a || iki[j] >= b) { set_error("ikmer.meta: invariant k-mer " + std::to_string(j) + " lies outside its locus " + std::to_string(t) + ": no windows over this build"); return DBTK_ERR_FORMAT; }
+            const LocusSpan L = locus_span(nk_cum, nik_cum, t);
+            for (uint32_t j = L.isi; j < L.iei; ++j)
+                if (iki[j] < L.si || iki[j] >= L.ei) { set_error("ikmer.meta: invariant k-mer " + std::to_string(j) + " lies outside its locus " + std::to_string(t) + ": no windows over this build"); return DBTK_ERR_FORMAT; }
         }
     }
     const uint64_t grows = windowed ? max_rows : nk;  // rows of d_G
-    std::vector<float> kc(nik);
-    for (uint64_t j = 0; j < nik; ++j) kc[j] = (float)ikmc[j];
     std::vector<uint32_t> loc(nk, NOLOC);  // (k-mers past the last locus' cumulative count belong to no locus, like in the reference's loop)
     for (uint64_t t = 0; t < ntr; ++t) {
-        const uint32_t a = t ? nk_cum[t - 1] : 0u, b = nk_cum[t], c = t ? nik_cum[t - 1] : 0u, d = nik_cum[t];
-        if (a == b || c == d) continue;
-        for (uint32_t k = a; k < b; ++k) loc[k] = (uint32_t)t;
+        const LocusSpan L = locus_span(nk_cum, nik_cum, t);
+        if (!L.skipped()) std::fill(loc.begin() + L.si, loc.begin() + L.ei, (uint32_t)t);
     }
-    std::vector<uint32_t> nkc;
-    std::vector<uint8_t> dirty;
-    if (windowed) { nkc.assign(nk_cum, nk_cum + ntr); dirty.assign(ns, 0); }
-    dbtk_pred* p = new dbtk_pred;  // (after the host-side vectors: nothing below throws)
+    std::unique_ptr<dbtk_pred, void (*)(dbtk_pred*)> hold(new dbtk_pred, dbtk_pred_free);  // (freed, should a vector or a string below throw)
+    dbtk_pred* p = hold.get();
     p->device = device_id; p->ns = ns; p->nk = nk; p->ntr = ntr; p->nik = nik;
-    p->windowed = windowed; p->max_rows = windowed ? max_rows : 0; p->nkc.swap(nkc); p->dirty.swap(dirty);
-    dbtk_status_t st = DBTK_OK;
-    auto fail = [&](hipError_t e, const char* what) { set_error(std::string(what) + ": " + hipGetErrorString(e)); st = DBTK_ERR_HIP; };
-    hipError_t e;
-    if ((e = hipStreamCreate(&p->stream)) != hipSuccess) fail(e, "hipStreamCreate");
-    for (int i = 0; i < 4 && !st; ++i) if ((e = hipEventCreate(&p->ev[i])) != hipSuccess) fail(e, "hipEventCreate");
-    if (!st && (e = hipMalloc(&p->d_G, grows * ns * sizeof(float))) != hipSuccess) {
-        if (e == hipErrorOutOfMemory) {  // the one allocation of this handle that competes with an aligner's tables for the HBM
-            (void)hipGetLastError();
-            size_t fr = 0, tot = 0;
-            (void)hipMemGetInfo(&fr, &tot);
-            set_error(std::string("genotype matrix: 4 * ") + (windowed ? "max_rows" : "nk") + " * ns = " + std::to_string(grows * ns * sizeof(float)) + " bytes do not fit, " + std::to_string(fr) + " of " + std::to_string(tot) + " bytes of HBM are free");
-            st = DBTK_ERR_NOMEM;
-        } else fail(e, "hipMalloc (genotype matrix)");
-    }
+    p->windowed = windowed; p->w_end = ntr; p->w_rows = nk;  // (a windowed handle opens its first window below)
+    if (windowed) { p->max_rows = max_rows; p->nkc.assign(nk_cum, nk_cum + ntr); p->dirty.assign(ns, 0); }
+    Setup& m = p->mem;
+    STEP(m, hipStreamCreate(&p->stream), "hipStreamCreate");
+    for (auto& e : p->ev) STEP(m, hipEventCreate(&e), "hipEventCreate");
+    // the one allocation of a whole-matrix handle that competes with an aligner's tables for the HBM
+    const std::string gfit = std::string("genotype matrix: 4 * ") + (windowed ? "max_rows" : "nk") + " * ns = " + std::to_string(grows * ns * sizeof(float)) + " bytes";
+    m.device(&p->d_G, grows * ns * sizeof(float), "hipMalloc (genotype matrix)", &gfit);
     if (windowed) {  // the window buffers, device and pinned host, sized once: 24 * max_rows * ns bytes of HBM beside the matrix' 4
-        auto take = [&](hipError_t er, const char* what) {
-            if (er == hipSuccess) return;
-            if (er == hipErrorOutOfMemory) {
-                (void)hipGetLastError();
-                size_t fr = 0, tot = 0;
-                (void)hipMemGetInfo(&fr, &tot);
-                set_error(std::string(what) + " of a window of max_rows = " + std::to_string(max_rows) + " x ns = " + std::to_string(ns) + " do not fit, " + std::to_string(fr) + " of " +
-                          std::to_string(tot) + " bytes of HBM are free");
-                st = DBTK_ERR_NOMEM;
-            } else fail(er, what);
-        };
+        const std::string win = " of a window of max_rows = " + std::to_string(max_rows) + " x ns = " + std::to_string(ns);
+        auto dev = [&](auto** q, uint64_t bytes, const char* what) { const std::string fit = what + win; m.device(q, bytes, what, &fit); };
+        auto pin = [&](auto** q, uint64_t bytes, const char* what) { const std::string fit = what + win; m.host(q, bytes, what, &fit); };
+        const std::string sfit = "hipStreamCreate" + win;
         const uint64_t cells = max_rows * ns;
-        if (!st) take(hipStreamCreate(&p->stream2), "hipStreamCreate");
+        STEP(m, hipStreamCreate(&p->stream2), "hipStreamCreate", &sfit);
         for (int i = 0; i < 2; ++i) {
-            if (!st) take(hipMalloc(&p->d_wc[i], cells * 8), "hipMalloc (staged counts)");
-            if (!st) take(hipMalloc(&p->d_wdepth[i], ns * 4), "hipMalloc (depths)");
-            if (!st) take(hipHostMalloc(&p->h_depth[i], ns * 4), "hipHostMalloc (depths)");
-            for (uint64_t s = 0; s < ns && !st; ++s) p->h_depth[i][s] = 1.f;
+            dev(&p->d_wc[i], cells * 8, "hipMalloc (staged counts)");
+            dev(&p->d_wdepth[i], ns * 4, "hipMalloc (depths)");
+            pin(&p->h_depth[i], ns * 4, "hipHostMalloc (depths)");
+            for (uint64_t s = 0; s < ns && !m.st; ++s) p->h_depth[i][s] = 1.f;
         }
-        if (!st) take(hipMalloc(&p->d_raw, cells * 4), "hipMalloc (raw window)");
-        if (!st) take(hipMalloc(&p->d_cor, cells * 4), "hipMalloc (corrected window)");
-        if (!st) take(hipHostMalloc(&p->h_stage, PW_STAGE * max_rows * 8), "hipHostMalloc (count staging)");
-        if (!st) take(hipHostMalloc(&p->h_raw, cells * 4), "hipHostMalloc (raw window)");
-        if (!st) take(hipHostMalloc(&p->h_cor, cells * 4), "hipHostMalloc (corrected window)");
+        dev(&p->d_raw, cells * 4, "hipMalloc (raw window)");
+        dev(&p->d_cor, cells * 4, "hipMalloc (corrected window)");
+        pin(&p->h_stage, PW_STAGE * max_rows * 8, "hipHostMalloc (count staging)");
+        pin(&p->h_raw, cells * 4, "hipHostMalloc (raw window)");
+        pin(&p->h_cor, cells * 4, "hipHostMalloc (corrected window)");
     }
-    if (!st && (e = hipMalloc(&p->d_bias, ntr * ns * sizeof(float))) != hipSuccess) fail(e, "hipMalloc (bias matrix)");
-    if (!st && (e = hipMalloc(&p->d_nk, ntr * 4)) != hipSuccess) fail(e, "hipMalloc");
-    if (!st && (e = hipMalloc(&p->d_nik, ntr * 4)) != hipSuccess) fail(e, "hipMalloc");
-    if (!st && (e = hipMalloc(&p->d_iki, (nik + 1) * 4)) != hipSuccess) fail(e, "hipMalloc");
-    if (!st && (e = hipMalloc(&p->d_loc, nk * 4)) != hipSuccess) fail(e, "hipMalloc");
-    if (!st && (e = hipMemcpyAsync(p->d_loc, loc.data(), nk * 4, hipMemcpyHostToDevice, p->stream)) != hipSuccess) fail(e, "hipMemcpy");
-    if (!st && (e = hipMalloc(&p->d_ikmc, (nik + 1) * 4)) != hipSuccess) fail(e, "hipMalloc");
-    if (!st && (e = hipMemsetAsync(p->d_G, 0, grows * ns * sizeof(float), p->stream)) != hipSuccess) fail(e, "hipMemset");
-    if (!st && (e = hipMemsetAsync(p->d_bias, 0, ntr * ns * sizeof(float), p->stream)) != hipSuccess) fail(e, "hipMemset");
-    if (!st && (e = hipMemcpyAsync(p->d_nk, nk_cum, ntr * 4, hipMemcpyHostToDevice, p->stream)) != hipSuccess) fail(e, "hipMemcpy");
-    if (!st && (e = hipMemcpyAsync(p->d_nik, nik_cum, ntr * 4, hipMemcpyHostToDevice, p->stream)) != hipSuccess) fail(e, "hipMemcpy");
-    if (!st && nik && (e = hipMemcpyAsync(p->d_iki, iki, nik * 4, hipMemcpyHostToDevice, p->stream)) != hipSuccess) fail(e, "hipMemcpy");
-    if (!st && nik && (e = hipMemcpyAsync(p->d_ikmc, kc.data(), nik * 4, hipMemcpyHostToDevice, p->stream)) != hipSuccess) fail(e, "hipMemcpy");
-    if (!st && (e = hipStreamSynchronize(p->stream)) != hipSuccess) fail(e, "hipStreamSynchronize");
-    if (!st && windowed) st = pred_open_window(p, 0);  // a windowed handle always has a current window
-    if (st) { dbtk_pred_free(p); return st; }
-    *out = p;
+    m.device(&p->d_bias, ntr * ns * sizeof(float), "hipMalloc (bias matrix)");
+    ikmer_upload(m, &p->meta, ntr, nk_cum, nik_cum, nik, iki, ikmc, p->stream);
+    m.device(&p->d_loc, nk * 4);
+    m.upload(p->d_loc, loc.data(), nk * 4, p->stream);
+    STEP(m, hipMemsetAsync(p->d_G, 0, grows * ns * sizeof(float), p->stream), "hipMemset");
+    STEP(m, hipMemsetAsync(p->d_bias, 0, ntr * ns * sizeof(float), p->stream), "hipMemset");
+    STEP(m, hipStreamSynchronize(p->stream), "hipStreamSynchronize");
+    if (!m.st && windowed) m.st = pred_open_window(p, 0);  // a windowed handle always has a current window
+    if (m.st) return m.st;
+    *out = hold.release();
     return DBTK_OK;
 }
 
@@ -525,11 +594,8 @@ void dbtk_pred_free(dbtk_pred_t* p) {
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     if (p->stream2) (void)hipStreamSynchronize(p->stream2);  // (a submitted window that nobody collected)
-    void* ptrs[] = {p->d_G, p->d_bias, p->d_nk, p->d_nik, p->d_iki, p->d_loc, p->d_ikmc, p->d_counts, p->d_depth, p->d_depth2,
-                    p->d_wc[0], p->d_wc[1], p->d_wdepth[0], p->d_wdepth[1], p->d_raw, p->d_cor};
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    void* pinned[] = {p->h_depth[0], p->h_depth[1], p->h_stage, p->h_raw, p->h_cor};
-    for (void* q : pinned) if (q) (void)hipHostFree(q);
+    p->mem.release();
+    for (void* q : {(void*)p->d_counts, (void*)p->d_depth, (void*)p->d_depth2}) if (q) (void)hipFree(q);
     for (auto& e : p->ev) if (e) (void)hipEventDestroy(e);
     if (p->stream) (void)hipStreamDestroy(p->stream);
     if (p->stream2) (void)hipStreamDestroy(p->stream2);
@@ -549,13 +615,10 @@ uint64_t dbtk_pred_ntr(const dbtk_pred_t* p) { return p ? p->ntr : 0; }
 
 static dbtk_status_t dbtk_pred_load_samples_impl(dbtk_pred_t* p, uint64_t first_sample, uint64_t n, const uint64_t* counts, const float* read_depth) {
     if (!p || !counts || !read_depth) { set_error("null argument"); return DBTK_ERR_ARG; }
-    if (first_sample + n > p->ns || n > 0xFFFFFFFFull) { set_error("sample range outside the cohort"); return DBTK_ERR_ARG; }
+    { const dbtk_status_t st = check_sample_range(first_sample, n, p->ns); if (st) return st; }
     if (!n) return DBTK_OK;
     PCHK(hipSetDevice(p->device));
-    if (p->windowed) {
-        if (first_sample > p->ns || n > p->ns - first_sample) { set_error("sample range outside the cohort"); return DBTK_ERR_ARG; }
-        return pred_window_load_host(p, first_sample, n, counts, read_depth);
-    }
+    if (p->windowed) return pred_window_load_host(p, first_sample, n, counts, read_depth);
     if (n > p->stage_cap) {
         if (p->d_counts) PCHK(hipFree(p->d_counts));
         if (p->d_depth) PCHK(hipFree(p->d_depth));
@@ -566,11 +629,7 @@ static dbtk_status_t dbtk_pred_load_samples_impl(dbtk_pred_t* p, uint64_t first_
     }
     PCHK(hipMemcpyAsync(p->d_counts, counts, n * p->nk * 8, hipMemcpyHostToDevice, p->stream));
     PCHK(hipMemcpyAsync(p->d_depth, read_depth, n * 4, hipMemcpyHostToDevice, p->stream));
-    const uint64_t kt = (p->nk + PT_K - 1) / PT_K;
-    if (kt > 0x7FFFFFFFull) { set_error("too many k-mers for one launch"); return DBTK_ERR_ARG; }
-    const uint32_t gy = (uint32_t)std::min<uint64_t>((n + PT_S - 1) / PT_S, 64);
-    hipLaunchKernelGGL(k_pred_load, dim3((uint32_t)kt, gy), dim3(64), 0, p->stream, p->d_counts, p->d_depth, p->d_G, p->nk, p->ns, first_sample, (uint32_t)n);
-    PCHK(hipGetLastError());
+    { const dbtk_status_t st = launch_tile(k_pred_load, p->stream, p->nk, n, p->d_counts, p->d_depth, p->d_G, p->nk, p->ns, first_sample, (uint32_t)n); if (st) return st; }
     PCHK(hipStreamSynchronize(p->stream));  // (the caller's buffers are free again)
     return DBTK_OK;
 }
@@ -592,25 +651,15 @@ static dbtk_status_t pred_load_device_async(dbtk_pred_t* p, uint64_t first_sampl
         p->depth_cap = n;
     }
     PCHK(hipMemcpyAsync(p->d_depth2, read_depth, n * 4, hipMemcpyHostToDevice, p->stream));
-    const uint64_t kt = (p->nk + PT_K - 1) / PT_K;
-    if (kt > 0x7FFFFFFFull) { set_error("too many k-mers for one launch"); return DBTK_ERR_ARG; }
-    const uint32_t gy = (uint32_t)std::min<uint64_t>((n + PT_S - 1) / PT_S, 64);
-    hipLaunchKernelGGL(k_pred_load, dim3((uint32_t)kt, gy), dim3(64), 0, p->stream, d_counts, p->d_depth2, p->d_G, p->nk, p->ns, first_sample, (uint32_t)n);
-    PCHK(hipGetLastError());
-    return DBTK_OK;
+    return launch_tile(k_pred_load, p->stream, p->nk, n, d_counts, p->d_depth2, p->d_G, p->nk, p->ns, first_sample, (uint32_t)n);
 }
 
 dbtk_status_t dbtk_pred_load_device(dbtk_pred_t* p, uint64_t first_sample, uint64_t n, const uint64_t* d_counts, const float* read_depth) {
     if (!p || !d_counts || !read_depth) { set_error("null argument"); return DBTK_ERR_ARG; }
-    if (first_sample > p->ns || n > p->ns - first_sample || n > 0xFFFFFFFFull) { set_error("sample range outside the cohort"); return DBTK_ERR_ARG; }
+    { const dbtk_status_t st = check_sample_range(first_sample, n, p->ns); if (st) return st; }
     if (!n) return DBTK_OK;
     PCHK(hipSetDevice(p->device));
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, d_counts) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != p->device) {
-        (void)hipGetLastError();
-        set_error("dbtk_pred_load_device: d_counts is not device memory of the handle's device");
-        return DBTK_ERR_ARG;
-    }
+    { const dbtk_status_t st = check_device_counts(d_counts, p->device, "dbtk_pred_load_device"); if (st) return st; }
     if (p->windowed) {  // the window's counts are staged (the fused pass reads all samples at once): one copy inside HBM
         hipStream_t s = p->ws(p->cur);
         if (p->w_rows) PCHK(hipMemcpyAsync(p->d_wc[p->cur] + first_sample * p->w_rows, d_counts, n * p->w_rows * 8, hipMemcpyDeviceToDevice, s));
@@ -627,22 +676,11 @@ dbtk_status_t dbtk_pred_load_device(dbtk_pred_t* p, uint64_t first_sample, uint6
 dbtk_status_t dbtk_pred_load_ctx(dbtk_pred_t* p, uint64_t sample, dbtk_ctx_t* ctx, float read_depth) {
     if (!p || !ctx) { set_error("null argument"); return DBTK_ERR_ARG; }
     if (p->windowed) { set_error("dbtk_pred_load_ctx: a context holds one sample's whole count vector, a windowed handle takes a window's counts of every sample: use dbtk_pred_load_device"); return DBTK_ERR_ARG; }
-    CtxFacts f;
-    { const dbtk_status_t st = ctx_facts(ctx, &f); if (st) return st; }
     if (sample >= p->ns) { set_error("sample outside the cohort"); return DBTK_ERR_ARG; }
-    if (f.ntrkmers != p->nk) { set_error("the context counts " + std::to_string(f.ntrkmers) + " TR k-mers, ikmer.meta has " + std::to_string(p->nk) + ": not the same RPGG build"); return DBTK_ERR_ARG; }
-    if (f.device != p->device) { set_error("the context is on device " + std::to_string(f.device) + ", the matrix on device " + std::to_string(p->device)); return DBTK_ERR_ARG; }
-    if (f.unflushed_pairs) {
-        set_error(std::to_string(f.unflushed_pairs) + " pairs appended by dbtk_ingest_align_merged are not aligned yet: flush them first (slot = ~0u, flush = 1)");
-        return DBTK_ERR_ARG;
-    }
-    // every batch done, the counter replicas folded, and a pending sticky error word reported instead of a tainted column
-    { const dbtk_status_t st = dbtk_ctx_synchronize(ctx); if (st) return st; }
-    void* base = nullptr; uint64_t n64 = 0;
-    { const dbtk_status_t st = dbtk_ctx_accum_buffer(ctx, &base, &n64); if (st) return st; }
-    if (!base || n64 < p->nk) { set_error("the context has no accumulators"); return DBTK_ERR_ARG; }
-    PCHK(hipSetDevice(p->device));
-    const dbtk_status_t st = pred_load_device_async(p, sample, 1, (const uint64_t*)base, &read_depth);
+    static const char* const whose[2] = {"ikmer.meta has", "the matrix"};
+    const uint64_t* base = nullptr;
+    { const dbtk_status_t st = ctx_counts_ready(ctx, p->device, p->nk, whose, &base); if (st) return st; }
+    const dbtk_status_t st = pred_load_device_async(p, sample, 1, base, &read_depth);
     if (st) return st;
     PCHK(hipStreamSynchronize(p->stream));  // (d_accum is no longer being read: dbtk_ctx_reset may follow)
     return DBTK_OK;
@@ -651,18 +689,17 @@ dbtk_status_t dbtk_pred_load_ctx(dbtk_pred_t* p, uint64_t sample, dbtk_ctx_t* ct
 dbtk_status_t dbtk_pred_correct(dbtk_pred_t* p) {
     if (!p) { set_error("null argument"); return DBTK_ERR_ARG; }
     PCHK(hipSetDevice(p->device));
-    // the loci and rows at work: everything, or the current window (whose Bias rows alone are made again)
-    const uint64_t t0 = p->windowed ? p->w_first : 0, nl = p->windowed ? p->w_end - p->w_first : p->ntr;
-    const uint64_t row0 = p->windowed ? p->w_row0 : 0, rows = p->windowed ? p->w_rows : p->nk;
-    hipStream_t s = p->ws(p->windowed ? p->cur : 0);
+    // the loci and rows at work: the current window's (everything on a whole-matrix handle); its Bias rows alone are made again
+    const uint64_t t0 = p->w_first, nl = p->w_end - p->w_first, row0 = p->w_row0, rows = p->w_rows;
+    hipStream_t s = p->ws(p->cur);
     if (p->windowed) { const dbtk_status_t st = pred_window_materialize(p); if (st) return st; }
     PCHK(hipMemsetAsync(p->d_bias + t0 * p->ns, 0, nl * p->ns * sizeof(float), s));
     PCHK(hipEventRecord(p->ev[0], s));
-    hipLaunchKernelGGL(k_pred_bias, dim3((uint32_t)nl, (uint32_t)((p->ns + 63) / 64)), dim3(64), 0, s, p->d_G, p->d_nk, p->d_nik, p->d_iki, p->d_ikmc, p->d_bias, p->ns,
+    hipLaunchKernelGGL(k_pred_bias, dim3((uint32_t)nl, (uint32_t)((p->ns + 63) / 64)), dim3(64), 0, s, p->d_G, p->meta.nk, p->meta.nik, p->meta.iki, p->meta.ikmc, p->d_bias, p->ns,
                        (uint32_t)t0, (uint32_t)row0);
     PCHK(hipGetLastError());
     PCHK(hipEventRecord(p->ev[1], s));
-    hipLaunchKernelGGL(k_pred_bias_norm, dim3((uint32_t)nl), dim3(256), 0, s, p->d_nk, p->d_nik, p->d_bias, p->ns, (uint32_t)t0);
+    hipLaunchKernelGGL(k_pred_bias_norm, dim3((uint32_t)nl), dim3(256), 0, s, p->meta.nk, p->meta.nik, p->d_bias, p->ns, (uint32_t)t0);
     PCHK(hipGetLastError());
     PCHK(hipEventRecord(p->ev[2], s));
     if (rows) {
@@ -682,10 +719,8 @@ dbtk_status_t dbtk_pred_matrix(dbtk_pred_t* p, float* out) {
     if (p->windowed) {
         { const dbtk_status_t st = pred_window_materialize(p); if (st) return st; }
         PCHK(hipStreamSynchronize(p->ws(p->cur)));
-        if (p->w_rows) PCHK(hipMemcpy(out, p->d_G, p->w_rows * p->ns * sizeof(float), hipMemcpyDeviceToHost));
-        return DBTK_OK;
     }
-    PCHK(hipMemcpy(out, p->d_G, p->nk * p->ns * sizeof(float), hipMemcpyDeviceToHost));
+    if (p->w_rows) PCHK(hipMemcpy(out, p->d_G, p->w_rows * p->ns * sizeof(float), hipMemcpyDeviceToHost));
     return DBTK_OK;
 }
 
@@ -720,16 +755,13 @@ dbtk_status_t dbtk_pred_window_submit(dbtk_pred_t* p) {
     PCHK(hipMemcpyAsync(p->d_wdepth[c], p->h_depth[c], ns * 4, hipMemcpyHostToDevice, s));
     PCHK(hipMemsetAsync(p->d_bias + p->w_first * ns, 0, nl * ns * sizeof(float), s));
     if (rows) {
-        const uint64_t kt = (rows + PT_K - 1) / PT_K;
-        if (kt > 0x7FFFFFFFull || nl > 0x7FFFFFFFull) { set_error("window too large for one launch"); return DBTK_ERR_ARG; }
-        hipLaunchKernelGGL(k_pred_wbias, dim3((uint32_t)nl, (uint32_t)((ns + WB_S - 1) / WB_S)), dim3(64), 0, s, p->d_wc[c], p->d_wdepth[c], p->d_nk, p->d_nik, p->d_iki, p->d_ikmc,
+        if (nl > 0x7FFFFFFFull) { set_error("window too large for one launch"); return DBTK_ERR_ARG; }
+        hipLaunchKernelGGL(k_pred_wbias, dim3((uint32_t)nl, (uint32_t)((ns + WB_S - 1) / WB_S)), dim3(64), 0, s, p->d_wc[c], p->d_wdepth[c], p->meta.nk, p->meta.nik, p->meta.iki, p->meta.ikmc,
                            p->d_bias, ns, rows, (uint32_t)p->w_first, (uint32_t)p->w_row0);
         PCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_pred_bias_norm, dim3((uint32_t)nl), dim3(256), 0, s, p->d_nk, p->d_nik, p->d_bias, ns, (uint32_t)p->w_first);
+        hipLaunchKernelGGL(k_pred_bias_norm, dim3((uint32_t)nl), dim3(256), 0, s, p->meta.nk, p->meta.nik, p->d_bias, ns, (uint32_t)p->w_first);
         PCHK(hipGetLastError());
-        const uint32_t gy = (uint32_t)std::min<uint64_t>((ns + PT_S - 1) / PT_S, 64);
-        hipLaunchKernelGGL(k_pred_wfused, dim3((uint32_t)kt, gy), dim3(64), 0, s, p->d_wc[c], p->d_wdepth[c], p->d_loc + p->w_row0, p->d_bias, p->d_raw, p->d_cor, rows, ns);
-        PCHK(hipGetLastError());
+        { const dbtk_status_t st = launch_tile(k_pred_wfused, s, rows, ns, p->d_wc[c], p->d_wdepth[c], p->d_loc + p->w_row0, p->d_bias, p->d_raw, p->d_cor, rows, ns); if (st) return st; }
         PCHK(hipMemcpyAsync(p->h_raw, p->d_raw, rows * ns * sizeof(float), hipMemcpyDeviceToHost, s));
         PCHK(hipMemcpyAsync(p->h_cor, p->d_cor, rows * ns * sizeof(float), hipMemcpyDeviceToHost, s));
     }
@@ -797,10 +829,11 @@ struct dbtk_dosage {
     float *d_raw = nullptr, *d_bias = nullptr;   // [ntr][ns]: the raw bias of the loads; normalised by dbtk_dosage_finish
     float* d_values = nullptr;                   // [ntr][ns]: what dbtk_dosage_values reads back (made by the call)
     float* d_depth = nullptr;                    // [ns]
-    uint32_t *d_nk = nullptr, *d_nik = nullptr, *d_iki = nullptr, *d_floc = nullptr, *d_fbeg = nullptr;
-    float* d_ikmc = nullptr;
+    IkmerDev meta;
+    uint32_t *d_floc = nullptr, *d_fbeg = nullptr;
     DosItem* d_items = nullptr;
     uint64_t* d_part = nullptr;
+    Setup mem;                                   // the creation's allocations (all above)
     uint64_t* d_stage = nullptr;                 // 16 samples' counts of dbtk_dosage_load_samples, allocated by its first call
     uint32_t nitems = 0, nfold = 0;
     uint64_t bytes = 0;
@@ -813,13 +846,14 @@ struct dbtk_dosage {
 constexpr uint64_t DS_STAGE = 16;  // samples per transfer of dbtk_dosage_load_samples (what danbing-tk-pred stages for the matrix, too)
 
 // the work list of k_dosage_sample: whole loci packed greedily into items of at most DS_CH k-mers, larger loci cut into parts
-static void dosage_items(uint64_t ntr, const uint32_t* nk_cum, bool with_bias, std::vector<DosItem>* items, std::vector<uint32_t>* floc, std::vector<uint32_t>* fbeg) {
+static void dosage_items(uint64_t ntr, const uint32_t* nk_cum, const uint32_t* nik_cum, bool with_bias, std::vector<DosItem>* items, std::vector<uint32_t>* floc, std::vector<uint32_t>* fbeg) {
     DosItem cur{0, 0, 0, 0, NOPART, 0};
     auto flush = [&] { if (cur.nl) { cur.nlb = with_bias ? cur.nl : 0; items->push_back(cur); } cur = DosItem{0, 0, 0, 0, NOPART, 0}; };
     uint32_t nparts = 0;
     fbeg->push_back(0);
     for (uint64_t t = 0; t < ntr; ++t) {
-        const uint32_t a = t ? nk_cum[t - 1] : 0u, n = nk_cum[t] - a;
+        const LocusSpan L = locus_span(nk_cum, nik_cum, t);
+        const uint32_t a = L.si, n = L.ei - L.si;
         if (n > (uint32_t)DS_CH) {
             flush();
             for (uint32_t o = 0; o < n; o += DS_CH)
@@ -840,8 +874,8 @@ extern "C" {
 void dbtk_dosage_free(dbtk_dosage_t* d) {
     if (!d) return;
     (void)hipSetDevice(d->device);
-    void* ptrs[] = {d->d_kms, d->d_raw, d->d_bias, d->d_values, d->d_depth, d->d_nk, d->d_nik, d->d_iki, d->d_floc, d->d_fbeg, d->d_ikmc, d->d_items, d->d_part, d->d_stage};
-    for (void* q : ptrs) if (q) (void)hipFree(q);
+    d->mem.release();
+    if (d->d_stage) (void)hipFree(d->d_stage);
     for (auto& e : d->ev) if (e) (void)hipEventDestroy(e);
     if (d->stream) (void)hipStreamDestroy(d->stream);
     delete d;
@@ -852,53 +886,39 @@ static dbtk_status_t dbtk_dosage_create_impl(int device_id, uint64_t ns, uint64_
     if (!out) { set_error("null argument"); return DBTK_ERR_ARG; }
     *out = nullptr;
     { const dbtk_status_t cs = check_ikmer_meta(device_id, ns, nk, ntr, nk_cum, nik_cum, nik, iki, ikmc); if (cs) return cs; }
-    std::vector<float> kc(nik);
-    for (uint64_t j = 0; j < nik; ++j) kc[j] = (float)ikmc[j];
     std::vector<DosItem> items;
     std::vector<uint32_t> floc, fbeg;
-    dosage_items(ntr, nk_cum, nik != 0, &items, &floc, &fbeg);
+    dosage_items(ntr, nk_cum, nik_cum, nik != 0, &items, &floc, &fbeg);
     if (items.size() > 0x7FFFFFFFull) { set_error("too many work items for one launch"); return DBTK_ERR_ARG; }
-    dbtk_dosage* d = new dbtk_dosage;  // (after the host-side vectors, but for this one: freed below should it throw)
-    dbtk_status_t st = DBTK_OK;
-    try { d->depth.assign(ns, 1.f); } catch (...) { delete d; throw; }
+    std::unique_ptr<dbtk_dosage, void (*)(dbtk_dosage*)> hold(new dbtk_dosage, dbtk_dosage_free);  // (freed, should a vector or a string below throw)
+    dbtk_dosage* d = hold.get();
+    d->depth.assign(ns, 1.f);
     d->device = device_id; d->ns = ns; d->nk = nk; d->ntr = ntr; d->nik = nik;
     d->nitems = (uint32_t)items.size(); d->nfold = (uint32_t)floc.size();
     const uint64_t cells = ntr * ns, nparts = fbeg.back();
-    const uint64_t sizes[] = {cells * 8, cells * 4, cells * 4, cells * 4, ns * 4, ntr * 4, ntr * 4, (nik + 1) * 4, (uint64_t)(floc.size() + 1) * 4, (uint64_t)fbeg.size() * 4,
-                              (nik + 1) * 4, (uint64_t)(items.size() + 1) * sizeof(DosItem), (nparts + 1) * 8};
-    void** const slots[] = {(void**)&d->d_kms, (void**)&d->d_raw, (void**)&d->d_bias, (void**)&d->d_values, (void**)&d->d_depth, (void**)&d->d_nk, (void**)&d->d_nik, (void**)&d->d_iki,
-                            (void**)&d->d_floc, (void**)&d->d_fbeg, (void**)&d->d_ikmc, (void**)&d->d_items, (void**)&d->d_part};
-    for (uint64_t b : sizes) d->bytes += b;
-    auto fail = [&](hipError_t e, const char* what) { set_error(std::string(what) + ": " + hipGetErrorString(e)); st = DBTK_ERR_HIP; };
-    hipError_t e;
-    if ((e = hipStreamCreate(&d->stream)) != hipSuccess) fail(e, "hipStreamCreate");
-    for (int i = 0; i < 4 && !st; ++i) if ((e = hipEventCreate(&d->ev[i])) != hipSuccess) fail(e, "hipEventCreate");
-    for (size_t i = 0; i < sizeof sizes / sizeof sizes[0] && !st; ++i) {
-        if ((e = hipMalloc(slots[i], sizes[i])) == hipSuccess) continue;
-        if (e == hipErrorOutOfMemory) {
-            (void)hipGetLastError();
-            size_t fr = 0, tot = 0;
-            (void)hipMemGetInfo(&fr, &tot);
-            set_error("dosage tables: " + std::to_string(d->bytes) + " bytes (20 * ntr * ns = " + std::to_string(cells * 20) + " of them) do not fit, " + std::to_string(fr) +
-                      " of " + std::to_string(tot) + " bytes of HBM are free");
-            st = DBTK_ERR_NOMEM;
-        } else fail(e, "hipMalloc (dosage tables)");
-    }
-    hipStream_t s = d->stream;
-    if (!st && (e = hipMemsetAsync(d->d_kms, 0, cells * 8, s)) != hipSuccess) fail(e, "hipMemset");
-    if (!st && (e = hipMemsetAsync(d->d_raw, 0, cells * 4, s)) != hipSuccess) fail(e, "hipMemset");
-    if (!st && (e = hipMemsetAsync(d->d_bias, 0, cells * 4, s)) != hipSuccess) fail(e, "hipMemset");
-    if (!st && (e = hipMemcpyAsync(d->d_depth, d->depth.data(), ns * 4, hipMemcpyHostToDevice, s)) != hipSuccess) fail(e, "hipMemcpy");
-    if (!st && (e = hipMemcpyAsync(d->d_nk, nk_cum, ntr * 4, hipMemcpyHostToDevice, s)) != hipSuccess) fail(e, "hipMemcpy");
-    if (!st && (e = hipMemcpyAsync(d->d_nik, nik_cum, ntr * 4, hipMemcpyHostToDevice, s)) != hipSuccess) fail(e, "hipMemcpy");
-    if (!st && nik && (e = hipMemcpyAsync(d->d_iki, iki, nik * 4, hipMemcpyHostToDevice, s)) != hipSuccess) fail(e, "hipMemcpy");
-    if (!st && nik && (e = hipMemcpyAsync(d->d_ikmc, kc.data(), nik * 4, hipMemcpyHostToDevice, s)) != hipSuccess) fail(e, "hipMemcpy");
-    if (!st && !items.empty() && (e = hipMemcpyAsync(d->d_items, items.data(), items.size() * sizeof(DosItem), hipMemcpyHostToDevice, s)) != hipSuccess) fail(e, "hipMemcpy");
-    if (!st && !floc.empty() && (e = hipMemcpyAsync(d->d_floc, floc.data(), floc.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess) fail(e, "hipMemcpy");
-    if (!st && (e = hipMemcpyAsync(d->d_fbeg, fbeg.data(), fbeg.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess) fail(e, "hipMemcpy");
-    if (!st && (e = hipStreamSynchronize(s)) != hipSuccess) fail(e, "hipStreamSynchronize");
-    if (st) { dbtk_dosage_free(d); return st; }
-    *out = d;
+    const struct { void** slot; uint64_t bytes; } tabs[] = {
+        {(void**)&d->d_kms, cells * 8}, {(void**)&d->d_raw, cells * 4}, {(void**)&d->d_bias, cells * 4}, {(void**)&d->d_values, cells * 4}, {(void**)&d->d_depth, ns * 4},
+        {(void**)&d->d_floc, (floc.size() + 1) * 4}, {(void**)&d->d_fbeg, fbeg.size() * 4}, {(void**)&d->d_items, (items.size() + 1) * sizeof(DosItem)}, {(void**)&d->d_part, (nparts + 1) * 8}};
+    d->bytes = 2 * ntr * 4 + 2 * (nik + 1) * 4;  // (ikmer_upload's four)
+    for (auto& t : tabs) d->bytes += t.bytes;
+    const char* const what = "hipMalloc (dosage tables)";
+    const std::string fit = "dosage tables: " + std::to_string(d->bytes) + " bytes (20 * ntr * ns = " + std::to_string(cells * 20) + " of them)";
+    Setup& m = d->mem;
+    hipStream_t& s = d->stream;
+    STEP(m, hipStreamCreate(&s), "hipStreamCreate");
+    for (auto& e : d->ev) STEP(m, hipEventCreate(&e), "hipEventCreate");
+    for (auto& t : tabs) m.device(t.slot, t.bytes, what, &fit);
+    ikmer_upload(m, &d->meta, ntr, nk_cum, nik_cum, nik, iki, ikmc, s, what, &fit);
+    STEP(m, hipMemsetAsync(d->d_kms, 0, cells * 8, s), "hipMemset");
+    STEP(m, hipMemsetAsync(d->d_raw, 0, cells * 4, s), "hipMemset");
+    STEP(m, hipMemsetAsync(d->d_bias, 0, cells * 4, s), "hipMemset");
+    m.upload(d->d_depth, d->depth.data(), ns * 4, s);
+    m.upload(d->d_items, items.data(), items.size() * sizeof(DosItem), s);
+    m.upload(d->d_floc, floc.data(), floc.size() * 4, s);
+    m.upload(d->d_fbeg, fbeg.data(), fbeg.size() * 4, s);
+    STEP(m, hipStreamSynchronize(s), "hipStreamSynchronize");
+    if (m.st) return m.st;
+    *out = hold.release();
     return DBTK_OK;
 }
 
@@ -923,15 +943,15 @@ uint64_t dbtk_dosage_nk(const dbtk_dosage_t* d) { return d ? d->nk : 0; }
 uint64_t dbtk_dosage_ntr(const dbtk_dosage_t* d) { return d ? d->ntr : 0; }
 uint64_t dbtk_dosage_bytes(const dbtk_dosage_t* d) { return d ? d->bytes : 0; }
 
-// n samples' counts in device memory -> their kms and raw entries; asynchronous on d->stream, between ev[0] and ev[1]
-static dbtk_status_t dosage_load_async(dbtk_dosage_t* d, uint64_t first, uint64_t n, const uint64_t* d_counts, const float* read_depth) {
+// n samples' counts in device memory -> their kms and raw entries, waited for; the kernels' time (ev[0] to ev[1]) is added to *ms_sum
+static dbtk_status_t dosage_load(dbtk_dosage_t* d, uint64_t first, uint64_t n, const uint64_t* d_counts, const float* read_depth, float* ms_sum) {
     hipStream_t s = d->stream;
     for (uint64_t i = 0; i < n; ++i) d->depth[first + i] = read_depth[i];
     d->finished = false;
     PCHK(hipMemcpyAsync(d->d_depth + first, d->depth.data() + first, n * 4, hipMemcpyHostToDevice, s));
     PCHK(hipEventRecord(d->ev[0], s));
     for (uint64_t i = 0; i < n && d->nitems; ++i) {
-        hipLaunchKernelGGL(k_dosage_sample, dim3(d->nitems), dim3(DS_T), 0, s, d_counts + i * d->nk, read_depth[i], d->d_items, d->d_nk, d->d_nik, d->d_iki, d->d_ikmc,
+        hipLaunchKernelGGL(k_dosage_sample, dim3(d->nitems), dim3(DS_T), 0, s, d_counts + i * d->nk, read_depth[i], d->d_items, d->meta.nk, d->meta.nik, d->meta.iki, d->meta.ikmc,
                            d->d_kms, d->d_raw, d->d_part, d->ns, first + i);
         PCHK(hipGetLastError());
         if (d->nfold) {
@@ -940,10 +960,7 @@ static dbtk_status_t dosage_load_async(dbtk_dosage_t* d, uint64_t first, uint64_
         }
     }
     PCHK(hipEventRecord(d->ev[1], s));
-    return DBTK_OK;
-}
-static dbtk_status_t dosage_load_wait(dbtk_dosage_t* d, float* ms_sum) {
-    PCHK(hipStreamSynchronize(d->stream));
+    PCHK(hipStreamSynchronize(s));  // (d_counts is no longer being read)
     float ms = 0;
     PCHK(hipEventElapsedTime(&ms, d->ev[0], d->ev[1]));
     *ms_sum += ms;
@@ -952,49 +969,31 @@ static dbtk_status_t dosage_load_wait(dbtk_dosage_t* d, float* ms_sum) {
 
 dbtk_status_t dbtk_dosage_load_device(dbtk_dosage_t* d, uint64_t first_sample, uint64_t n, const uint64_t* d_counts, const float* read_depth) {
     if (!d || !d_counts || !read_depth) { set_error("null argument"); return DBTK_ERR_ARG; }
-    if (first_sample > d->ns || n > d->ns - first_sample || n > 0xFFFFFFFFull) { set_error("sample range outside the cohort"); return DBTK_ERR_ARG; }
+    { const dbtk_status_t st = check_sample_range(first_sample, n, d->ns); if (st) return st; }
     if (!n) return DBTK_OK;
     PCHK(hipSetDevice(d->device));
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, d_counts) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != d->device) {
-        (void)hipGetLastError();
-        set_error("dbtk_dosage_load_device: d_counts is not device memory of the handle's device");
-        return DBTK_ERR_ARG;
-    }
-    { const dbtk_status_t st = dosage_load_async(d, first_sample, n, d_counts, read_depth); if (st) return st; }
+    { const dbtk_status_t st = check_device_counts(d_counts, d->device, "dbtk_dosage_load_device"); if (st) return st; }
     float ms = 0;
-    { const dbtk_status_t st = dosage_load_wait(d, &ms); if (st) return st; }  // (d_counts is no longer being read)
+    { const dbtk_status_t st = dosage_load(d, first_sample, n, d_counts, read_depth, &ms); if (st) return st; }
     d->ms[0] = ms;
     return DBTK_OK;
 }
 
 dbtk_status_t dbtk_dosage_load_ctx(dbtk_dosage_t* d, uint64_t sample, dbtk_ctx_t* ctx, float read_depth) {
     if (!d || !ctx) { set_error("null argument"); return DBTK_ERR_ARG; }
-    CtxFacts f;
-    { const dbtk_status_t st = ctx_facts(ctx, &f); if (st) return st; }
     if (sample >= d->ns) { set_error("sample outside the cohort"); return DBTK_ERR_ARG; }
-    if (f.ntrkmers != d->nk) { set_error("the context counts " + std::to_string(f.ntrkmers) + " TR k-mers, the dosage handle " + std::to_string(d->nk) + ": not the same RPGG build"); return DBTK_ERR_ARG; }
-    if (f.device != d->device) { set_error("the context is on device " + std::to_string(f.device) + ", the dosage tables on device " + std::to_string(d->device)); return DBTK_ERR_ARG; }
-    if (f.unflushed_pairs) {
-        set_error(std::to_string(f.unflushed_pairs) + " pairs appended by dbtk_ingest_align_merged are not aligned yet: flush them first (slot = ~0u, flush = 1)");
-        return DBTK_ERR_ARG;
-    }
-    // every batch done, the counter replicas folded, and a pending sticky error word reported instead of tainted sums
-    { const dbtk_status_t st = dbtk_ctx_synchronize(ctx); if (st) return st; }
-    void* base = nullptr; uint64_t n64 = 0;
-    { const dbtk_status_t st = dbtk_ctx_accum_buffer(ctx, &base, &n64); if (st) return st; }
-    if (!base || n64 < d->nk) { set_error("the context has no accumulators"); return DBTK_ERR_ARG; }
-    PCHK(hipSetDevice(d->device));
-    { const dbtk_status_t st = dosage_load_async(d, sample, 1, (const uint64_t*)base, &read_depth); if (st) return st; }
+    static const char* const whose[2] = {"the dosage handle", "the dosage tables"};
+    const uint64_t* base = nullptr;
+    { const dbtk_status_t st = ctx_counts_ready(ctx, d->device, d->nk, whose, &base); if (st) return st; }
     float ms = 0;
-    { const dbtk_status_t st = dosage_load_wait(d, &ms); if (st) return st; }  // (d_accum is no longer being read: dbtk_ctx_reset may follow)
+    { const dbtk_status_t st = dosage_load(d, sample, 1, base, &read_depth, &ms); if (st) return st; }  // (d_accum is no longer being read: dbtk_ctx_reset may follow)
     d->ms[0] = ms;
     return DBTK_OK;
 }
 
 static dbtk_status_t dbtk_dosage_load_samples_impl(dbtk_dosage_t* d, uint64_t first_sample, uint64_t n, const uint64_t* counts, const float* read_depth) {
     if (!d || !counts || !read_depth) { set_error("null argument"); return DBTK_ERR_ARG; }
-    if (first_sample > d->ns || n > d->ns - first_sample || n > 0xFFFFFFFFull) { set_error("sample range outside the cohort"); return DBTK_ERR_ARG; }
+    { const dbtk_status_t st = check_sample_range(first_sample, n, d->ns); if (st) return st; }
     if (!n) return DBTK_OK;
     PCHK(hipSetDevice(d->device));
     if (!d->d_stage) {
@@ -1005,8 +1004,7 @@ static dbtk_status_t dbtk_dosage_load_samples_impl(dbtk_dosage_t* d, uint64_t fi
     for (uint64_t i0 = 0; i0 < n; i0 += DS_STAGE) {
         const uint64_t ni = std::min<uint64_t>(DS_STAGE, n - i0);
         PCHK(hipMemcpyAsync(d->d_stage, counts + i0 * d->nk, ni * d->nk * 8, hipMemcpyHostToDevice, d->stream));
-        { const dbtk_status_t st = dosage_load_async(d, first_sample + i0, ni, d->d_stage, read_depth + i0); if (st) return st; }
-        { const dbtk_status_t st = dosage_load_wait(d, &ms); if (st) return st; }  // (the staging buffer is free again)
+        { const dbtk_status_t st = dosage_load(d, first_sample + i0, ni, d->d_stage, read_depth + i0, &ms); if (st) return st; }  // (the staging buffer is free again)
     }
     d->ms[0] = ms;
     return DBTK_OK;
@@ -1018,7 +1016,7 @@ dbtk_status_t dbtk_dosage_finish(dbtk_dosage_t* d) {
     hipStream_t s = d->stream;
     PCHK(hipEventRecord(d->ev[2], s));
     PCHK(hipMemcpyAsync(d->d_bias, d->d_raw, d->ntr * d->ns * sizeof(float), hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(k_pred_bias_norm, dim3((uint32_t)d->ntr), dim3(256), 0, s, d->d_nk, d->d_nik, d->d_bias, d->ns, 0u);
+    hipLaunchKernelGGL(k_pred_bias_norm, dim3((uint32_t)d->ntr), dim3(256), 0, s, d->meta.nk, d->meta.nik, d->d_bias, d->ns, 0u);
     PCHK(hipGetLastError());
     PCHK(hipEventRecord(d->ev[3], s));
     PCHK(hipStreamSynchronize(s));
@@ -1044,7 +1042,7 @@ dbtk_status_t dbtk_dosage_values(dbtk_dosage_t* d, float* out) {
     if (!d || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
     if (!d->finished) { set_error("dbtk_dosage_values: samples were loaded since the last dbtk_dosage_finish (or it was never called)"); return DBTK_ERR_ARG; }
     PCHK(hipSetDevice(d->device));
-    hipLaunchKernelGGL(k_dosage_values, dim3((uint32_t)d->ntr, (uint32_t)((d->ns + 255) / 256)), dim3(256), 0, d->stream, d->d_kms, d->d_bias, d->d_depth, d->d_nk, d->d_nik, d->d_values, d->ns);
+    hipLaunchKernelGGL(k_dosage_values, dim3((uint32_t)d->ntr, (uint32_t)((d->ns + 255) / 256)), dim3(256), 0, d->stream, d->d_kms, d->d_bias, d->d_depth, d->meta.nk, d->meta.nik, d->d_values, d->ns);
     PCHK(hipGetLastError());
     PCHK(hipMemcpyAsync(out, d->d_values, d->ntr * d->ns * sizeof(float), hipMemcpyDeviceToHost, d->stream));
     PCHK(hipStreamSynchronize(d->stream));

@@ -35,17 +35,32 @@ static void read_gt_meta(const std::string& fn, std::vector<std::string>* fns, s
     while (std::getline(fin, f1, '\t') && std::getline(fin, f2)) { fns->push_back(f1); rds->push_back(std::stof(f2)); }
     if (fns->empty()) die(fn + ": no samples");
 }
-// load_eachBinGT (pred.h:166-186), one file: 8 bytes (nk) | 8 * nk bytes (counts)
-static void read_counts(const std::string& fn, uint64_t nk, uint64_t* out) {
+// load_eachBinGT (pred.h:166-186), one file: 8 bytes (nk) | 8 * nk bytes (counts).  The file, open behind a header of this RPGG build
+static FILE* check_nk_header(const std::string& fn, uint64_t nk) {
     FILE* f = fopen(fn.c_str(), "rb");
     if (!f) die("cannot open " + fn, 134);
     uint64_t nkf = 0;
     if (fread(&nkf, 8, 1, f) != 1 || nkf != nk) { fprintf(stderr, "nk %llu != nk_ %llu\n", (unsigned long long)nkf, (unsigned long long)nk); exit(134); }  // the reference asserts
+    return f;
+}
+static void read_counts(const std::string& fn, uint64_t nk, uint64_t* out) {
+    FILE* f = check_nk_header(fn, nk);
     if (fread(out, 8, nk, f) != nk) die("truncated " + fn, 134);
     fclose(f);
 }
+// the cohort's count files to the GPU, 16 samples per transfer: load(first sample, n, their counts, their depths) hands a batch to the handle
+template <class Load>
+static void load_batches(const std::vector<std::string>& fns, const std::vector<float>& rds, uint64_t nk, Load load) {
+    const uint64_t B = 16, ns = fns.size();
+    std::vector<uint64_t> buf(B * nk);
+    for (uint64_t s0 = 0; s0 < ns; s0 += B) {
+        const uint64_t n = std::min<uint64_t>(B, ns - s0);
+        for (uint64_t i = 0; i < n; ++i) read_counts(fns[s0 + i], nk, buf.data() + i * nk);
+        if (load(s0, n, buf.data(), rds.data() + s0)) die(dbtk_last_error());
+    }
+}
 
-// --dosage: the count files go to the GPU 16 samples at a time like below, but into the per-locus tables
+// --dosage: the count files go to the GPU like below, but into the per-locus tables
 static int dosage_tables(int device, const std::string& finGtMeta, const std::string& finIkMeta, const std::string& foutBias, const std::string& foutDosage,
                          const std::string& foutKms) {
     printf("metadata of *.trkmc.ar: %s\ninvariant kmers: %s\ndosage table will be written to: %s\nbias matrix will be written to: %s\n",
@@ -58,16 +73,13 @@ static int dosage_tables(int device, const std::string& finGtMeta, const std::st
     if (dbtk_dosage_create_from_file(device, ns, finIkMeta.c_str(), &D)) die(dbtk_last_error());
     const uint64_t nk = dbtk_dosage_nk(D), ntr = dbtk_dosage_ntr(D);
     printf("%llu loci in total.\nreading %llu gt files\n", (unsigned long long)ntr, (unsigned long long)ns);
-    const uint64_t B = 16;
-    std::vector<uint64_t> buf(B * nk);
     float load_ms = 0, ms[2];
-    for (uint64_t s0 = 0; s0 < ns; s0 += B) {
-        const uint64_t n = std::min<uint64_t>(B, ns - s0);
-        for (uint64_t i = 0; i < n; ++i) read_counts(fns[s0 + i], nk, buf.data() + i * nk);
-        if (dbtk_dosage_load_samples(D, s0, n, buf.data(), rds.data() + s0)) die(dbtk_last_error());
+    load_batches(fns, rds, nk, [&](uint64_t s0, uint64_t n, const uint64_t* counts, const float* depths) {
+        const dbtk_status_t st = dbtk_dosage_load_samples(D, s0, n, counts, depths);
         dbtk_dosage_times(D, ms);
         load_ms += ms[0];
-    }
+        return st;
+    });
     if (dbtk_dosage_finish(D)) die(dbtk_last_error());
     dbtk_dosage_times(D, ms);
     printf("finished in %.3f ms on the GPU (per-locus sums and raw bias %.3f, bias normalisation %.3f)\n", load_ms + ms[1], load_ms, ms[1]);
@@ -98,13 +110,7 @@ static int windowed(int device, const std::string& finGtMeta, const std::string&
     const uint64_t nk = dbtk_pred_nk(P), ntr = dbtk_pred_ntr(P);
     printf("%llu loci in total.\n", (unsigned long long)ntr);
     printf("reading %llu gt files in windows of at most %llu k-mers\n", (unsigned long long)ns, (unsigned long long)dbtk_pred_max_rows(P));
-    for (uint64_t s = 0; s < ns; ++s) {  // load_eachBinGT's assertion, once per file and before anything is written
-        FILE* f = fopen(fns[s].c_str(), "rb");
-        if (!f) die("cannot open " + fns[s], 134);
-        uint64_t nkf = 0;
-        if (fread(&nkf, 8, 1, f) != 1 || nkf != nk) { fprintf(stderr, "nk %llu != nk_ %llu\n", (unsigned long long)nkf, (unsigned long long)nk); exit(134); }  // the reference asserts
-        fclose(f);
-    }
+    for (uint64_t s = 0; s < ns; ++s) fclose(check_nk_header(fns[s], nk));  // load_eachBinGT's assertion, once per file and before anything is written
     FILE* fo[2] = {fopen(foutRaw.c_str(), "wb"), fopen(fout.c_str(), "wb")};
     const std::string* fon[2] = {&foutRaw, &fout};
     for (int i = 0; i < 2; ++i) {
@@ -228,13 +234,7 @@ int main(int argc, char** argv) {
     const uint64_t nk = dbtk_pred_nk(P), ntr = dbtk_pred_ntr(P);
     printf("%llu loci in total.\n", (unsigned long long)ntr);
     printf("reading %llu gt files\n", (unsigned long long)ns);
-    const uint64_t B = 16;  // samples per transfer
-    std::vector<uint64_t> buf(B * nk);
-    for (uint64_t s0 = 0; s0 < ns; s0 += B) {
-        const uint64_t n = std::min<uint64_t>(B, ns - s0);
-        for (uint64_t i = 0; i < n; ++i) read_counts(fns[s0 + i], nk, buf.data() + i * nk);
-        if (dbtk_pred_load_samples(P, s0, n, buf.data(), rds.data() + s0)) die(dbtk_last_error());
-    }
+    load_batches(fns, rds, nk, [&](uint64_t s0, uint64_t n, const uint64_t* counts, const float* depths) { return dbtk_pred_load_samples(P, s0, n, counts, depths); });
     std::vector<float> mat(ns * nk);
     printf("normalizaing read depth\n");
     if (dbtk_pred_matrix(P, mat.data())) die(dbtk_last_error());
