@@ -671,6 +671,89 @@ class Dosage:
             self.h = None
 
 
+EXPORTS_KCP = [
+    "dbtk_kcp_api_version", "dbtk_kcp_create", "dbtk_kcp_free", "dbtk_kcp_add", "dbtk_kcp_count", "dbtk_kcp_read", "dbtk_kcp_write", "dbtk_kcp_reset",
+    "dbtk_kcp_stats", "dbtk_kcp_times",
+]
+
+
+class Kcp:
+    """The bait k-mer count profile table of include/dbtk_kcp.h through ctypes: per (assigned locus, canonical k-mer) and class
+    (0: true positives, 1: false positives) the exact n, sum, sum of squares, min and max of the k-mer's per-read count."""
+
+    def __init__(self, lib, ksize, nloci, device=0, tp_only=False):
+        self._lib = lib
+        L = lib.L
+        dp = C.POINTER(C.c_double)
+        L.dbtk_kcp_api_version.restype = C.c_uint32
+        L.dbtk_kcp_api_version.argtypes = []
+        L.dbtk_kcp_create.argtypes = [C.c_uint32, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.dbtk_kcp_free.argtypes = [C.c_void_p]
+        L.dbtk_kcp_free.restype = None
+        L.dbtk_kcp_add.argtypes = [C.c_void_p, u8p, u64p, C.c_uint64, u32p, u32p]
+        L.dbtk_kcp_count.argtypes = [C.c_void_p, C.c_uint32, u64p]
+        L.dbtk_kcp_read.argtypes = [C.c_void_p, C.c_uint32, u32p, u64p, u32p, u64p, u64p, u32p, u32p, C.c_uint64]
+        L.dbtk_kcp_write.argtypes = [C.c_void_p, C.c_char_p]
+        L.dbtk_kcp_reset.argtypes = [C.c_void_p]
+        L.dbtk_kcp_stats.argtypes = [C.c_void_p, u64p, u64p, u64p]
+        L.dbtk_kcp_times.argtypes = [C.c_void_p, dp, u64p]
+        if L.dbtk_kcp_api_version() != abi.KCP_API_VERSION:
+            raise RuntimeError("libdbtk_hip.so: dbtk_kcp.h version mismatch")
+        self.h = C.c_void_p()
+        lib._chk(L.dbtk_kcp_create(int(ksize), int(nloci), int(device), abi.KCP_TP_ONLY if tp_only else 0, C.byref(self.h)))
+
+    def add(self, seq, off, src, dst):
+        """seq / off as for Context.align (reads 2p, 2p + 1 = pair p); src / dst: one locus each per pair."""
+        seq = np.ascontiguousarray(seq, np.uint8)
+        off = np.ascontiguousarray(off, np.uint64)
+        src = np.ascontiguousarray(src, np.uint32)
+        dst = np.ascontiguousarray(dst, np.uint32)
+        npairs = (len(off) - 1) // 2
+        if len(src) != npairs or len(dst) != npairs:
+            raise ValueError("one src and one dst per pair")
+        self._lib._chk(self._lib.L.dbtk_kcp_add(self.h, _ptr(seq, u8p), _ptr(off, u64p), npairs, _ptr(src, u32p), _ptr(dst, u32p)))
+
+    def count(self, cls):
+        n = C.c_uint64()
+        self._lib._chk(self._lib.L.dbtk_kcp_count(self.h, int(cls), C.byref(n)))
+        return int(n.value)
+
+    def read(self, cls):
+        """{(locus, kmer): (n, sum, sumsq, min, max)} of the class; the library returns the entries sorted by (locus, k-mer)."""
+        cap = self.count(cls)
+        loci, n, mn, mx = (np.empty(cap, np.uint32) for _ in range(4))
+        kmers, sm, sq = (np.empty(cap, np.uint64) for _ in range(3))
+        self._lib._chk(self._lib.L.dbtk_kcp_read(self.h, int(cls), _ptr(loci, u32p), _ptr(kmers, u64p), _ptr(n, u32p), _ptr(sm, u64p), _ptr(sq, u64p), _ptr(mn, u32p),
+                                                 _ptr(mx, u32p), cap))
+        keys = list(zip(loci.tolist(), kmers.tolist()))
+        if keys != sorted(keys):
+            raise RuntimeError("dbtk_kcp_read: entries out of order")
+        return dict(zip(keys, zip(n.tolist(), sm.tolist(), sq.tolist(), mn.tolist(), mx.tolist())))
+
+    def write(self, prefix):
+        self._lib._chk(self._lib.L.dbtk_kcp_write(self.h, os.fsencode(prefix)))
+
+    def reset(self):
+        self._lib._chk(self._lib.L.dbtk_kcp_reset(self.h))
+
+    def stats(self):
+        """(table bytes, slots, slots taken)"""
+        b, s, o = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._lib._chk(self._lib.L.dbtk_kcp_stats(self.h, C.byref(b), C.byref(s), C.byref(o)))
+        return int(b.value), int(s.value), int(o.value)
+
+    def times(self):
+        """(milliseconds in the add kernel, first occurrences inserted)"""
+        ms, n = C.c_double(), C.c_uint64()
+        self._lib._chk(self._lib.L.dbtk_kcp_times(self.h, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
+
+    def close(self):
+        if self.h:
+            self._lib.L.dbtk_kcp_free(self.h)
+            self.h = None
+
+
 class Synth:
     """Seeded release-scale workload generator (csrc/dbtk_synth.cpp): a flat
     RPGG + 150 bp read pairs, for bench.py and the scale tests."""

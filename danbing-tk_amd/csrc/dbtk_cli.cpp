@@ -46,6 +46,7 @@
 
 #include "../../include/dbtk.h"
 #include "../../include/dbtk_pred.h"
+#include "../../include/dbtk_kcp.h"
 #include "dbtk_pred_io.h"
 
 namespace {
@@ -103,6 +104,8 @@ struct Opts {
     std::vector<std::string> pred;     // --pred IKMER.META RAW.gt CORRECTED.gt BIAS.tsv
     std::string kms;                   // --kms OUT.kms: the per-locus k-mer sums of every sample (the table of `ktools sum -f`)
     std::vector<std::string> dosage;   // --dosage IKMER.META OUT.dosage.tsv OUT.bias.tsv: the bias-corrected per-locus dosages, without the matrix
+    std::string baitProfile;           // --bait-profile OUTPREF: the k-mer count profiles of the assigned pairs (-s), counted in a table in HBM
+    bool tpOnly = false;               // --tp-only: the true-positive profile alone (baitBuilder's -tp)
 };
 struct CohortSample { std::string reads, prefix; float depth = 0; };
 
@@ -126,6 +129,11 @@ void usage() {
             "  -bu                    write read (k+1)-mers absent from the graph\n"
             "  --bu-table             with -bu: count them in a table in HBM (no host step per batch; OUT.bub.kmdb then holds every locus'\n"
             "                         entries in ascending order of the edge: the same set, a defined order).  With --cohort: PREFIX.bub.kmdb per sample\n"
+            "  --bait-profile <PREF>  with -s 1|2: per (assigned locus, k-mer) the min / max / mean / sd of the k-mer's count per read, counted\n"
+            "                         in a table in HBM from the pairs the kam records name: PREF.TP_pf.txt (source locus == assigned locus) and\n"
+            "                         PREF.FP_pf.txt, what `baitBuilder v1.pf` makes from the kam text (input of `ktools fps`).  With -ka no kam\n"
+            "                         text is written at all.  One GPU, host reader; not with --cohort, -e, -g/-gc/-gcc, --ingest-shards\n"
+            "  --tp-only              with --bait-profile: PREF.TP_pf.txt alone\n"
             "Algorithm:\n"
             "  -k <INT> [21]  -kf <N> <M> [4 1]  -cth <INT> [10]  -c <INT> [40]  -qth <INT> [20]  -qc <FILE>  -b [FILE]\n"
             "Execution:\n"
@@ -398,6 +406,8 @@ int main(int argc, char* argv[]) {
         else if (a == "--cohort-names") o.cohortNames = true;
         else if (a == "--no-trkmc") o.noTrkmc = true;
         else if (a == "--bu-table") o.buTable = true;
+        else if (a == "--bait-profile") o.baitProfile = need(++argi);
+        else if (a == "--tp-only") o.tpOnly = true;
         else if (a == "--pred") { o.pred.clear(); for (int i = 0; i < 4; ++i) o.pred.push_back(need(++argi)); }
         else if (a == "--kms") o.kms = need(++argi);
         else if (a == "--dosage") { o.dosage.clear(); for (int i = 0; i < 3; ++i) o.dosage.push_back(need(++argi)); }
@@ -414,6 +424,18 @@ int main(int argc, char* argv[]) {
     const bool cohort = !o.cohortFn.empty();
     std::vector<CohortSample> samples;
     if (o.buTable && !o.outputBubbles) refuse("--bu-table needs -bu");
+    // --bait-profile: the pairs it counts are those of the kam records of -s, on the one pipeline that makes them
+    const bool profile = !o.baitProfile.empty();
+    if (o.tpOnly && !profile) refuse("--tp-only needs --bait-profile");
+    if (profile) {
+        if (o.simmode != 1 && o.simmode != 2) refuse("--bait-profile needs -s 1 or -s 2: the titles of simulated reads carry the source locus that tells true from false positives");
+        if (cohort) refuse("--bait-profile cannot be combined with --cohort");
+        if (o.extractFastX) refuse("--bait-profile cannot be combined with -e");
+        if (o.threading) refuse("--bait-profile cannot be combined with -g/-gc/-gcc (no pair is assigned behind the threading gate)");
+        if (o.ngpus > 1) refuse("--bait-profile runs on one GPU: --gpus > 1 is not supported with it (the tables of several contexts are not merged)");
+        if (o.ingestShards > 0) refuse("--bait-profile cannot be combined with --ingest-shards");
+        if (o.parseOnly) refuse("--bait-profile cannot be combined with --parse-only");
+    }
     if (o.buTable && (o.extractFastX || o.threading)) refuse("--bu-table: with -e or -g/-gc/-gcc -bu does nothing (novel edges are counted on the assignment path only)");
     // (cohort mode has no place for the event log's host replay after every batch: -bu there is the table's, and is asked for as such)
     if (cohort && o.outputBubbles && !o.buTable) refuse("--cohort cannot be combined with -bu alone: add --bu-table (the novel edges are then counted in a table in HBM, and PREFIX.bub.kmdb holds every locus' entries in ascending order of the edge)");
@@ -615,7 +637,8 @@ int main(int argc, char* argv[]) {
     P.ksize = (uint32_t)o.ksize; P.n_filter = (uint32_t)o.N_FILTER; P.nm_filter = (uint32_t)o.NM_FILTER;
     P.cthreshold = (uint32_t)(uint16_t)o.Cthreshold;  // uint16_t in the reference (AQ.cpp:1765)
     P.nm_tr = (uint32_t)o.NM_TR; P.max_nt = (uint32_t)o.MAX_NT; P.qth = (uint32_t)o.qth;
-    P.okam = o.okam; P.qc = o.qc; P.extract = (uint32_t)o.extractFastX; P.simmode = (uint32_t)o.simmode;
+    P.okam = o.okam || profile;  // (--bait-profile -ka: the records are made and counted, never printed)
+    P.qc = o.qc; P.extract = (uint32_t)o.extractFastX; P.simmode = (uint32_t)o.simmode;
     P.threading = walk ? DBTK_THREADING_V13 : (o.threading ? DBTK_THREADING_HEAD : 0);
     P.thread_cth = (uint32_t)o.thread_cth; P.maxncorrection = (uint32_t)o.maxncorrection;
     P.correction = o.correction;
@@ -736,7 +759,13 @@ int main(int argc, char* argv[]) {
     const uint64_t minReadSize = (uint16_t)o.Cthreshold + o.ksize - 1;
     // (with -g / -gc no pair record is ever produced — at HEAD nothing happens behind the threading gate, AQ.cpp:2070-2090; under the v1.3
     // contract the walk counts exactly and prints alignments, not kam lines — so no record buffer travels and the blocks take the record-free path)
-    const bool want_recs = !o.threading && (o.okam || o.extractFastX);
+    const bool want_recs = !o.threading && (o.okam || o.extractFastX || profile);
+    // --bait-profile: the table, and per batch the reads of the assigned pairs in the layout of dbtk_align_batch
+    dbtk_kcp_t* kcp = nullptr;
+    if (profile && dbtk_kcp_create((uint32_t)o.ksize, nloci, dev_of(0), o.tpOnly ? DBTK_KCP_TP_ONLY : 0u, &kcp)) die_assert(std::string("--bait-profile: ") + dbtk_last_error());
+    struct { std::vector<uint8_t> seq; std::vector<uint64_t> off; std::vector<uint32_t> src, dst; } kb;
+    kb.off.assign(1, 0);
+    double kcp_host_s = 0;
     bool fq = o.isFastq;  // (cohort mode: per sample)
     time1 = time(nullptr);
     fprintf(stderr, "threads created\n");
@@ -880,6 +909,15 @@ int main(int argc, char* argv[]) {
             const uint64_t src = o.simmode ? b.src[p] : ~0ull;
             const bool src_ok = src != nloci && src != ~0ull;
             if (!(src_ok || r.dst != nloci)) continue;  // AQ.cpp:2169
+            if (kcp && r.dst != nloci) {  // what baitBuilder v1.pf takes from this line: src, dst and both reads (bait.cpp:393-403)
+                for (int which = 1; which >= 0; --which) {
+                    const Batch::Span x = b.seq_s(2 * p + which);
+                    kb.seq.insert(kb.seq.end(), x.first, x.first + x.second);
+                    kb.off.push_back(kb.seq.size());
+                }
+                kb.src.push_back((uint32_t)std::min<uint64_t>(src, 0xFFFFFFFFull)); kb.dst.push_back(r.dst);
+            }
+            if (!o.okam) continue;
             out += (src == ~0ull ? std::string(".") : std::to_string((int)src)); out += '\t';
             out += std::to_string(r.dst); out += '\t';
             out += std::to_string(r.dst != r.dst0 ? (int)r.dst0 : -1); out += '\t';
@@ -897,6 +935,13 @@ int main(int argc, char* argv[]) {
             out += fq ? qual(2 * p) : std::string("."); out += '\n';
         }
         if (!out.empty()) { std::lock_guard<std::mutex> lk(out_m); fwrite(out.data(), 1, out.size(), stdout); }
+        if (kcp && !kb.dst.empty()) {
+            const double tk0 = wall();
+            kb.seq.push_back(0);
+            if (dbtk_kcp_add(kcp, kb.seq.data(), kb.off.data(), kb.dst.size(), kb.src.data(), kb.dst.data())) die_assert(std::string("--bait-profile: ") + dbtk_last_error());
+            kb.seq.clear(); kb.off.assign(1, 0); kb.src.clear(); kb.dst.clear();
+            kcp_host_s += wall() - tk0;
+        }
         fprintf(stderr, "Batch query in %ld sec. %llu pairs, %llu records\n", b.gpu_sec, (unsigned long long)(b.nreads / 2), (unsigned long long)b.nrec);
     };
     // --parse-only: what the pairing stage handed on (pairs, bases, order-independent digest)
@@ -2017,6 +2062,19 @@ int main(int argc, char* argv[]) {
                 fwrite(&zero, 8, 1, f); fwrite(&szv, 8, 1, f);
                 fclose(f);
             }
+            if (kcp) {
+                fprintf(stderr, "writing k-mer count profiles...\n");
+                const double tw0 = wall();
+                if (dbtk_kcp_write(kcp, o.baitProfile.c_str())) die_assert(std::string("--bait-profile: ") + dbtk_last_error());
+                if (getenv("DBTK_VERBOSE")) fprintf(stderr, "bait profile: compacted, sorted and written in %.3f s\n", wall() - tw0);
+                if (getenv("DBTK_VERBOSE")) {  // (tools/kcp_bench.py)
+                    uint64_t bytes = 0, slots = 0, occ = 0, ins = 0;
+                    double ms = 0;
+                    if (dbtk_kcp_stats(kcp, &bytes, &slots, &occ) || dbtk_kcp_times(kcp, &ms, &ins)) die_assert(dbtk_last_error());
+                    fprintf(stderr, "bait profile: %llu entries in %llu slots, %llu bytes; %llu inserts in %.3f ms of the add kernel; %.3f s in dbtk_kcp_add\n", (unsigned long long)occ,
+                            (unsigned long long)slots, (unsigned long long)bytes, (unsigned long long)ins, ms, kcp_host_s);
+                }
+            }
             if (o.outputBubbles) {  // dumpBubbles, AQ.cpp:2648-2651
                 fprintf(stderr, "writing bubbles...\n");
                 if (P.bubbles) {
@@ -2055,6 +2113,7 @@ int main(int argc, char* argv[]) {
         if (pred) dbtk_pred_free(pred);
         dbtk_dosage_free(dosage);
         dbtk_dosage_free(kms);
+        dbtk_kcp_free(kcp);
         for (auto c : ctx) dbtk_ctx_free(c);
         dbtk_rpgg_free(rpgg);
     }
