@@ -673,7 +673,7 @@ class Dosage:
 
 EXPORTS_KCP = [
     "dbtk_kcp_api_version", "dbtk_kcp_create", "dbtk_kcp_free", "dbtk_kcp_add", "dbtk_kcp_count", "dbtk_kcp_read", "dbtk_kcp_write", "dbtk_kcp_reset",
-    "dbtk_kcp_stats", "dbtk_kcp_times",
+    "dbtk_kcp_stats", "dbtk_kcp_times", "dbtk_kcp_add_device",
 ]
 
 
@@ -691,6 +691,7 @@ class Kcp:
         L.dbtk_kcp_free.argtypes = [C.c_void_p]
         L.dbtk_kcp_free.restype = None
         L.dbtk_kcp_add.argtypes = [C.c_void_p, u8p, u64p, C.c_uint64, u32p, u32p]
+        L.dbtk_kcp_add_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, u32p]
         L.dbtk_kcp_count.argtypes = [C.c_void_p, C.c_uint32, u64p]
         L.dbtk_kcp_read.argtypes = [C.c_void_p, C.c_uint32, u32p, u64p, u32p, u64p, u64p, u32p, u32p, C.c_uint64]
         L.dbtk_kcp_write.argtypes = [C.c_void_p, C.c_char_p]
@@ -712,6 +713,13 @@ class Kcp:
         if len(src) != npairs or len(dst) != npairs:
             raise ValueError("one src and one dst per pair")
         self._lib._chk(self._lib.L.dbtk_kcp_add(self.h, _ptr(seq, u8p), _ptr(off, u64p), npairs, _ptr(src, u32p), _ptr(dst, u32p)))
+
+    def add_device(self, d_seq, d_off, npairs, d_src, dst):
+        """The same for a batch in device memory (addresses as integers); dst: one locus per pair, on the host."""
+        dst = np.ascontiguousarray(dst, np.uint32)
+        if len(dst) != npairs:
+            raise ValueError("one dst per pair")
+        self._lib._chk(self._lib.L.dbtk_kcp_add_device(self.h, d_seq, d_off, int(npairs), d_src, _ptr(dst, u32p)))
 
     def count(self, cls):
         n = C.c_uint64()
@@ -751,6 +759,105 @@ class Kcp:
     def close(self):
         if self.h:
             self._lib.L.dbtk_kcp_free(self.h)
+            self.h = None
+
+
+EXPORTS_SIM = [
+    "dbtk_sim_api_version", "dbtk_sim_open", "dbtk_sim_free", "dbtk_sim_info", "dbtk_sim_contig", "dbtk_sim_describe", "dbtk_sim_labels", "dbtk_sim_attach", "dbtk_sim_batch",
+    "dbtk_sim_batch_wait", "dbtk_sim_align", "dbtk_sim_times",
+]
+
+
+class Sim:
+    """The simulated read source of include/dbtk_sim.h through ctypes: an assembly tiled into error-free read pairs (what
+    `sim_reads -pe -no-err` prints), with the source locus of every pair from a BED.  The constructor is the host pass (no device);
+    attach() and what follows need the GPU."""
+
+    def __init__(self, lib, fasta, bed, nloci, flen=500, rlen=150, cv=15, ml=50000):
+        self._lib = lib
+        L = lib.L
+        vpp = C.POINTER(C.c_void_p)
+        L.dbtk_sim_api_version.restype = C.c_uint32
+        L.dbtk_sim_api_version.argtypes = []
+        L.dbtk_sim_open.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, vpp]
+        L.dbtk_sim_free.argtypes = [C.c_void_p]
+        L.dbtk_sim_free.restype = None
+        L.dbtk_sim_info.argtypes = [C.c_void_p, C.POINTER(abi.SimFacts)]
+        L.dbtk_sim_contig.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), vpp, u64p, u64p]
+        L.dbtk_sim_describe.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, u32p, u64p, u32p]
+        L.dbtk_sim_labels.argtypes = [C.c_void_p, C.c_uint64, u32p, C.c_uint32, u32p]
+        L.dbtk_sim_attach.argtypes = [C.c_void_p, C.c_int]
+        L.dbtk_sim_batch.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, vpp, vpp, vpp, u32p]
+        L.dbtk_sim_batch_wait.argtypes = [C.c_void_p]
+        L.dbtk_sim_align.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(abi.PairRec), C.c_uint64, u64p]
+        L.dbtk_sim_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), u64p, u64p]
+        if L.dbtk_sim_api_version() != abi.SIM_API_VERSION:
+            raise RuntimeError("libdbtk_hip.so: dbtk_sim.h version mismatch")
+        self.h = C.c_void_p()
+        lib._chk(L.dbtk_sim_open(os.fsencode(fasta), os.fsencode(bed), int(flen), int(rlen), int(cv), int(ml), int(nloci), C.byref(self.h)))
+        self.rlen = int(rlen)
+        self.npairs = 0  # of the batch made last
+
+    def info(self) -> abi.SimFacts:
+        f = abi.SimFacts()
+        self._lib._chk(self._lib.L.dbtk_sim_info(self.h, C.byref(f)))
+        return f
+
+    def contig(self, c):
+        """(header line, bases as read, number of its first fragment) of kept contig c"""
+        hdr, bases, size, first = C.c_char_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        self._lib._chk(self._lib.L.dbtk_sim_contig(self.h, int(c), C.byref(hdr), C.byref(bases), C.byref(size), C.byref(first)))
+        return hdr.value.decode(), C.string_at(bases.value, size.value) if size.value else b"", int(first.value)
+
+    def describe(self, first=0, n=None):
+        """(contig, beg, src) arrays of fragments first .. first + n - 1 (default: all)"""
+        if n is None:
+            n = int(self.info().nfrags) - first
+        ctg, src = np.empty(n, np.uint32), np.empty(n, np.uint32)
+        beg = np.empty(n, np.uint64)
+        self._lib._chk(self._lib.L.dbtk_sim_describe(self.h, int(first), int(n), _ptr(ctg, u32p), _ptr(beg, u64p), _ptr(src, u32p)))
+        return ctg, beg, src
+
+    def labels(self, frag):
+        """every locus overlapping the fragment, ascending (what distinct_sort_num writes into the title)"""
+        n = C.c_uint32()
+        self._lib._chk(self._lib.L.dbtk_sim_labels(self.h, int(frag), None, 0, C.byref(n)))
+        out = np.empty(max(n.value, 1), np.uint32)
+        self._lib._chk(self._lib.L.dbtk_sim_labels(self.h, int(frag), _ptr(out, u32p), n.value, C.byref(n)))
+        return out[:n.value].tolist()
+
+    def attach(self, device=0):
+        self._lib._chk(self._lib.L.dbtk_sim_attach(self.h, int(device)))
+
+    def batch(self, first, npairs):
+        """Tiles the pairs into the next buffer set; returns the device addresses (d_seq, d_offsets, d_src) as integers."""
+        seq, off, src = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        mx = C.c_uint32()
+        self._lib._chk(self._lib.L.dbtk_sim_batch(self.h, int(first), int(npairs), C.byref(seq), C.byref(off), C.byref(src), C.byref(mx)))
+        self.npairs = int(npairs)
+        return seq.value, off.value, src.value
+
+    def wait(self):
+        self._lib._chk(self._lib.L.dbtk_sim_batch_wait(self.h))
+
+    def align(self, ctx, sync=True):
+        """The batch made last through ctx's hot path; with sync the records (ctypes array, pair order) and their number."""
+        p = ctx.params
+        want = sync and bool(p.trace or p.okam or p.extract)
+        recs = (abi.PairRec * max(self.npairs, 1))() if want else None
+        nrec = C.c_uint64(0)
+        self._lib._chk(self._lib.L.dbtk_sim_align(self.h, ctx.h, 1 if sync else 0, recs, self.npairs if want else 0, C.byref(nrec)))
+        return recs, int(nrec.value)
+
+    def times(self):
+        """(milliseconds in k_sim_tile, bytes of reads written, bytes of arena uploaded)"""
+        ms, b, u = C.c_double(), C.c_uint64(), C.c_uint64()
+        self._lib._chk(self._lib.L.dbtk_sim_times(self.h, C.byref(ms), C.byref(b), C.byref(u)))
+        return float(ms.value), int(b.value), int(u.value)
+
+    def close(self):
+        if self.h:
+            self._lib.L.dbtk_sim_free(self.h)
             self.h = None
 
 
@@ -812,6 +919,17 @@ class Synth:
         self.L.dbtk_synth_reads_loci(self.h, npairs, first_pair, rlen, _ptr(loci, C.POINTER(C.c_uint32)), len(loci), float(odd_frac), seed, _ptr(out, u8p), nthreads)
         off = np.arange(2 * npairs + 1, dtype=np.uint64) * np.uint64(rlen)
         return out, off
+
+    def sequences(self):
+        """(seq, hap_beg, locus_hap0) as numpy views of the generator's memory: haplotype j of locus l (flank + TR + flank) is
+        seq[hap_beg[locus_hap0[l] + j]:hap_beg[locus_hap0[l] + j + 1]]"""
+        self.L.dbtk_synth_sequences.argtypes = [C.c_void_p, C.POINTER(u8p), C.POINTER(u64p), C.POINTER(u32p)]
+        self.L.dbtk_synth_sequences.restype = None
+        seq, hb, lh = u8p(), u64p(), u32p()
+        self.L.dbtk_synth_sequences(self.h, C.byref(seq), C.byref(hb), C.byref(lh))
+        lh = np.ctypeslib.as_array(lh, (self.nloci + 1,))
+        hb = np.ctypeslib.as_array(hb, (int(lh[-1]) + 1,))
+        return np.ctypeslib.as_array(seq, (int(self.L.dbtk_synth_nbases(self.h)),)), hb, lh
 
     def close(self):
         if self.h:

@@ -7,6 +7,7 @@ NAN32 = 0xFFFFFFFF
 ABI_VERSION = 11
 KCP_API_VERSION = 1  # include/dbtk_kcp.h: DBTK_KCP_API_VERSION (a version of its own beside ABI_VERSION)
 KCP_TP_ONLY = 1      # dbtk_kcp_create flags
+SIM_API_VERSION = 1  # include/dbtk_sim.h: DBTK_SIM_API_VERSION
 BUBBLES_LOG, BUBBLES_TABLE = 1, 2  # params.bubbles: event log replayed on the host (reference order) | counts in a device table
 ALN_TEXT = 4  # params.aln | ALN_TEXT: alignment records in text form (dbtk_ctx_aln_text)
 THREAD_CAP = 384
@@ -102,3 +103,9 @@ class IngestInfo(C.Structure):
 class IngestSpan(C.Structure):
     _fields_ = [("title", C.c_uint32), ("title_len", C.c_uint32), ("seq", C.c_uint32 * 2), ("seq_len", C.c_uint32 * 2),
                 ("qual", C.c_uint32 * 2), ("qual_len", C.c_uint32 * 2)]
+
+
+class SimFacts(C.Structure):
+    """include/dbtk_sim.h: dbtk_sim_facts_t"""
+    _fields_ = [(n, C.c_uint64) for n in ("ncontigs", "nskipped", "nfrags", "arena_bytes", "nbreaks")] + \
+               [(n, C.c_uint32) for n in ("flen", "rlen", "shft", "ngroups")]

@@ -47,6 +47,7 @@
 #include "../../include/dbtk.h"
 #include "../../include/dbtk_pred.h"
 #include "../../include/dbtk_kcp.h"
+#include "../../include/dbtk_sim.h"
 #include "dbtk_pred_io.h"
 
 namespace {
@@ -106,6 +107,10 @@ struct Opts {
     std::vector<std::string> dosage;   // --dosage IKMER.META OUT.dosage.tsv OUT.bias.tsv: the bias-corrected per-locus dosages, without the matrix
     std::string baitProfile;           // --bait-profile OUTPREF: the k-mer count profiles of the assigned pairs (-s), counted in a table in HBM
     bool tpOnly = false;               // --tp-only: the true-positive profile alone (baitBuilder's -tp)
+    // --sim ASSEMBLY BED (any number of times): the reads are tiled from the assemblies on the device, sim_reads -pe -no-err's
+    std::vector<std::pair<std::string, std::string>> sim;
+    uint64_t simFs = 500, simRlen = 150, simC = 15, simMl = 50000;  // --sim-fs / --sim-rlen / --sim-c / --sim-ml
+    std::string simParam;              // the first --sim-* flag given (they need --sim)
 };
 struct CohortSample { std::string reads, prefix; float depth = 0; };
 
@@ -122,6 +127,13 @@ void usage() {
             "  (MI355X build: the alignment hot path runs on the GPU through libdbtk_hip.so)\n"
             "Input:\n"
             "  -fa <STR> | -fq <STR>  paired reads as FASTA | FASTQ (e.g. samtools fasta/fastq -n); mates are paired on the fly\n"
+            "  --sim <FASTA> <BED>    in place of -fa/-fq: tile every contig of the assembly FASTA into error-free read pairs on the GPU, byte for\n"
+            "                         byte what `sim_reads -pe -no-err` prints, each pair's source locus taken from BED (CTG START END LOCUS,\n"
+            "                         0-based, half-open: the lowest LOCUS overlapping the fragment); implies -s 2; may be given several times\n"
+            "                         (the assemblies are tiled in that order).  One GPU; not with -s 1, -e, -a/-ae, -g/-gc/-gcc, -tb, -bu, --cohort,\n"
+            "                         --ingest-shards\n"
+            "  --sim-fs <INT> [500]  --sim-rlen <INT> [150]  --sim-c <INT> [15]  --sim-ml <INT> [50000]\n"
+            "                         with --sim: fragment size, read length, coverage (step = 2 * rlen / c) and the shortest contig tiled\n"
             "  -qs <STR>              prefix of the RPGG files (PREF.tr.kmers, PREF.kmers.dbi, PREF.fl.kdb, PREF.tre.kdb)\n"
             "Output:\n"
             "  -o <STR> | -on <STR>   output prefix (OUT.trkmc.ar + OUT.tr.summary.txt | OUT.tr.kmers with names)\n"
@@ -408,6 +420,12 @@ int main(int argc, char* argv[]) {
         else if (a == "--bu-table") o.buTable = true;
         else if (a == "--bait-profile") o.baitProfile = need(++argi);
         else if (a == "--tp-only") o.tpOnly = true;
+        else if (a == "--sim") { const std::string fa = need(++argi); o.sim.emplace_back(fa, need(++argi)); }
+        else if (a == "--sim-fs" || a == "--sim-rlen" || a == "--sim-c" || a == "--sim-ml") {
+            if (o.simParam.empty()) o.simParam = a;
+            const uint64_t v = strtoull(need(++argi).c_str(), nullptr, 10);
+            (a == "--sim-fs" ? o.simFs : a == "--sim-rlen" ? o.simRlen : a == "--sim-c" ? o.simC : o.simMl) = v;
+        }
         else if (a == "--pred") { o.pred.clear(); for (int i = 0; i < 4; ++i) o.pred.push_back(need(++argi)); }
         else if (a == "--kms") o.kms = need(++argi);
         else if (a == "--dosage") { o.dosage.clear(); for (int i = 0; i < 3; ++i) o.dosage.push_back(need(++argi)); }
@@ -420,6 +438,32 @@ int main(int argc, char* argv[]) {
     // (`danbing-tk -gc 85 3 -ae ...`, README.md:38-39) then runs unchanged
     if (const char* e = getenv("DBTK_V13_THREADING")) if (atoi(e) != 0) o.v13 = true;
 
+    // ---- --sim: what it refuses — before the GPU is asked for anything
+    const bool sim = !o.sim.empty();
+    if (!sim && !o.simParam.empty()) refuse(o.simParam + " needs --sim");
+    if (sim) {
+        if (!o.fastxFname.empty()) refuse("--sim takes the place of -fa/-fq: the reads are tiled from the assembly");
+        if (o.simmode == 1) refuse("--sim cannot be combined with -s 1: its pairs carry the source locus of -s 2 titles (>CTG:BEG-END:LOCUS)");
+        if (o.extractFastX) refuse("--sim cannot be combined with -e (the pre-filter it stood for is not needed: no file is written)");
+        if (o.aln) refuse("--sim cannot be combined with -a/-ae");
+        if (o.threading) refuse("--sim cannot be combined with -g/-gc/-gcc");
+        if (o.trackBait) refuse("--sim cannot be combined with -tb (its replay needs the reads in host buffers)");
+        if (o.outputBubbles) refuse("--sim cannot be combined with -bu");
+        if (!o.cohortFn.empty()) refuse("--sim cannot be combined with --cohort");
+        if (o.ngpus > 1) refuse("--sim runs on one GPU: --gpus > 1 is not supported with it");
+        if (o.ingestShards > 0) refuse("--sim cannot be combined with --ingest-shards (there is no file to cut)");
+        if (o.parseOnly) refuse("--sim cannot be combined with --parse-only");
+        if (o.simRlen == 0 || o.simRlen >= o.simFs) refuse("--sim: the read length (--sim-rlen " + std::to_string(o.simRlen) + ") must be at least 1 and below the fragment size (--sim-fs " + std::to_string(o.simFs) + ")");
+        if (o.simRlen > DBTK_MAX_READ_LEN) refuse("--sim: --sim-rlen " + std::to_string(o.simRlen) + " exceeds the longest read the aligner takes (" + std::to_string(DBTK_MAX_READ_LEN) + ")");
+        if (o.simC == 0 || o.simC > 2 * o.simRlen) refuse("--sim: --sim-c must be 1 .. 2 * --sim-rlen (the step 2 * " + std::to_string(o.simRlen) + " / " + std::to_string(o.simC) + " would be 0)");
+        if (o.simFs > 0xFFFFFFFFull) refuse("--sim: --sim-fs does not fit 32 bits");
+        if (o.simRlen < (uint64_t)(uint16_t)o.Cthreshold + o.ksize - 1)
+            refuse("--sim: reads of " + std::to_string(o.simRlen) + " bases are shorter than -cth + -k - 1 = " + std::to_string((uint64_t)(uint16_t)o.Cthreshold + o.ksize - 1) + ": the reader drops every such pair");
+        for (auto& fb : o.sim)
+            for (const std::string* fn : {&fb.first, &fb.second})
+                if (!readable(*fn)) refuse("--sim: cannot open " + *fn);
+        o.simmode = 2;
+    }
     // ---- cohort mode: what it refuses, and its manifest — all of it before the GPU is asked for anything
     const bool cohort = !o.cohortFn.empty();
     std::vector<CohortSample> samples;
@@ -629,6 +673,23 @@ int main(int argc, char* argv[]) {
         if (dbtk_rpgg_set_index_cache(rpgg, (cp + ".dbtk.idx").c_str(), 2)) die_assert(dbtk_last_error());
     }
     fprintf(stderr, "total number of loci in %s: %llu\n", o.trFname.c_str(), (unsigned long long)nloci);
+    // --sim: the host pass over every assembly and its BED (contig table, source-locus step functions); a file that does not parse ends the run here
+    std::vector<dbtk_sim_t*> sims;
+    double sim_open_s = 0;
+    for (auto& fb : o.sim) {
+        timespec t0, t1;
+        clock_gettime(CLOCK_MONOTONIC, &t0);
+        dbtk_sim_t* sm = nullptr;
+        if (dbtk_sim_open(fb.first.c_str(), fb.second.c_str(), (uint32_t)o.simFs, (uint32_t)o.simRlen, (uint32_t)o.simC, o.simMl, nloci, &sm)) refuse(std::string("--sim: ") + dbtk_last_error());
+        clock_gettime(CLOCK_MONOTONIC, &t1);
+        sim_open_s += (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec);
+        dbtk_sim_facts_t sf;
+        dbtk_sim_info(sm, &sf);
+        fprintf(stderr, "--sim %s: %llu contigs kept (%llu skipped), %llu bases, %llu pairs, %llu source-locus breakpoints\n", fb.first.c_str(), (unsigned long long)sf.ncontigs,
+                (unsigned long long)sf.nskipped, (unsigned long long)sf.arena_bytes, (unsigned long long)sf.nfrags, (unsigned long long)sf.nbreaks);
+        sims.push_back(sm);
+    }
+    if (sim) fprintf(stderr, "--sim: assemblies and BED files read in %.2f s\n", sim_open_s);
     fprintf(stderr, "deserialized graph/index and read tr.kmers in %ld sec.\n# unique kmers in kmerDBi: %llu\n", (long)(time(nullptr) - time1),
             (unsigned long long)dbtk_rpgg_nkeys(rpgg));
 
@@ -909,7 +970,7 @@ int main(int argc, char* argv[]) {
             const uint64_t src = o.simmode ? b.src[p] : ~0ull;
             const bool src_ok = src != nloci && src != ~0ull;
             if (!(src_ok || r.dst != nloci)) continue;  // AQ.cpp:2169
-            if (kcp && r.dst != nloci) {  // what baitBuilder v1.pf takes from this line: src, dst and both reads (bait.cpp:393-403)
+            if (kcp && !sim && r.dst != nloci) {  // what baitBuilder v1.pf takes from this line: src, dst and both reads (bait.cpp:393-403)
                 for (int which = 1; which >= 0; --which) {
                     const Batch::Span x = b.seq_s(2 * p + which);
                     kb.seq.insert(kb.seq.end(), x.first, x.first + x.second);
@@ -1822,6 +1883,105 @@ int main(int argc, char* argv[]) {
             fprintf(stderr, "cross-range pairing: %llu reads\n", (unsigned long long)nleft);
         }
     };  // run_input
+    // --sim: no file and no reader.  The assembly goes to HBM once (in groups of contigs where it is larger than the arena) and a kernel
+    // tiles it into the batch layout with every pair's source locus beside it (include/dbtk_sim.h).  Without records (-ka alone) the
+    // batches go through asynchronously, one being tiled while the one before is aligned; with records a batch runs to completion and
+    // the host formats titles and reads, for the pairs that have a record only, from its own copy of the contigs: no read comes back
+    // from the device, and the profile of --bait-profile is fed from the batch where it lies.
+    auto run_sim = [&] {
+        uint64_t BP = std::max<uint64_t>(1ull << 20, 24 * nloci);  // (the merged batch of the device reader)
+        if (const char* e = getenv("DBTK_SIM_BATCH_PAIRS")) { const long long v = atoll(e); if (v > 0) BP = (uint64_t)v; }  // (tests: many small batches)
+        Batch b;
+        std::vector<uint32_t> dstv, lab(64);
+        double tile_ms = 0, kcp_s = 0, fmt_s = 0;
+        uint64_t tile_bytes = 0, up_bytes = 0;
+        auto revcomp_up = [](const uint8_t* p, uint64_t n, std::string& out) {
+            out.resize(n);
+            for (uint64_t i = 0; i < n; ++i) {
+                const char c = (char)(p[n - 1 - i] & 0xDF);
+                out[i] = c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : 'N';
+            }
+        };
+        std::string r1, r2, title;
+        for (dbtk_sim_t* S : sims) {
+            if (dbtk_sim_attach(S, dev_of(0))) die_assert(std::string("--sim: ") + dbtk_last_error());
+            dbtk_sim_facts_t sf;
+            if (dbtk_sim_info(S, &sf)) die_assert(dbtk_last_error());
+            for (uint64_t f0 = 0; f0 < sf.nfrags; f0 += BP) {
+                const uint64_t n = std::min<uint64_t>(BP, sf.nfrags - f0);
+                const time_t t2 = time(nullptr);
+                const double tg = now();
+                void *d_seq = nullptr, *d_off = nullptr, *d_src = nullptr;
+                if (dbtk_sim_batch(S, f0, n, &d_seq, &d_off, &d_src, nullptr)) die_assert(std::string("--sim: ") + dbtk_last_error());
+                nReads += 2 * n;
+                fprintf(stderr, "Buffered reading %llu\t%llu\t%d\n", 2 * (unsigned long long)n, (unsigned long long)nReads, 0);
+                if (!want_recs) {
+                    if (dbtk_sim_align(S, ctx[0], 0, nullptr, 0, nullptr)) die_assert(std::string("align: ") + dbtk_last_error());
+                    gpu_busy += now() - tg;
+                    continue;
+                }
+                b.recs.resize(n);
+                if (dbtk_sim_align(S, ctx[0], 1, b.recs.data(), n, &b.nrec)) die_assert(std::string("align: ") + dbtk_last_error());
+                gpu_busy += now() - tg;
+                if (kcp) {  // the assigned pairs of the batch, counted where the batch lies (AQ.cpp:2169 / bait.cpp:393-403: the kam lines with a destination)
+                    const double tk0 = now();
+                    dstv.assign(n, (uint32_t)nloci);
+                    bool any = false;
+                    for (uint64_t i = 0; i < b.nrec; ++i) if (b.recs[i].dst != nloci) { dstv[b.recs[i].pair] = b.recs[i].dst; any = true; }
+                    if (any && dbtk_kcp_add_device(kcp, d_seq, d_off, n, d_src, dstv.data())) die_assert(std::string("--bait-profile: ") + dbtk_last_error());
+                    kcp_s += now() - tk0;
+                }
+                const double tw = now();
+                b.flat.clear(); b.off.assign(1, 0); b.tar.clear(); b.toff.assign(1, 0); b.src.clear();
+                uint64_t kept = 0;
+                for (uint64_t i = 0; o.okam && i < b.nrec; ++i) {
+                    const uint64_t fr = f0 + b.recs[i].pair;
+                    uint32_t ci = 0, src = 0, nlab = 0;
+                    uint64_t beg = 0, size = 0;
+                    if (dbtk_sim_describe(S, fr, 1, &ci, &beg, &src)) die_assert(std::string("--sim: ") + dbtk_last_error());
+                    if (src == nloci && b.recs[i].dst == nloci) continue;  // AQ.cpp:2169: no line
+                    const char* hdr = nullptr;
+                    const uint8_t* bases = nullptr;
+                    if (dbtk_sim_contig(S, ci, &hdr, &bases, &size, nullptr)) die_assert(std::string("--sim: ") + dbtk_last_error());
+                    // the title bedtools map + awk give the pair (fn1b.annot.sh): >CTG:BEG-END:LOCI, LOCI = the overlapping loci ascending, '.' for none
+                    title.assign(hdr); title += ':'; title += std::to_string(beg); title += '-'; title += std::to_string(beg + sf.flen); title += ':';
+                    for (;;) {
+                        if (dbtk_sim_labels(S, fr, lab.data(), (uint32_t)lab.size(), &nlab)) die_assert(std::string("--sim: ") + dbtk_last_error());
+                        if (nlab <= lab.size()) break;
+                        lab.resize(nlab);
+                    }
+                    if (!nlab) title += '.';
+                    for (uint32_t j = 0; j < nlab; ++j) { if (j) title += ','; title += std::to_string(lab[j]); }
+                    b.tar.insert(b.tar.end(), title.begin(), title.end()); b.toff.push_back(b.tar.size());
+                    revcomp_up(bases + beg + sf.flen - sf.rlen, sf.rlen, r2);
+                    r1.assign((const char*)bases + beg, sf.rlen);
+                    for (char& c : r1) c = (char)(c & 0xDF);
+                    b.add_read(r2.data(), r2.size(), nullptr, 0, false);  // seqs[2p]: the /2 record, as the reader delivers an interleaved file
+                    b.add_read(r1.data(), r1.size(), nullptr, 0, false);
+                    b.src.push_back(src);
+                    b.recs[kept] = b.recs[i];
+                    b.recs[kept].pair = (uint32_t)kept;
+                    ++kept;
+                }
+                b.nrec = o.okam ? kept : 0;
+                b.nreads = 2 * n;
+                b.gpu_sec = (long)(time(nullptr) - t2);
+                emit(b);
+                fmt_s += now() - tw;
+                write_busy += now() - tw;
+            }
+            double ms = 0;
+            uint64_t wb = 0, ub = 0;
+            if (dbtk_ctx_synchronize(ctx[0])) die_assert(dbtk_last_error());
+            if (dbtk_sim_times(S, &ms, &wb, &ub)) die_assert(std::string("--sim: ") + dbtk_last_error());
+            tile_ms += ms; tile_bytes += wb; up_bytes += ub;
+            dbtk_sim_free(S);  // (its arena and batch buffers: the next assembly takes their place)
+        }
+        sims.clear();
+        fprintf(stderr, "--sim: k_sim_tile wrote %llu bytes of reads in %.3f ms (%.1f GB/s); %llu bytes of assembly uploaded; profile feed %.3f s, titles and kam text %.3f s\n",
+                (unsigned long long)tile_bytes, tile_ms, tile_ms > 0 ? tile_bytes / tile_ms / 1e6 : 0.0, (unsigned long long)up_bytes, kcp_s, fmt_s);
+        kcp_host_s += kcp_s;
+    };
     // ---- cohort mode: one RPGG load, one table build, one warm-up; then per sample what a single run does from its batch loop on.
     // Two contexts alternate: while this thread reads and aligns sample i + 1 on one, the finisher thread takes sample i's counts
     // off the other — into the genotype matrix (device to device), to the host, into its files — and resets it.
@@ -1983,7 +2143,8 @@ int main(int argc, char* argv[]) {
             fprintf(stderr, "cohort: finishing the samples (pred column, counts to the host, files, reset) took %.3f s on %s; the reader waited %.3f s of it with the GPU idle (%.1f %% of the run)\n",
                     cohort_finish_s, cohort_nctx == 2 ? "the finisher thread, beside the next sample's batch loop" : "the one thread (DBTK_COHORT_CONTEXTS=1)", cohort_wait_s, 100 * cohort_wait_s / dt);
         g_cohort_drain = nullptr;
-    } else run_input();
+    } else if (sim) run_sim();
+    else run_input();
     fflush(stdout);
     const double t_tail0 = now();
     { std::lock_guard<std::mutex> l(ep_m); ep_stop = true; }

@@ -3174,3 +3174,21 @@ dbtk_status_t dbtk::ctx_facts(const dbtk_ctx_t* c, dbtk::CtxFacts* out) {
     return DBTK_OK;
 }
 
+// (dbtk_internal.h: for dbtk_sim_align)
+dbtk_status_t dbtk::ctx_align_device(dbtk_ctx_t* c, int device, const uint8_t* d_seq, const uint64_t* d_off, uint64_t npairs, uint32_t max_read_len, int sync, void* ready,
+                                     void* done, dbtk_pair_rec_t* recs, uint64_t rec_cap, uint64_t* nrec) {
+    if (!c || !d_seq || !d_off) { set_error("null argument"); return DBTK_ERR_ARG; }
+    if (c->device != device) { set_error("the context is on device " + std::to_string(c->device) + ", the batch on device " + std::to_string(device)); return DBTK_ERR_ARG; }
+    if (max_read_len > DBTK_MAX_READ_LEN) { set_error("max_read_len > DBTK_MAX_READ_LEN"); return DBTK_ERR_READ_TOO_LONG; }
+    if (((uintptr_t)d_seq & 15) != 0) { set_error("d_seq must be 16-byte aligned"); return DBTK_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    if (!sync) {
+        if (c->P.bubbles == 1) { set_error("-bu is replayed batch by batch on the host: sync = 1"); return DBTK_ERR_ARG; }
+        if (c->two_lanes) switch_lane(c);
+    }
+    if (ready) HIPCHK(hipStreamWaitEvent(c->stream, (hipEvent_t)ready, 0));
+    const dbtk_status_t st = sync ? run_batch_sync(c, d_seq, d_off, nullptr, ~0ull, npairs, max_read_len, nullptr, nullptr, nullptr, recs, rec_cap, nrec)
+                                  : launch_batch(c, d_seq, d_off, ~0ull, npairs, max_read_len, nullptr, 0);
+    if (done) HIPCHK(hipEventRecord((hipEvent_t)done, c->stream));
+    return st;
+}

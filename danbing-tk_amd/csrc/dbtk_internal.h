@@ -58,6 +58,11 @@ template <class F> dbtk_status_t guarded(F&& f) noexcept {
 // counts part of its accumulators, and the pairs appended by dbtk_ingest_align_merged (on any lane) that no batch has taken yet.
 struct CtxFacts { int device; uint64_t ntrkmers, unflushed_pairs; };
 dbtk_status_t ctx_facts(const dbtk_ctx_t* c, CtxFacts* out);
+// A batch another part of the library made in HBM on a stream of its own (dbtk_sim.hip), through the hot path of `c` (on `device`): the
+// context's stream waits for `ready` (a hipEvent_t) before its kernels and records `done` (a hipEvent_t) behind them.  sync = 0: as
+// dbtk_align_batch_device; sync = 1: as dbtk_ingest_align with sync = 1 (run to completion, records in pair order, no reads on the host).
+dbtk_status_t ctx_align_device(dbtk_ctx_t* c, int device, const uint8_t* d_seq, const uint64_t* d_off, uint64_t npairs, uint32_t max_read_len, int sync, void* ready,
+                               void* done, dbtk_pair_rec_t* recs, uint64_t rec_cap, uint64_t* nrec);
 }  // namespace dbtk
 
 #endif

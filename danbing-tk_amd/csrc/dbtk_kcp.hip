@@ -283,8 +283,11 @@ dbtk_status_t kcp_create_impl(uint32_t ksize, uint64_t nloci, int device_id, uin
     return DBTK_OK;
 }
 
-dbtk_status_t kcp_add_impl(dbtk_kcp_t* c, const uint8_t* seq, const uint64_t* off, uint64_t npairs, const uint32_t* src, const uint32_t* dst) {
-    if (!c || (npairs && (!seq || !off || !src || !dst))) { set_error("dbtk_kcp_add: null argument"); return DBTK_ERR_ARG; }
+// seq == nullptr: the reads and their offsets are in device memory already (d_seq, indexed by the offsets as they are; d_off), and
+// off / src are the host's copies of the offsets and sources (dbtk_kcp_add_device)
+dbtk_status_t kcp_add_impl(dbtk_kcp_t* c, const uint8_t* seq, const uint64_t* off, uint64_t npairs, const uint32_t* src, const uint32_t* dst, const uint8_t* d_seq = nullptr,
+                           const uint64_t* d_off = nullptr) {
+    if (!c || (npairs && ((!seq && !d_seq) || !off || !src || !dst))) { set_error("dbtk_kcp_add: null argument"); return DBTK_ERR_ARG; }
     if (npairs > 0x7FFFFFFFull) { set_error("dbtk_kcp_add: more than 2^31 - 1 pairs in one call"); return DBTK_ERR_ARG; }
     KCHK(hipSetDevice(c->device));
     {  // a failed insert of an earlier call
@@ -316,14 +319,17 @@ dbtk_status_t kcp_add_impl(dbtk_kcp_t* c, const uint8_t* seq, const uint64_t* of
         npos.push_back(np);
     }
     if (sel.empty()) return DBTK_OK;
-    const uint64_t base = off[0], nbytes = off[2 * npairs] - base;
+    const uint64_t base = seq ? off[0] : 0, nbytes = off[2 * npairs] - base;
     dbtk_status_t st;
-    if ((st = kcp_reserve(&c->d_seq, &c->seq_cap, (size_t)nbytes + 1))) return st;
-    if ((st = kcp_reserve(&c->d_off, &c->off_cap, (size_t)(2 * npairs + 1)))) return st;
+    if (seq && (st = kcp_reserve(&c->d_seq, &c->seq_cap, (size_t)nbytes + 1))) return st;
+    if (seq && (st = kcp_reserve(&c->d_off, &c->off_cap, (size_t)(2 * npairs + 1)))) return st;
     if ((st = kcp_reserve(&c->d_sel, &c->sel_cap, sel.size()))) return st;
     // (the stream is idle — kcp_words above waited for it — and these copies return when they are done)
-    KCHK(hipMemcpy(c->d_seq, seq + base, nbytes, hipMemcpyHostToDevice));
-    KCHK(hipMemcpy(c->d_off, off, sizeof(uint64_t) * (2 * npairs + 1), hipMemcpyHostToDevice));
+    if (seq) {
+        KCHK(hipMemcpy(c->d_seq, seq + base, nbytes, hipMemcpyHostToDevice));
+        KCHK(hipMemcpy(c->d_off, off, sizeof(uint64_t) * (2 * npairs + 1), hipMemcpyHostToDevice));
+        d_seq = c->d_seq; d_off = c->d_off;
+    }
     KCHK(hipMemcpy(c->d_sel, sel.data(), sizeof(KcpSel) * sel.size(), hipMemcpyHostToDevice));
     // piece by piece: room first, then the kernel
     size_t nev = 0;
@@ -343,7 +349,7 @@ dbtk_status_t kcp_add_impl(dbtk_kcp_t* c, const uint8_t* seq, const uint64_t* of
         const uint64_t w0 = 2 * (uint64_t)i, w1 = 2 * (uint64_t)j;
         const uint32_t grid = (uint32_t)std::min<uint64_t>(w1 - w0, (uint64_t)c->num_cu * 32);
         KCHK(hipEventRecord(c->ev[nev], c->stream));
-        hipLaunchKernelGGL(k_kcp_add, dim3(grid), dim3(64), 0, c->stream, (const uint8_t*)c->d_seq, (const uint64_t*)c->d_off, base, (const KcpSel*)c->d_sel, w0, w1, c->k, c->d_tab,
+        hipLaunchKernelGGL(k_kcp_add, dim3(grid), dim3(64), 0, c->stream, d_seq, d_off, base, (const KcpSel*)c->d_sel, w0, w1, c->k, c->d_tab,
                            c->slots - 1, 64 - log2u64(c->slots), c->d_words);
         KCHK(hipGetLastError());
         KCHK(hipEventRecord(c->ev[nev + 1], c->stream));
@@ -452,6 +458,21 @@ void dbtk_kcp_free(dbtk_kcp_t* c) {
 
 dbtk_status_t dbtk_kcp_add(dbtk_kcp_t* c, const uint8_t* seq_bytes, const uint64_t* seq_offsets, uint64_t npairs, const uint32_t* src, const uint32_t* dst) {
     return guarded([&] { return kcp_add_impl(c, seq_bytes, seq_offsets, npairs, src, dst); });
+}
+
+dbtk_status_t dbtk_kcp_add_device(dbtk_kcp_t* c, const void* d_seq, const void* d_offsets, uint64_t npairs, const void* d_src, const uint32_t* dst) {
+    return guarded([&]() -> dbtk_status_t {
+        if (!c || (npairs && (!d_seq || !d_offsets || !d_src || !dst))) { set_error("dbtk_kcp_add_device: null argument"); return DBTK_ERR_ARG; }
+        if (npairs > 0x7FFFFFFFull) { set_error("dbtk_kcp_add_device: more than 2^31 - 1 pairs in one call"); return DBTK_ERR_ARG; }
+        if (!npairs) return kcp_add_impl(c, nullptr, nullptr, 0, nullptr, nullptr);
+        KCHK(hipSetDevice(c->device));
+        // what decides which pairs are counted, and the bound on their new keys, comes to the host: 20 bytes per pair; the reads stay
+        std::vector<uint64_t> off(2 * npairs + 1);
+        std::vector<uint32_t> src(npairs);
+        KCHK(hipMemcpy(off.data(), d_offsets, off.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        KCHK(hipMemcpy(src.data(), d_src, src.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        return kcp_add_impl(c, nullptr, off.data(), npairs, src.data(), dst, (const uint8_t*)d_seq, (const uint64_t*)d_offsets);
+    });
 }
 
 dbtk_status_t dbtk_kcp_count(dbtk_kcp_t* c, uint32_t cls, uint64_t* n) {

@@ -434,6 +434,11 @@ int dbtk_synth_write_fasta(const uint8_t* reads, uint64_t npairs, uint32_t rlen,
 }
 
 uint64_t dbtk_synth_nbases(void* h) { return ((Synth*)h)->seq.size(); }
+// the haplotype sequences themselves (flank + TR + flank, back to back): haplotype j of locus l = seq[hap_beg[locus_hap0[l] + j], hap_beg[locus_hap0[l] + j + 1])
+void dbtk_synth_sequences(void* h, const uint8_t** seq, const uint64_t** hap_beg, const uint32_t** locus_hap0) {
+    Synth* s = (Synth*)h;
+    *seq = s->seq.data(); *hap_beg = s->hap_beg.data(); *locus_hap0 = s->locus_hap0.data();
+}
 
 // npairs pairs of rlen-bp reads into out[npairs * 2 * rlen]; read r at r*rlen.
 // hit_frac of the pairs come from the loci, the rest are uniform random.

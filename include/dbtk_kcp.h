@@ -54,6 +54,14 @@ void dbtk_kcp_free(dbtk_kcp_t* kcp);
 dbtk_status_t dbtk_kcp_add(dbtk_kcp_t* kcp, const uint8_t* seq_bytes, const uint64_t* seq_offsets, uint64_t npairs, const uint32_t* src,
                            const uint32_t* dst);
 
+/* The same for a batch that lies in device memory in the layout of dbtk_align_batch_device: d_seq (indexed by the offsets as they
+ * are), d_offsets = uint64[2 * npairs + 1], d_src = uint32[npairs], all on the handle's device and complete before the call (the
+ * handle's stream is not ordered against the one that made them); dst[npairs] is a host array (>= nloci: skip the pair).  The reads
+ * and sources stay in HBM: the offsets and sources (20 bytes per pair) are copied to the host to choose the pairs and bound their
+ * keys, the counting kernel is dbtk_kcp_add's.  Returns when the batch is counted.  Added without moving DBTK_KCP_API_VERSION
+ * (nothing that existed changed); its presence goes with dbtk_sim.h (DBTK_SIM_API_VERSION 1). */
+dbtk_status_t dbtk_kcp_add_device(dbtk_kcp_t* kcp, const void* d_seq, const void* d_offsets, uint64_t npairs, const void* d_src, const uint32_t* dst);
+
 /* cls 0: true positives, 1: false positives.  *n = entries of the class. */
 dbtk_status_t dbtk_kcp_count(dbtk_kcp_t* kcp, uint32_t cls, uint64_t* n);
 /* The entries of the class sorted by (locus, k-mer) into the arrays (each may be null).  DBTK_ERR_OVERFLOW (nothing copied) when
