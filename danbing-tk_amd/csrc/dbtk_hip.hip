@@ -14,6 +14,7 @@
 
 #include <algorithm>
 #include <deque>
+#include <functional>
 #include <map>
 #include <atomic>
 #include <chrono>
@@ -343,16 +344,56 @@ struct Timed {
 // The HBM tables of an RPGG on a device, shared by every context created for that (handle, device): the index and its
 // minimizer-grouped copy, the presence filter, the class table, vv, ... are built by the first context and freed with the
 // last one (two contexts on one GPU used to hold two copies: 26 GB each at release scale).  The optional tables (graph,
-// TR edges, bait) are added by the first context that needs them.
+// TR edges, bait) are added by the first context that needs them.  The share OWNS every table: this is the one place their
+// pointers are declared (drop_share the one that frees them), a context only keeps a copy of T for its kernels.
+enum { TB_IDX, TB_FLT, TB_CLS, TB_MZ, TB_OVF, TB_GR, TB_GRMZ, TB_LIMG, TB_LIMG_CACHED, TB_SMALL, TB_GATES, TB_TOTAL, TB_GLIMG, TB_COUNT };
 struct TableShare {
     int refs = 0;
-    IdxBucket* d_idx = nullptr; uint64_t* d_flt = nullptr; uint64_t flt_words = 0; uint32_t* d_trbeg = nullptr; ClsSlot* d_cls = nullptr;
-    MzBucket* d_mz = nullptr; MzSlot* d_ovf = nullptr; GrSlot* d_gr = nullptr; MzBucket* d_grmz = nullptr; uint32_t* d_vv = nullptr; uint8_t* d_qc = nullptr; uint16_t* d_perm = nullptr;
-    ClsSlot* d_tre = nullptr; ClsSlot* d_bait = nullptr;
-    LocusDir* d_ldir = nullptr; uint8_t* d_limg = nullptr; LocusDir* d_gldir = nullptr; uint8_t* d_glimg = nullptr;
-    uint64_t bytes[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // HBM bytes per table (dbtk_ctx_table_bytes)
-    DevTables T;
-    uint32_t consistent = 0;
+    IdxBucket* d_idx = nullptr;
+    uint64_t* d_flt = nullptr;
+    uint32_t* d_trbeg = nullptr;
+    ClsSlot* d_cls = nullptr;
+    MzBucket* d_mz = nullptr;     // the probe kernel's minimizer-grouped copy of the index (level 1)
+    MzSlot* d_ovf = nullptr;      //   ... and its overflow table (level 2)
+    GrSlot* d_gr = nullptr;       // graph table (threading = 2), nullptr when the handle holds no graph or no context has walked yet
+    MzBucket* d_grmz = nullptr;   //   ... and its minimizer-grouped copy (the lean walk kernel)
+    uint32_t* d_vv = nullptr; uint8_t* d_qc = nullptr; uint16_t* d_perm = nullptr;
+    ClsSlot* d_tre = nullptr; ClsSlot* d_bait = nullptr;  // optional gates
+    LocusDir* d_ldir = nullptr;   // per-locus images of the index (dbtk_locus.h): directory,
+    uint8_t* d_limg = nullptr;    //   ... and the images
+    LocusDir* d_gldir = nullptr;  // per-locus images of the graph table (walking contexts)
+    uint8_t* d_glimg = nullptr;
+    // HBM bytes per table (dbtk_ctx_table_bytes; TB_LIMG_CACHED is a flag, TB_TOTAL is summed when asked for): every builder enters its own
+    uint64_t bytes[TB_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t loc_nimg = 0, loc_left_out = 0;  // index images: loci that have one, keys that found no place in theirs
+    DevTables T;  // (T.consistent: the index-vs-sets verdict of the build)
+};
+// what a builder of tables works with (the context that asked is only where the stream comes from)
+struct TableBuild {
+    TableShare* sh;
+    const dbtk_rpgg* g;
+    hipStream_t stream;
+};
+
+// A device (or pinned) temporary of the table builders: freed on every way out of its scope, HIPCHK's and LAUNCH's returns included.
+// Allocated at the place of use, so that the allocation trace names that line: HIPCHK(hipMalloc(t.out(), bytes)).
+template <class T, bool PINNED = false>
+class Scoped {
+public:
+    Scoped() = default;
+    Scoped(Scoped&& o) noexcept : p_(o.release()) {}
+    Scoped& operator=(Scoped&& o) noexcept { if (this != &o) { drop(); p_ = o.release(); } return *this; }
+    ~Scoped() { drop(); }
+    T* get() const { return p_; }
+    T** out() { drop(); return &p_; }
+    T* release() { T* r = p_; p_ = nullptr; return r; }  // a finished table: the share's from here on
+private:
+    void drop() {
+        if (!p_) return;
+        if (PINNED) (void)hipHostFree(p_); else (void)hipFree(p_);
+        p_ = nullptr;
+    }
+    T* p_ = nullptr;
 };
 
 constexpr uint32_t TK_INLINE = 8;  // words in front of d_small (same allocation): the chunk counters of a batch of up to three chunks
@@ -363,31 +404,12 @@ struct dbtk_ctx {
     dbtk_params_t P;
     int device = 0;
     hipStream_t stream = nullptr;
-    DevTables T;
+    DevTables T;                  // the share's tables as the kernels get them (a copy of share->T, taken once the optional tables are in)
     // device allocations
-    IdxBucket* d_idx = nullptr;
-    uint64_t* d_flt = nullptr; uint64_t flt_words = 0;
-    uint32_t* d_trbeg = nullptr;
-    ClsSlot* d_cls = nullptr;
-    MzBucket* d_mz = nullptr;     // the probe kernel's minimizer-grouped copy of the index (level 1)
-    MzSlot* d_ovf = nullptr;      //   ... and its overflow table (level 2)
-    GrSlot* d_gr = nullptr;       // graph table (threading = 2), nullptr when the handle holds no graph
-    MzBucket* d_grmz = nullptr;   //   ... and its minimizer-grouped copy (the lean walk kernel)
-    LocusDir* d_ldir = nullptr;   // per-locus images of the index (dbtk_locus.h): directory,
-    uint8_t* d_limg = nullptr;    //   ... and the images
-    LocusDir* d_gldir = nullptr;  // per-locus images of the graph table (walking contexts)
-    uint8_t* d_glimg = nullptr;
-    uint64_t glimg_bytes = 0;
     int wfl_blocks[6] = {0, 0, 0, 0, 0, 0};  // workgroups of k_walk_fast_locus<3 | 5, class 0 | 1 | 2>
-    uint64_t limg_bytes = 0, loc_nimg = 0, loc_left_out = 0;
-    bool loc_from_cache = false;
-    uint64_t tb_idx = 0, tb_flt = 0, tb_cls = 0, tb_mz = 0, tb_ovf = 0, tb_gr = 0, tb_grmz = 0;  // bytes of the tables this context built
     int loc_blocks[6] = {0, 0, 0, 0, 0, 0};  // workgroups of k_probe_locus<3 | 5, class 0 | 1 | 2>
     int locf_blocks[6] = {0, 0, 0, 0, 0, 0}; // ... of its fused form (more LDS per workgroup)
     uint32_t* h_sortflag = nullptr;  // pinned: survivors [0] and sort flag [6] of the batch before (a hint: see launch_batch)
-    uint32_t* d_vv = nullptr;
-    uint8_t* d_qc = nullptr;
-    uint16_t* d_perm = nullptr;
     uint64_t* d_accum = nullptr;  // counts | kmc | nmapread | counters
     uint64_t* d_ctr = nullptr;    // counter replicas (folded into d_accum's counters before anything reads them: sync_all)
     bool fold_pending = false;    // batches have been launched since the replicas were last folded
@@ -419,7 +441,6 @@ struct dbtk_ctx {
     uint64_t last_walk_npairs = 0; bool last_walk_recs = false;  // what dbtk_ctx_walk_results may fetch
     int walk_blocks = 0, walkfast_blocks = 0;
     // optional gates
-    ClsSlot* d_tre = nullptr; ClsSlot* d_bait = nullptr;
     uint8_t* d_qual = nullptr; uint64_t qual_cap = 0;
     uint64_t* d_edge = nullptr; uint64_t edge_cap = 0;
     uint64_t* d_qmask = nullptr; uint64_t qmask_cap = 0;
@@ -438,7 +459,6 @@ struct dbtk_ctx {
     std::vector<std::unordered_map<uint64_t, uint64_t>> btTK;
     std::vector<std::unordered_map<uint64_t, uint16_t>> baitDB_host;
     std::vector<dbtk_pair_rec_t> own_recs;  // record buffer when the caller passes none but -tb needs the bait-stage records
-    uint64_t mz_turned = 0;       // keys in the overflow table
     int k1_blocks = 0, probe_wpc = 32, probe2_wpc[4] = {8, 8, 8, 8}, probe2f_wpc[4] = {8, 8, 8, 8};
     bool timers_on = true;
     uint32_t timers_every = 1;  // event records around the kernels of every n-th batch (8 records cost ~30 us per batch)
@@ -447,7 +467,6 @@ struct dbtk_ctx {
     uint32_t* d_epoch = nullptr;
     int pair_blocks[3] = {0, 0, 0}, usual_blocks[3] = {0, 0, 0}, num_cu = 0, max_pair_blocks = 0;
     int vote_rows = 0;  // rows of the vote-spill pool: the workgroups of the general resolve kernel that can be resident at once
-    uint32_t consistent = 0;
     Timed timed[NKERN];
     // Second lane of the device-resident entry point: successive batches alternate between two streams, each with its own
     // per-batch scratch, so that one batch's VALU-bound encode kernel overlaps the other's request-bound probe kernel
@@ -486,19 +505,18 @@ uint32_t log2u(uint64_t c) { return 63u - (uint32_t)__builtin_clzll(c); }
 std::mutex g_share_m;
 std::map<std::pair<uint64_t, int>, TableShare*> g_shares;  // (handle's uid, device): see dbtk_rpgg::uid
 
+// the one place a share's tables are freed (a share whose first build failed comes here too, before anyone could see it)
+void drop_share(TableShare* sh) {
+    void* ptrs[] = {sh->d_flt, sh->d_trbeg, sh->d_idx, sh->d_cls, sh->d_vv, sh->d_qc, sh->d_perm, sh->d_tre, sh->d_bait, sh->d_gr, sh->d_grmz, sh->d_mz, sh->d_ovf, sh->d_ldir, sh->d_limg, sh->d_gldir, sh->d_glimg};
+    for (void* p : ptrs) if (p) (void)hipFree(p);
+    delete sh;
+}
 void release_share(dbtk_ctx* c) {
     std::lock_guard<std::mutex> l(g_share_m);
     TableShare* sh = c->share;
-    if (!sh) {  // the context never got as far as sharing: the tables (if any) are its own
-        void* own[] = {c->d_flt, c->d_trbeg, c->d_idx, c->d_cls, c->d_vv, c->d_qc, c->d_perm, c->d_tre, c->d_bait, c->d_gr, c->d_grmz, c->d_mz, c->d_ovf, c->d_ldir, c->d_limg, c->d_gldir, c->d_glimg};
-        for (void* p : own) if (p) (void)hipFree(p);
-        return;
-    }
-    if (--sh->refs > 0) return;
-    void* ptrs[] = {sh->d_flt, sh->d_trbeg, sh->d_idx, sh->d_cls, sh->d_vv, sh->d_qc, sh->d_perm, sh->d_tre, sh->d_bait, sh->d_gr, sh->d_grmz, sh->d_mz, sh->d_ovf, sh->d_ldir, sh->d_limg, sh->d_gldir, sh->d_glimg};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
+    if (!sh || --sh->refs > 0) return;  // (no share: the context never got as far as the tables)
     g_shares.erase(std::make_pair(c->g_uid, c->device));
-    delete sh;
+    drop_share(sh);
 }
 
 void free_ctx(dbtk_ctx* c) {
@@ -529,12 +547,14 @@ void free_ctx(dbtk_ctx* c) {
     delete c;
 }
 
-dbtk_status_t build_locus_images(dbtk_ctx* c);
-dbtk_status_t build_graph_images(dbtk_ctx* c);
-dbtk_status_t build_tables(dbtk_ctx* c) {
-    const dbtk_rpgg* g = c->g;
+dbtk_status_t build_locus_images(const TableBuild& b);
+dbtk_status_t build_graph_images(const TableBuild& b);
+// The tables every context needs, into a share nobody else sees yet (a failure leaves what was built to drop_share).
+dbtk_status_t build_tables(const TableBuild& b) {
+    TableShare* sh = b.sh;
+    const dbtk_rpgg* g = b.g;
     const uint64_t nloci = g->nloci;
-    hipStream_t s = c->stream;
+    hipStream_t s = b.stream;
     // (DBTK_VERBOSE: where the start-up goes)
     const bool verbose = getenv("DBTK_VERBOSE") != nullptr;
     auto wallclk = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -548,82 +568,80 @@ dbtk_status_t build_tables(dbtk_ctx* c) {
     uint64_t sparsity = 2;
     if (const char* e = getenv("DBTK_IDX_SPARSITY")) { const long v = atol(e); if (v >= 2 && v <= 64) sparsity = (uint64_t)v; }
     const uint64_t icap = pow2_at_least(sparsity * nkeys + 8), nbkt = icap / 4;
-    HIPCHK(hipMalloc(&c->d_idx, nbkt * sizeof(IdxBucket)));
-    c->tb_idx = nbkt * sizeof(IdxBucket);
-    LAUNCH(k_fill_idx, dim3(2048), dim3(256), s, c->d_idx, icap);
+    HIPCHK(hipMalloc(&sh->d_idx, nbkt * sizeof(IdxBucket)));
+    sh->bytes[TB_IDX] = nbkt * sizeof(IdxBucket);
+    LAUNCH(k_fill_idx, dim3(2048), dim3(256), s, sh->d_idx, icap);
+    uint64_t flt_words = 0;
     if (nkeys) {
-        uint64_t* dk = nullptr; uint32_t* dv = nullptr;
-        HIPCHK(hipMalloc(&dk, nkeys * 8));
-        HIPCHK(hipMalloc(&dv, nkeys * 4));
-        HIPCHK(hipMemcpyAsync(dk, g->keys.data(), nkeys * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(dv, g->vals.data(), nkeys * 4, hipMemcpyHostToDevice, s));
-        IdxBuildArgs a{c->d_idx, nbkt - 1, 64 - log2u(nbkt), dk, dv, nkeys};
+        Scoped<uint64_t> dk; Scoped<uint32_t> dv;
+        HIPCHK(hipMalloc(dk.out(), nkeys * 8));
+        HIPCHK(hipMalloc(dv.out(), nkeys * 4));
+        HIPCHK(hipMemcpyAsync(dk.get(), g->keys.data(), nkeys * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dv.get(), g->vals.data(), nkeys * 4, hipMemcpyHostToDevice, s));
+        IdxBuildArgs a{sh->d_idx, nbkt - 1, 64 - log2u(nbkt), dk.get(), dv.get(), nkeys};
         LAUNCH(k_idx_insert, dim3(2048), dim3(256), s, a);
         {   // presence filter: DBTK_FILTER_BPK bits per key (default 4, 0 = none), rounded up to a power of two of words
             uint64_t bpk = 4;
             if (const char* e = getenv("DBTK_FILTER_BPK")) { const long v = atol(e); if (v >= 0 && v <= 64) bpk = (uint64_t)v; }
             if (bpk) {
-                c->flt_words = pow2_at_least((bpk * nkeys + 63) / 64);
-                HIPCHK(hipMalloc(&c->d_flt, c->flt_words * 8));
-                c->tb_flt = c->flt_words * 8;
-                HIPCHK(hipMemsetAsync(c->d_flt, 0, c->flt_words * 8, s));
-                FltBuildArgs fa{c->d_flt, log2u(c->flt_words), g->ksize, dk, nkeys};
+                flt_words = pow2_at_least((bpk * nkeys + 63) / 64);
+                HIPCHK(hipMalloc(&sh->d_flt, flt_words * 8));
+                sh->bytes[TB_FLT] = flt_words * 8;
+                HIPCHK(hipMemsetAsync(sh->d_flt, 0, flt_words * 8, s));
+                FltBuildArgs fa{sh->d_flt, log2u(flt_words), g->ksize, dk.get(), nkeys};
                 LAUNCH(k_flt_insert, dim3(2048), dim3(256), s, fa);
             }
         }
-        LAUNCH(k_idx_finalize, dim3(2048), dim3(256), s, c->d_idx, icap);
+        LAUNCH(k_idx_finalize, dim3(2048), dim3(256), s, sh->d_idx, icap);
         HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(hipFree(dk));
-        HIPCHK(hipFree(dv));
     }
     tick("index + presence filter (H2D of keys and values, insert, finalize)");
     // ---- vv (never empty on the device: odd vals index it)
-    HIPCHK(hipMalloc(&c->d_vv, (g->vv.size() + 1) * 4));
-    if (!g->vv.empty()) HIPCHK(hipMemcpyAsync(c->d_vv, g->vv.data(), g->vv.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMalloc(&sh->d_vv, (g->vv.size() + 1) * 4));
+    sh->bytes[TB_SMALL] += (g->vv.size() + 1) * 4;
+    if (!g->vv.empty()) HIPCHK(hipMemcpyAsync(sh->d_vv, g->vv.data(), g->vv.size() * 4, hipMemcpyHostToDevice, s));
     // ---- class table: TR pass first, then flank (flank overrides)
     const uint64_t ntrf = g->tr_ks.size(), nfl = g->fl_ks.size();
     uint64_t cls_pct = 130;  // slots per entry, in percent, before rounding up to a power of two (DBTK_CLS_SPARSITY_PCT): only k-mers shared between loci are looked up here
     if (const char* e = getenv("DBTK_CLS_SPARSITY_PCT")) { const long v = atol(e); if (v >= 110 && v <= 1600) cls_pct = (uint64_t)v; }
     const uint64_t ccap = pow2_at_least((ntrf + nfl) * cls_pct / 100 + 2);
-    HIPCHK(hipMalloc(&c->d_cls, ccap * sizeof(ClsSlot)));
-    c->tb_cls = ccap * sizeof(ClsSlot);
-    HIPCHK(hipMemsetAsync(c->d_cls, 0xFF, ccap * sizeof(ClsSlot), s));
-    uint64_t* dstats = nullptr;  // [0] index memberships, [1] of them missing from the class table, [2] class entries
-    HIPCHK(hipMalloc(&dstats, 3 * 8));
-    HIPCHK(hipMemsetAsync(dstats, 0, 3 * 8, s));
+    HIPCHK(hipMalloc(&sh->d_cls, ccap * sizeof(ClsSlot)));
+    sh->bytes[TB_CLS] = ccap * sizeof(ClsSlot);
+    HIPCHK(hipMemsetAsync(sh->d_cls, 0xFF, ccap * sizeof(ClsSlot), s));
+    Scoped<uint64_t> dstats;  // [0] index memberships, [1] of them missing from the class table, [2] class entries
+    HIPCHK(hipMalloc(dstats.out(), 3 * 8));
+    HIPCHK(hipMemsetAsync(dstats.get(), 0, 3 * 8, s));
     {
         std::vector<uint64_t> beg(nloci + 1, 0);
-        uint64_t *dks = nullptr, *dbeg = nullptr, *dslot = nullptr;
+        Scoped<uint64_t> dks, dbeg, dslot;
         const uint64_t nmax = ntrf > nfl ? ntrf : nfl;
-        HIPCHK(hipMalloc(&dks, (nmax + 1) * 8));
-        HIPCHK(hipMalloc(&dslot, (ntrf + 1) * 8));
-        HIPCHK(hipMalloc(&dbeg, (nloci + 1) * 8));
+        HIPCHK(hipMalloc(dks.out(), (nmax + 1) * 8));
+        HIPCHK(hipMalloc(dslot.out(), (ntrf + 1) * 8));
+        HIPCHK(hipMalloc(dbeg.out(), (nloci + 1) * 8));
         for (uint64_t l = 0; l < nloci; ++l) beg[l + 1] = beg[l] + g->tr_cnt[l];
         if (ntrf) {
-            HIPCHK(hipMemcpyAsync(dks, g->tr_ks.data(), ntrf * 8, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(dslot, g->out_slot.data(), ntrf * 8, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(dbeg, beg.data(), (nloci + 1) * 8, hipMemcpyHostToDevice, s));
-            ClsBuildArgs a{c->d_cls, ccap - 1, 64 - log2u(ccap), dks, dbeg, (uint32_t)nloci, dslot, ntrf, dstats + 2};
+            HIPCHK(hipMemcpyAsync(dks.get(), g->tr_ks.data(), ntrf * 8, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(dslot.get(), g->out_slot.data(), ntrf * 8, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(dbeg.get(), beg.data(), (nloci + 1) * 8, hipMemcpyHostToDevice, s));
+            ClsBuildArgs a{sh->d_cls, ccap - 1, 64 - log2u(ccap), dks.get(), dbeg.get(), (uint32_t)nloci, dslot.get(), ntrf, dstats.get() + 2};
             LAUNCH(k_cls_insert, dim3(2048), dim3(256), s, a);
             HIPCHK(hipStreamSynchronize(s));
         }
         for (uint64_t l = 0; l < nloci; ++l) beg[l + 1] = beg[l] + g->fl_cnt[l];
         if (nfl) {
-            HIPCHK(hipMemcpyAsync(dks, g->fl_ks.data(), nfl * 8, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(dbeg, beg.data(), (nloci + 1) * 8, hipMemcpyHostToDevice, s));
-            ClsBuildArgs a{c->d_cls, ccap - 1, 64 - log2u(ccap), dks, dbeg, (uint32_t)nloci, nullptr, nfl, dstats + 2};
+            HIPCHK(hipMemcpyAsync(dks.get(), g->fl_ks.data(), nfl * 8, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(dbeg.get(), beg.data(), (nloci + 1) * 8, hipMemcpyHostToDevice, s));
+            ClsBuildArgs a{sh->d_cls, ccap - 1, 64 - log2u(ccap), dks.get(), dbeg.get(), (uint32_t)nloci, nullptr, nfl, dstats.get() + 2};
             LAUNCH(k_cls_insert, dim3(2048), dim3(256), s, a);
             HIPCHK(hipStreamSynchronize(s));
         }
-        HIPCHK(hipFree(dks));
-        HIPCHK(hipFree(dslot));
-        HIPCHK(hipFree(dbeg));
     }
     tick("class table (H2D of TR and flank k-mers, insert)");
     // ---- QC mask
     if (!g->qc.empty()) {
-        HIPCHK(hipMalloc(&c->d_qc, nloci));
-        HIPCHK(hipMemcpyAsync(c->d_qc, g->qc.data(), nloci, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMalloc(&sh->d_qc, nloci));
+        sh->bytes[TB_SMALL] += nloci;
+        HIPCHK(hipMemcpyAsync(sh->d_qc, g->qc.data(), nloci, hipMemcpyHostToDevice, s));
     }
     // ---- introsort permutation of n equal keys (the common case: every k-mer unique to one locus)
     {
@@ -631,38 +649,38 @@ dbtk_status_t build_tables(dbtk_ctx* c) {
         std::vector<uint32_t> key(NHMAX, 1);
         int stack[3 * 40];
         for (int n = 1; n <= NHMAX; ++n) gcc_sort_index(perm.data() + (size_t)n * (n - 1) / 2, n, key.data(), stack);
-        HIPCHK(hipMalloc(&c->d_perm, perm.size() * 2));
-        HIPCHK(hipMemcpyAsync(c->d_perm, perm.data(), perm.size() * 2, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMalloc(&sh->d_perm, perm.size() * 2));
+        sh->bytes[TB_SMALL] += perm.size() * 2;
+        HIPCHK(hipMemcpyAsync(sh->d_perm, perm.data(), perm.size() * 2, hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
     }
     {   // first output slot of each locus
         std::vector<uint32_t> tb(nloci + 1, 0);
         for (uint64_t l = 0; l <= nloci; ++l) tb[l] = (uint32_t)g->out_beg[l];
-        HIPCHK(hipMalloc(&c->d_trbeg, (nloci + 1) * 4));
-        HIPCHK(hipMemcpyAsync(c->d_trbeg, tb.data(), (nloci + 1) * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMalloc(&sh->d_trbeg, (nloci + 1) * 4));
+        sh->bytes[TB_SMALL] += (nloci + 1) * 4;
+        HIPCHK(hipMemcpyAsync(sh->d_trbeg, tb.data(), (nloci + 1) * 4, hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
     }
-    DevTables& T = c->T;
+    DevTables& T = sh->T;
     memset(&T, 0, sizeof(T));  // optional tables (tre, bait, gr, mz) stay null unless built
-    T.trbeg = c->d_trbeg;
-    T.flt = c->d_flt; T.flt_logw = c->flt_words ? log2u(c->flt_words) : 0;
-    T.idx = c->d_idx; T.idx_mask = nbkt - 1; T.idx_shift = 64 - log2u(nbkt);
-    T.vv = c->d_vv;
-    T.cls = c->d_cls; T.cls_mask = ccap - 1; T.cls_shift = 64 - log2u(ccap);
-    T.qc = c->d_qc;
-    T.permtab = c->d_perm;
+    T.trbeg = sh->d_trbeg;
+    T.flt = sh->d_flt; T.flt_logw = flt_words ? log2u(flt_words) : 0;
+    T.idx = sh->d_idx; T.idx_mask = nbkt - 1; T.idx_shift = 64 - log2u(nbkt);
+    T.vv = sh->d_vv;
+    T.cls = sh->d_cls; T.cls_mask = ccap - 1; T.cls_shift = 64 - log2u(ccap);
+    T.qc = sh->d_qc;
+    T.permtab = sh->d_perm;
     T.nloci = (uint32_t)nloci;
     T.ksize = g->ksize;
     T.consistent = 0;
     {   // class of single-locus k-mers into the index slots + index-vs-sets consistency verdict
-        IdxAuxArgs a{c->d_idx, icap, T, dstats};
+        IdxAuxArgs a{sh->d_idx, icap, T, dstats.get()};
         LAUNCH(k_idx_aux, dim3(2048), dim3(256), s, a);
         uint64_t st[3] = {0, 0, 0};
-        HIPCHK(hipMemcpyAsync(st, dstats, sizeof(st), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(st, dstats.get(), sizeof(st), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(hipFree(dstats));
         T.consistent = (st[1] == 0 && st[0] == st[2]) ? 1u : 0u;
-        c->consistent = T.consistent;
     }
     tick("permutation table, counters' first slots, index consistency + classes");
     {   // the probe kernel's minimizer-grouped copy of the index, for the values of k its lean form exists for
@@ -675,36 +693,34 @@ dbtk_status_t build_tables(dbtk_ctx* c) {
             if (const char* e = getenv("DBTK_MZ_SPARSITY")) { const long v = atol(e); if (v >= 1 && v <= 64) per = (uint64_t)v; }
             uint64_t nb = pow2_at_least(nkeys * per / 8 + 8);
             if (nb > (1ull << 28)) nb = 1ull << 28;  // the bucket number comes out of 28 bits of the minimizer's hash
-            HIPCHK(hipMalloc(&c->d_mz, nb * sizeof(MzBucket)));
-            c->tb_mz = nb * sizeof(MzBucket);
-            LAUNCH(k_mz_fill, dim3(2048), dim3(256), s, reinterpret_cast<uint64_t*>(c->d_mz), nb * 16, 1);
-            uint64_t* dn = nullptr;
-            HIPCHK(hipMalloc(&dn, 8));
-            HIPCHK(hipMemsetAsync(dn, 0, 8, s));
-            MzBuildArgs a{c->d_idx, icap, c->d_mz, (uint32_t)(nb - 1), nullptr, 0, g->ksize, m, 0, dn};
+            HIPCHK(hipMalloc(&sh->d_mz, nb * sizeof(MzBucket)));
+            sh->bytes[TB_MZ] = nb * sizeof(MzBucket);
+            LAUNCH(k_mz_fill, dim3(2048), dim3(256), s, reinterpret_cast<uint64_t*>(sh->d_mz), nb * 16, 1);
+            Scoped<uint64_t> dn;
+            HIPCHK(hipMalloc(dn.out(), 8));
+            HIPCHK(hipMemsetAsync(dn.get(), 0, 8, s));
+            MzBuildArgs a{sh->d_idx, icap, sh->d_mz, (uint32_t)(nb - 1), nullptr, 0, g->ksize, m, 0, dn.get()};
             LAUNCH(k_mz_insert, dim3(2048), dim3(256), s, a);  // level 1; counts the keys it turns away
             uint64_t nturned = 0;
-            HIPCHK(hipMemcpyAsync(&nturned, dn, 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(&nturned, dn.get(), 8, hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
-            HIPCHK(hipFree(dn));
             uint64_t ovf_sp = 8;  // level 2: those keys, at most an eighth full (DBTK_OVF_SPARSITY; a sixteenth: twice the bytes for 1 % of the lean kernel's time)
             if (const char* e = getenv("DBTK_OVF_SPARSITY")) { const long v = atol(e); if (v >= 2 && v <= 64) ovf_sp = (uint64_t)v; }
             uint64_t ocap = pow2_at_least(ovf_sp * nturned + 8);
             if (ocap > (1ull << 32)) { set_error("overflow table of the probe kernel: more than 2^28 keys turned away by full buckets"); return DBTK_ERR_UNSUPPORTED; }
-            HIPCHK(hipMalloc(&c->d_ovf, ocap * sizeof(MzSlot)));
-            c->tb_ovf = ocap * sizeof(MzSlot);
-            LAUNCH(k_mz_fill, dim3(2048), dim3(256), s, reinterpret_cast<uint64_t*>(c->d_ovf), ocap * 2, 0);
-            a.ovf = c->d_ovf; a.ovf_mask = (uint32_t)(ocap - 1); a.pass = 1;
+            HIPCHK(hipMalloc(&sh->d_ovf, ocap * sizeof(MzSlot)));
+            sh->bytes[TB_OVF] = ocap * sizeof(MzSlot);
+            LAUNCH(k_mz_fill, dim3(2048), dim3(256), s, reinterpret_cast<uint64_t*>(sh->d_ovf), ocap * 2, 0);
+            a.ovf = sh->d_ovf; a.ovf_mask = (uint32_t)(ocap - 1); a.pass = 1;
             LAUNCH(k_mz_insert, dim3(2048), dim3(256), s, a);
             HIPCHK(hipStreamSynchronize(s));
             HIPCHK(hipGetLastError());
-            T.mz = c->d_mz; T.mz_mask = nb - 1; T.mz_m = m;
-            T.ovf = c->d_ovf; T.ovf_mask = ocap - 1;
-            c->mz_turned = nturned;
+            T.mz = sh->d_mz; T.mz_mask = nb - 1; T.mz_m = m;
+            T.ovf = sh->d_ovf; T.ovf_mask = ocap - 1;
         }
     }
     tick("index by minimizer + overflow table");
-    const dbtk_status_t li = build_locus_images(c);
+    const dbtk_status_t li = build_locus_images(b);
     tick("index images");
     return li;
 }
@@ -728,25 +744,33 @@ static uint64_t rpgg_fingerprint(const dbtk_rpgg* g) {
     return h;
 }
 // checksum of the sidecar's payload: the directory (host) and the arena as it lies in HBM (device)
-static dbtk_status_t locus_cache_checksum(dbtk_ctx* c, const std::vector<LocusDir>& dir, const uint8_t* d_arena, uint64_t arena_bytes, uint64_t* out) {
+static dbtk_status_t locus_cache_checksum(hipStream_t s, const std::vector<LocusDir>& dir, const uint8_t* d_arena, uint64_t arena_bytes, uint64_t* out) {
     static_assert(sizeof(LocusDir) == 16, "directory entries are two checksum words");
     uint64_t hd = 0;
     const uint64_t* dw = reinterpret_cast<const uint64_t*>(dir.data());
     for (uint64_t i = 0; i < 2 * dir.size(); ++i) hd += csum_term(dw[i], i);
-    uint64_t* dsum = nullptr;
-    HIPCHK(hipMalloc(&dsum, 8));
-    HIPCHK(hipMemsetAsync(dsum, 0, 8, c->stream));
-    LAUNCH(k_csum, dim3(2048), dim3(256), c->stream, reinterpret_cast<const uint64_t*>(d_arena), arena_bytes / 8, dsum);
+    Scoped<uint64_t> dsum;
+    HIPCHK(hipMalloc(dsum.out(), 8));
+    HIPCHK(hipMemsetAsync(dsum.get(), 0, 8, s));
+    LAUNCH(k_csum, dim3(2048), dim3(256), s, reinterpret_cast<const uint64_t*>(d_arena), arena_bytes / 8, dsum.get());
     uint64_t ha = 0;
-    HIPCHK(hipMemcpyAsync(&ha, dsum, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipFree(dsum));
+    HIPCHK(hipMemcpyAsync(&ha, dsum.get(), 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     *out = ha + hd * 0x9E3779B97F4A7C15ull + arena_bytes;
     return DBTK_OK;
 }
+// the index's images are in HBM: into the share and its T
+static void commit_locus_images(TableShare* sh, uint64_t nloci, LocusDir* d_dir, uint8_t* d_arena, uint64_t arena_bytes, uint64_t nimg, uint64_t left_out, bool from_cache) {
+    sh->d_ldir = d_dir; sh->d_limg = d_arena;
+    sh->T.ldir = d_dir; sh->T.limg = d_arena;
+    sh->bytes[TB_LIMG] = arena_bytes; sh->bytes[TB_LIMG_CACHED] = from_cache ? 1 : 0; sh->bytes[TB_SMALL] += nloci * sizeof(LocusDir);
+    sh->loc_nimg = nimg; sh->loc_left_out = left_out;
+}
 // DBTK_OK: the images are in HBM, from the file; DBTK_ERR_FORMAT: no file, or not one of this RPGG / this layout / this build: the caller builds
-static dbtk_status_t load_locus_cache(dbtk_ctx* c, uint64_t fp) {
-    const dbtk_rpgg* g = c->g;
+// (directory and arena are the share's only once every check has passed: before that, each way out drops them)
+static dbtk_status_t load_locus_cache(const TableBuild& b, uint64_t fp) {
+    TableShare* sh = b.sh;
+    const dbtk_rpgg* g = b.g;
     const uint64_t nloci = g->nloci;
     FILE* f = fopen(g->idx_cache.c_str(), "rb");
     if (!f) return DBTK_ERR_FORMAT;
@@ -766,90 +790,83 @@ static dbtk_status_t load_locus_cache(dbtk_ctx* c, uint64_t fp) {
         ++nimg;
     }
     if (!nimg) return DBTK_ERR_FORMAT;
-    hipStream_t s = c->stream;
-    HIPCHK(hipMalloc(&c->d_ldir, nloci * sizeof(LocusDir)));
-    HIPCHK(hipMalloc(&c->d_limg, h.arena_bytes + 16));
+    hipStream_t s = b.stream;
+    Scoped<LocusDir> ldir; Scoped<uint8_t> limg;
+    HIPCHK(hipMalloc(ldir.out(), nloci * sizeof(LocusDir)));
+    HIPCHK(hipMalloc(limg.out(), h.arena_bytes + 16));
     {   // the arena, through a pinned buffer, 64 MB at a time
         const uint64_t CH = 64ull << 20;
-        uint8_t* pin = nullptr;
-        HIPCHK(hipHostMalloc((void**)&pin, CH, hipHostMallocDefault));
-        bool ok = true;
-        for (uint64_t at = 0; at < h.arena_bytes && ok; at += CH) {
+        Scoped<uint8_t, true> pin;
+        HIPCHK(hipHostMalloc(pin.out(), CH, hipHostMallocDefault));
+        for (uint64_t at = 0; at < h.arena_bytes; at += CH) {
             const uint64_t n = std::min<uint64_t>(CH, h.arena_bytes - at);
-            ok = fread(pin, 1, n, f) == n && hipMemcpy(c->d_limg + at, pin, n, hipMemcpyHostToDevice) == hipSuccess;
+            if (fread(pin.get(), 1, n, f) != n || hipMemcpy(limg.get() + at, pin.get(), n, hipMemcpyHostToDevice) != hipSuccess) return DBTK_ERR_FORMAT;
         }
-        (void)hipHostFree(pin);
-        if (!ok) { (void)hipFree(c->d_ldir); (void)hipFree(c->d_limg); c->d_ldir = nullptr; c->d_limg = nullptr; return DBTK_ERR_FORMAT; }
     }
-    auto drop = [&]() { (void)hipFree(c->d_ldir); (void)hipFree(c->d_limg); c->d_ldir = nullptr; c->d_limg = nullptr; return DBTK_ERR_FORMAT; };
     {   // the bytes are the ones that were written (a torn write, two writers' blocks mixed, a flipped bit: not used)
         uint64_t sum = 0;
-        const dbtk_status_t cs = locus_cache_checksum(c, dir, c->d_limg, h.arena_bytes, &sum);
-        if (cs) { (void)drop(); return cs; }
-        if (sum != h.checksum) return drop();
+        const dbtk_status_t cs = locus_cache_checksum(s, dir, limg.get(), h.arena_bytes, &sum);
+        if (cs) return cs;
+        if (sum != h.checksum) return DBTK_ERR_FORMAT;
     }
-    HIPCHK(hipMemcpyAsync(c->d_ldir, dir.data(), nloci * sizeof(LocusDir), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ldir.get(), dir.data(), nloci * sizeof(LocusDir), hipMemcpyHostToDevice, s));
     // ... and they are THIS index's images: every entry looked up in the plain index just built from the RPGG, the entries of a locus
     // counted against its keys in the index (a file of another RPGG of the same sizes, one rebuilt in place: not used)
-    uint32_t *dbad = nullptr, *dvcnt = nullptr, *dcnt = nullptr;
-    HIPCHK(hipMalloc(&dbad, nloci * 4));
-    HIPCHK(hipMalloc(&dvcnt, nloci * 4));
-    HIPCHK(hipMalloc(&dcnt, nloci * 4));
-    HIPCHK(hipMemsetAsync(dbad, 0, nloci * 4, s));
-    HIPCHK(hipMemsetAsync(dvcnt, 0, nloci * 4, s));
-    HIPCHK(hipMemsetAsync(dcnt, 0, nloci * 4, s));
+    Scoped<uint32_t> dbad, dvcnt, dcnt;
+    HIPCHK(hipMalloc(dbad.out(), nloci * 4));
+    HIPCHK(hipMalloc(dvcnt.out(), nloci * 4));
+    HIPCHK(hipMalloc(dcnt.out(), nloci * 4));
+    HIPCHK(hipMemsetAsync(dbad.get(), 0, nloci * 4, s));
+    HIPCHK(hipMemsetAsync(dvcnt.get(), 0, nloci * 4, s));
+    HIPCHK(hipMemsetAsync(dcnt.get(), 0, nloci * 4, s));
     LocBuildArgs a;
     memset(&a, 0, sizeof(a));
-    a.idx = c->d_idx; a.nslots = (c->T.idx_mask + 1) * 4; a.idx_mask = c->T.idx_mask; a.idx_shift = c->T.idx_shift; a.vv = c->d_vv;
-    a.cls = c->T.cls; a.cls_mask = c->T.cls_mask; a.cls_shift = c->T.cls_shift;
-    a.trbeg = c->d_trbeg; a.nloci = (uint32_t)nloci; a.ksize = g->ksize; a.dir = c->d_ldir; a.arena = c->d_limg; a.bad = dbad; a.vcnt = dvcnt; a.cnt = dcnt;
+    a.idx = sh->d_idx; a.nslots = (sh->T.idx_mask + 1) * 4; a.idx_mask = sh->T.idx_mask; a.idx_shift = sh->T.idx_shift; a.vv = sh->d_vv;
+    a.cls = sh->T.cls; a.cls_mask = sh->T.cls_mask; a.cls_shift = sh->T.cls_shift;
+    a.trbeg = sh->d_trbeg; a.nloci = (uint32_t)nloci; a.ksize = g->ksize; a.dir = ldir.get(); a.arena = limg.get(); a.bad = dbad.get(); a.vcnt = dvcnt.get(); a.cnt = dcnt.get();
     LAUNCH(k_loc_count, dim3(2048), dim3(256), s, a);
     LAUNCH(k_loc_verify, dim3(4096), dim3(256), s, a);
     std::vector<uint32_t> bad(nloci), vcnt(nloci), cnt(nloci);
-    HIPCHK(hipMemcpyAsync(bad.data(), dbad, nloci * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(vcnt.data(), dvcnt, nloci * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(cnt.data(), dcnt, nloci * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(bad.data(), dbad.get(), nloci * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(vcnt.data(), dvcnt.get(), nloci * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(cnt.data(), dcnt.get(), nloci * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipFree(dbad)); HIPCHK(hipFree(dvcnt)); HIPCHK(hipFree(dcnt));
     for (uint64_t l = 0; l < nloci; ++l)
-        if (bad[l] || (dir[l].bytes && vcnt[l] != cnt[l])) return drop();  // nothing of such a file is used
-    c->limg_bytes = h.arena_bytes; c->loc_nimg = nimg; c->loc_left_out = h.left_out; c->loc_from_cache = true;
-    c->T.ldir = c->d_ldir; c->T.limg = c->d_limg;
+        if (bad[l] || (dir[l].bytes && vcnt[l] != cnt[l])) return DBTK_ERR_FORMAT;  // nothing of such a file is used
+    commit_locus_images(sh, nloci, ldir.release(), limg.release(), h.arena_bytes, nimg, h.left_out, true);
     if (getenv("DBTK_VERBOSE")) fprintf(stderr, "locus images: %llu loci, %.1f MB, from %s\n", (unsigned long long)nimg, h.arena_bytes / 1e6, g->idx_cache.c_str());
     return DBTK_OK;
 }
 // (best effort: a sidecar that cannot be written is not an error of the run)
-static void write_locus_cache(dbtk_ctx* c, uint64_t fp, const std::vector<LocusDir>& dir) {
-    const dbtk_rpgg* g = c->g;
+static void write_locus_cache(const TableBuild& b, uint64_t fp, const std::vector<LocusDir>& dir) {
+    const TableShare* sh = b.sh;
+    const dbtk_rpgg* g = b.g;
     // (a name of its own per writer: two jobs on one RPGG prefix must not write into one file)
     std::random_device rd;
     const std::string tmp = g->idx_cache + ".tmp" + std::to_string((unsigned long long)getpid()) + "." + std::to_string((unsigned long long)g->uid) + "." + std::to_string((unsigned long long)rd());
     uint64_t sum = 0;
-    if (locus_cache_checksum(c, dir, c->d_limg, (c->limg_bytes + 15) & ~15ull, &sum)) return;
+    if (locus_cache_checksum(b.stream, dir, sh->d_limg, (sh->bytes[TB_LIMG] + 15) & ~15ull, &sum)) return;
     FILE* f = fopen(tmp.c_str(), "wb");
     if (!f) return;
     LocCacheHdr h;
     memset(&h, 0, sizeof(h));
     memcpy(h.magic, "DBTKIDX\1", 8);
     h.version = LOC_CACHE_VERSION; h.ksize = g->ksize; h.nloci = g->nloci; h.nkeys = g->keys.size(); h.fingerprint = fp;
-    h.arena_bytes = (c->limg_bytes + 15) & ~15ull; h.nimg = c->loc_nimg; h.left_out = c->loc_left_out; h.lg_max = LOC_LG_MAX; h.hdr_bytes = sizeof(h); h.checksum = sum;
+    h.arena_bytes = (sh->bytes[TB_LIMG] + 15) & ~15ull; h.nimg = sh->loc_nimg; h.left_out = sh->loc_left_out; h.lg_max = LOC_LG_MAX; h.hdr_bytes = sizeof(h); h.checksum = sum;
     bool ok = fwrite(&h, sizeof(h), 1, f) == 1 && fwrite(dir.data(), sizeof(LocusDir), dir.size(), f) == dir.size();
     const uint64_t CH = 64ull << 20;
-    uint8_t* pin = nullptr;
-    if (ok && hipHostMalloc((void**)&pin, CH, hipHostMallocDefault) == hipSuccess) {
+    Scoped<uint8_t, true> pin;
+    if (ok && hipHostMalloc(pin.out(), CH, hipHostMallocDefault) == hipSuccess) {
         for (uint64_t at = 0; at < h.arena_bytes && ok; at += CH) {
             const uint64_t n = std::min<uint64_t>(CH, h.arena_bytes - at);
-            ok = hipMemcpy(pin, c->d_limg + at, n, hipMemcpyDeviceToHost) == hipSuccess && fwrite(pin, 1, n, f) == n;
+            ok = hipMemcpy(pin.get(), sh->d_limg + at, n, hipMemcpyDeviceToHost) == hipSuccess && fwrite(pin.get(), 1, n, f) == n;
         }
-        (void)hipHostFree(pin);
     } else ok = false;
     if (ok && (fflush(f) != 0 || fsync(fileno(f)) != 0)) ok = false;  // (on the disk before it takes the name)
     if (fclose(f) != 0) ok = false;
     if (!ok || rename(tmp.c_str(), g->idx_cache.c_str()) != 0) remove(tmp.c_str());
 }
 
-// Per-locus images of the index (dbtk_locus.h), from the finished plain index: keys per locus -> image sizes (host) -> empty images
-// -> every (key, locus) membership into its locus' image.  DBTK_LOCUS=0: do without (the global tables answer every look-up).
 // the images' placement: a wave per locus, three launches by image class (the LDS a block needs: 19 / 37 / 83 KB)
 static dbtk_status_t launch_loc_place(const LocBuildArgs& a, uint64_t nloci, hipStream_t s) {
     static const bool per_thread = [] { const char* e = getenv("DBTK_LOC_PLACE_THREAD"); return e && atoi(e) != 0; }();
@@ -861,15 +878,102 @@ static dbtk_status_t launch_loc_place(const LocBuildArgs& a, uint64_t nloci, hip
     return DBTK_OK;
 }
 
-dbtk_status_t build_locus_images(dbtk_ctx* c) {
-    const dbtk_rpgg* g = c->g;
-    hipStream_t s = c->stream;
+// Per-locus images (dbtk_locus.h) of a finished table: entries per locus -> image sizes (host) -> empty images -> every (key, locus)
+// membership into its locus' image.  The index's images and the graph table's are built by this one body; what differs is said here:
+struct ImageBuild {
+    bool graph;           // the entries are the graph table's (k_gloc_count / k_gloc_scatter), else the index's (k_loc_count / k_loc_scatter)
+    LocBuildArgs src;     // the table the entries come from (the fields of the source; the rest zero)
+    uint64_t slot_max;    // a locus with this many TR k-mers or more gets no image (GLOC_SLOT_MAX for the graph)
+    bool all_or_none;     // a key that found no place (`left_out`) makes every image unusable (graph), else it is only counted (index)
+    std::function<void(const char*)> tick;  // (DBTK_VERBOSE: where the build's time goes)
+};
+struct ImagesBuilt {
+    Scoped<LocusDir> d_dir; Scoped<uint8_t> d_arena;  // null: no locus got an image
+    std::vector<LocusDir> dir;                        // the directory as it lies in HBM
+    uint64_t arena_bytes = 0, nimg = 0, left_out = 0;
+};
+static dbtk_status_t build_images(const TableBuild& b, const ImageBuild& ib, ImagesBuilt* out) {
+    const dbtk_rpgg* g = b.g;
+    hipStream_t s = b.stream;
+    const uint64_t nloci = g->nloci;
+    Scoped<uint32_t> dcnt, dbad;
+    HIPCHK(hipMalloc(dcnt.out(), nloci * 4));
+    HIPCHK(hipMalloc(dbad.out(), nloci * 4));
+    HIPCHK(hipMemsetAsync(dcnt.get(), 0, nloci * 4, s));
+    HIPCHK(hipMemsetAsync(dbad.get(), 0, nloci * 4, s));
+    LocBuildArgs a = ib.src;
+    a.trbeg = b.sh->d_trbeg; a.nloci = (uint32_t)nloci; a.ksize = g->ksize;
+    a.cnt = dcnt.get(); a.bad = dbad.get();
+    if (ib.graph) LAUNCH(k_gloc_count, dim3(2048), dim3(256), s, a);
+    else LAUNCH(k_loc_count, dim3(2048), dim3(256), s, a);
+    std::vector<uint32_t> cnt(nloci), bad(nloci);
+    HIPCHK(hipMemcpyAsync(cnt.data(), dcnt.get(), nloci * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    ib.tick("count");
+    std::vector<LocusDir>& dir = out->dir;
+    dir.resize(nloci);
+    std::vector<uint64_t> ebeg(nloci + 1, 0);
+    uint64_t at = 0, nimg = 0;
+    for (uint64_t l = 0; l < nloci; ++l) {
+        const uint32_t lg = loc_lgnb_for(cnt[l], g->ksize);
+        dir[l] = LocusDir{(uint32_t)(at / 16), 0u, lg, (uint32_t)g->out_beg[l]};
+        ebeg[l + 1] = ebeg[l];
+        if (!cnt[l] || lg > LOC_LG_MAX || cnt[l] > 0xFFF0u || at + loc_image_bytes(lg) > (16ull << 32) || g->out_beg[l + 1] - g->out_beg[l] >= ib.slot_max) continue;
+        dir[l].bytes = loc_image_bytes(lg);
+        at += dir[l].bytes;
+        ebeg[l + 1] += cnt[l];
+        ++nimg;
+    }
+    if (!nimg) return DBTK_OK;
+    const uint64_t nent = ebeg[nloci];
+    const uint32_t gstride = 2 * (1u << LOC_LG_MAX) + 2;
+    Scoped<LocusDir> d_dir; Scoped<uint8_t> d_arena;
+    Scoped<uint64_t> debeg, dekey, dskey, dnleft;
+    Scoped<uint32_t> depay, dspay;
+    Scoped<uint16_t> dgscr;
+    HIPCHK(hipMalloc(d_dir.out(), nloci * sizeof(LocusDir)));
+    HIPCHK(hipMalloc(d_arena.out(), at + 16));
+    HIPCHK(hipMalloc(debeg.out(), (nloci + 1) * 8));
+    HIPCHK(hipMalloc(dekey.out(), (nent + 1) * 8)); HIPCHK(hipMalloc(dskey.out(), (nent + 1) * 8));
+    HIPCHK(hipMalloc(depay.out(), (nent + 1) * 4)); HIPCHK(hipMalloc(dspay.out(), (nent + 1) * 4));
+    HIPCHK(hipMalloc(dgscr.out(), nloci * (uint64_t)gstride * 2));
+    HIPCHK(hipMalloc(dnleft.out(), 8));
+    HIPCHK(hipMemsetAsync(dnleft.get(), 0, 8, s));
+    HIPCHK(hipMemsetAsync(dcnt.get(), 0, nloci * 4, s));  // (now the gather cursors)
+    HIPCHK(hipMemcpyAsync(d_dir.get(), dir.data(), nloci * sizeof(LocusDir), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(debeg.get(), ebeg.data(), (nloci + 1) * 8, hipMemcpyHostToDevice, s));
+    a.dir = d_dir.get(); a.arena = d_arena.get(); a.ebeg = debeg.get(); a.ecur = dcnt.get(); a.ekey = dekey.get(); a.epay = depay.get(); a.skey = dskey.get(); a.spay = dspay.get();
+    a.gscr = dgscr.get(); a.gstride = gstride; a.nleft = dnleft.get();
+    ib.tick("directory + allocations");
+    if (ib.graph) LAUNCH(k_gloc_scatter, dim3(2048), dim3(256), s, a);
+    else LAUNCH(k_loc_scatter, dim3(2048), dim3(256), s, a);
+    ib.tick("scatter");
+    { const dbtk_status_t stp = launch_loc_place(a, nloci, s); if (stp) return stp; }
+    ib.tick("place");
+    uint64_t nleft = 0;
+    HIPCHK(hipMemcpyAsync(bad.data(), dbad.get(), nloci * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&nleft, dnleft.get(), 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    uint64_t nbad = 0;
+    for (uint64_t l = 0; l < nloci; ++l) if (bad[l] && dir[l].bytes) { dir[l].bytes = 0; ++nbad; }
+    if (nleft && ib.all_or_none) { for (uint64_t l = 0; l < nloci; ++l) dir[l].bytes = 0; nbad = nimg; }
+    if (nbad) HIPCHK(hipMemcpy(d_dir.get(), dir.data(), nloci * sizeof(LocusDir), hipMemcpyHostToDevice));
+    out->d_dir = std::move(d_dir); out->d_arena = std::move(d_arena);
+    out->arena_bytes = at; out->nimg = nimg - nbad; out->left_out = nleft;
+    return DBTK_OK;
+}
+
+// The index's images, from the finished plain index or from their sidecar.  DBTK_LOCUS=0: do without (the global tables answer every look-up).
+dbtk_status_t build_locus_images(const TableBuild& b) {
+    TableShare* sh = b.sh;
+    const dbtk_rpgg* g = b.g;
+    hipStream_t s = b.stream;
     const uint64_t nloci = g->nloci;
     if (const char* e = getenv("DBTK_LOCUS")) if (!atoi(e)) return DBTK_OK;
-    if (!nloci || g->keys.empty() || loc_lg_min(g->ksize) > LOC_LG_MAX || !c->T.consistent) return DBTK_OK;
+    if (!nloci || g->keys.empty() || loc_lg_min(g->ksize) > LOC_LG_MAX || !sh->T.consistent) return DBTK_OK;
     const uint64_t fp = rpgg_fingerprint(g);
     if (g->idx_cache_mode >= 1 && !g->idx_cache.empty()) {
-        const dbtk_status_t lc = load_locus_cache(c, fp);
+        const dbtk_status_t lc = load_locus_cache(b, fp);
         if (lc != DBTK_ERR_FORMAT) return lc;  // loaded (DBTK_OK), or a device error; DBTK_ERR_FORMAT: no usable file: build
     }
     static const bool verbose = getenv("DBTK_VERBOSE") != nullptr;
@@ -883,193 +987,89 @@ dbtk_status_t build_locus_images(dbtk_ctx* c) {
         tk0 = now;
     };
     tk("");
-    uint32_t *dcnt = nullptr, *dbad = nullptr;
-    HIPCHK(hipMalloc(&dcnt, nloci * 4));
-    HIPCHK(hipMalloc(&dbad, nloci * 4));
-    HIPCHK(hipMemsetAsync(dcnt, 0, nloci * 4, s));
-    HIPCHK(hipMemsetAsync(dbad, 0, nloci * 4, s));
-    LocBuildArgs a;
-    memset(&a, 0, sizeof(a));
-    a.idx = c->d_idx; a.nslots = (c->T.idx_mask + 1) * 4; a.vv = c->d_vv; a.trbeg = c->d_trbeg; a.nloci = (uint32_t)nloci; a.ksize = g->ksize;
-    a.cls = c->T.cls; a.cls_mask = c->T.cls_mask; a.cls_shift = c->T.cls_shift;
-    a.cnt = dcnt; a.bad = dbad;
-    LAUNCH(k_loc_count, dim3(2048), dim3(256), s, a);
-    std::vector<uint32_t> cnt(nloci), bad(nloci);
-    HIPCHK(hipMemcpyAsync(cnt.data(), dcnt, nloci * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    tk("count");
-    std::vector<LocusDir> dir(nloci);
-    std::vector<uint64_t> ebeg(nloci + 1, 0);
-    uint64_t at = 0, nimg = 0;
-    for (uint64_t l = 0; l < nloci; ++l) {
-        const uint32_t lg = loc_lgnb_for(cnt[l], g->ksize);
-        dir[l] = LocusDir{(uint32_t)(at / 16), 0u, lg, (uint32_t)g->out_beg[l]};
-        ebeg[l + 1] = ebeg[l];
-        if (!cnt[l] || lg > LOC_LG_MAX || cnt[l] > 0xFFF0u || at + loc_image_bytes(lg) > (16ull << 32)) continue;
-        dir[l].bytes = loc_image_bytes(lg);
-        at += dir[l].bytes;
-        ebeg[l + 1] += cnt[l];
-        ++nimg;
-    }
-    if (!nimg) { HIPCHK(hipFree(dcnt)); HIPCHK(hipFree(dbad)); return DBTK_OK; }
-    const uint64_t nent = ebeg[nloci];
-    const uint32_t gstride = 2 * (1u << LOC_LG_MAX) + 2;
-    uint64_t *debeg = nullptr, *dekey = nullptr, *dskey = nullptr, *dnleft = nullptr;
-    uint32_t *depay = nullptr, *dspay = nullptr;
-    uint16_t* dgscr = nullptr;
-    HIPCHK(hipMalloc(&c->d_ldir, nloci * sizeof(LocusDir)));
-    HIPCHK(hipMalloc(&c->d_limg, at + 16));
-    HIPCHK(hipMalloc(&debeg, (nloci + 1) * 8));
-    HIPCHK(hipMalloc(&dekey, (nent + 1) * 8)); HIPCHK(hipMalloc(&dskey, (nent + 1) * 8));
-    HIPCHK(hipMalloc(&depay, (nent + 1) * 4)); HIPCHK(hipMalloc(&dspay, (nent + 1) * 4));
-    HIPCHK(hipMalloc(&dgscr, nloci * (uint64_t)gstride * 2));
-    HIPCHK(hipMalloc(&dnleft, 8));
-    HIPCHK(hipMemsetAsync(dnleft, 0, 8, s));
-    HIPCHK(hipMemsetAsync(dcnt, 0, nloci * 4, s));  // (now the gather cursors)
-    HIPCHK(hipMemcpyAsync(c->d_ldir, dir.data(), nloci * sizeof(LocusDir), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(debeg, ebeg.data(), (nloci + 1) * 8, hipMemcpyHostToDevice, s));
-    a.dir = c->d_ldir; a.arena = c->d_limg; a.ebeg = debeg; a.ecur = dcnt; a.ekey = dekey; a.epay = depay; a.skey = dskey; a.spay = dspay;
-    a.gscr = dgscr; a.gstride = gstride; a.nleft = dnleft;
-    tk("directory + allocations");
-    LAUNCH(k_loc_scatter, dim3(2048), dim3(256), s, a);
-    tk("scatter");
-    { const dbtk_status_t stp = launch_loc_place(a, nloci, s); if (stp) return stp; }
-    tk("place");
-    uint64_t nleft = 0;
-    HIPCHK(hipMemcpyAsync(bad.data(), dbad, nloci * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&nleft, dnleft, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    uint64_t nbad = 0;
-    for (uint64_t l = 0; l < nloci; ++l) if (bad[l] && dir[l].bytes) { dir[l].bytes = 0; ++nbad; }
-    if (nbad) HIPCHK(hipMemcpy(c->d_ldir, dir.data(), nloci * sizeof(LocusDir), hipMemcpyHostToDevice));
-    HIPCHK(hipFree(debeg)); HIPCHK(hipFree(dekey)); HIPCHK(hipFree(dskey)); HIPCHK(hipFree(depay)); HIPCHK(hipFree(dspay)); HIPCHK(hipFree(dgscr)); HIPCHK(hipFree(dnleft));
+    ImageBuild ib{false, LocBuildArgs{}, ~0ull, false, tk};
+    ib.src.idx = sh->d_idx; ib.src.nslots = (sh->T.idx_mask + 1) * 4; ib.src.vv = sh->d_vv;
+    ib.src.cls = sh->T.cls; ib.src.cls_mask = sh->T.cls_mask; ib.src.cls_shift = sh->T.cls_shift;
+    ImagesBuilt im;
+    { const dbtk_status_t st = build_images(b, ib, &im); if (st) return st; }
+    if (!im.d_dir.get()) return DBTK_OK;
     tk("read-back + frees");
-    c->loc_left_out = nleft;
-    HIPCHK(hipFree(dcnt)); HIPCHK(hipFree(dbad));
-    c->limg_bytes = at; c->loc_nimg = nimg - nbad;
-    c->T.ldir = c->d_ldir; c->T.limg = c->d_limg;
-    if (g->idx_cache_mode == 2 && !g->idx_cache.empty()) write_locus_cache(c, fp, dir);
-    if (getenv("DBTK_VERBOSE")) fprintf(stderr, "locus images: %llu of %llu loci, %.1f MB, %llu keys left out\n", (unsigned long long)c->loc_nimg, (unsigned long long)nloci, at / 1e6, (unsigned long long)c->loc_left_out);
+    commit_locus_images(sh, nloci, im.d_dir.release(), im.d_arena.release(), im.arena_bytes, im.nimg, im.left_out, false);
+    if (g->idx_cache_mode == 2 && !g->idx_cache.empty()) write_locus_cache(b, fp, im.dir);
+    if (getenv("DBTK_VERBOSE")) fprintf(stderr, "locus images: %llu of %llu loci, %.1f MB, %llu keys left out\n", (unsigned long long)sh->loc_nimg, (unsigned long long)nloci, im.arena_bytes / 1e6, (unsigned long long)sh->loc_left_out);
     return DBTK_OK;
 }
 
 // The same images for the graph table (the lean walk kernel's; dbtk_locus.h: body_gloc_*), from the finished hashed table.  No sidecar.
-dbtk_status_t build_graph_images(dbtk_ctx* c) {
-    const dbtk_rpgg* g = c->g;
-    hipStream_t s = c->stream;
-    const uint64_t nloci = g->nloci;
+// (a group left out of a GRAPH image would read as "no node": unlike the index images there is no second look-up behind a miss, so
+// such an image is not used at all: all_or_none)
+dbtk_status_t build_graph_images(const TableBuild& b) {
+    TableShare* sh = b.sh;
+    const dbtk_rpgg* g = b.g;
     if (const char* e = getenv("DBTK_LOCUS")) if (!atoi(e)) return DBTK_OK;
-    if (!nloci || !c->d_gr || loc_lg_min(g->ksize) > LOC_LG_MAX) return DBTK_OK;
-    uint32_t *dcnt = nullptr, *dbad = nullptr;
-    HIPCHK(hipMalloc(&dcnt, nloci * 4));
-    HIPCHK(hipMalloc(&dbad, nloci * 4));
-    HIPCHK(hipMemsetAsync(dcnt, 0, nloci * 4, s));
-    HIPCHK(hipMemsetAsync(dbad, 0, nloci * 4, s));
-    LocBuildArgs a;
-    memset(&a, 0, sizeof(a));
-    a.gr = c->d_gr; a.gr_nslots = c->T.gr_mask + 1; a.trbeg = c->d_trbeg; a.nloci = (uint32_t)nloci; a.ksize = g->ksize;
-    a.cnt = dcnt; a.bad = dbad;
-    LAUNCH(k_gloc_count, dim3(2048), dim3(256), s, a);
-    std::vector<uint32_t> cnt(nloci), bad(nloci);
-    HIPCHK(hipMemcpyAsync(cnt.data(), dcnt, nloci * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    std::vector<LocusDir> dir(nloci);
-    std::vector<uint64_t> ebeg(nloci + 1, 0);
-    uint64_t at = 0, nimg = 0;
-    for (uint64_t l = 0; l < nloci; ++l) {
-        const uint32_t lg = loc_lgnb_for(cnt[l], g->ksize);
-        dir[l] = LocusDir{(uint32_t)(at / 16), 0u, lg, (uint32_t)g->out_beg[l]};
-        ebeg[l + 1] = ebeg[l];
-        if (!cnt[l] || lg > LOC_LG_MAX || cnt[l] > 0xFFF0u || at + loc_image_bytes(lg) > (16ull << 32) || g->out_beg[l + 1] - g->out_beg[l] >= GLOC_SLOT_MAX) continue;
-        dir[l].bytes = loc_image_bytes(lg);
-        at += dir[l].bytes;
-        ebeg[l + 1] += cnt[l];
-        ++nimg;
-    }
-    if (!nimg) { HIPCHK(hipFree(dcnt)); HIPCHK(hipFree(dbad)); return DBTK_OK; }
-    const uint64_t nent = ebeg[nloci];
-    const uint32_t gstride = 2 * (1u << LOC_LG_MAX) + 2;
-    uint64_t *debeg = nullptr, *dekey = nullptr, *dskey = nullptr, *dnleft = nullptr;
-    uint32_t *depay = nullptr, *dspay = nullptr;
-    uint16_t* dgscr = nullptr;
-    HIPCHK(hipMalloc(&c->d_gldir, nloci * sizeof(LocusDir)));
-    HIPCHK(hipMalloc(&c->d_glimg, at + 16));
-    HIPCHK(hipMalloc(&debeg, (nloci + 1) * 8));
-    HIPCHK(hipMalloc(&dekey, (nent + 1) * 8)); HIPCHK(hipMalloc(&dskey, (nent + 1) * 8));
-    HIPCHK(hipMalloc(&depay, (nent + 1) * 4)); HIPCHK(hipMalloc(&dspay, (nent + 1) * 4));
-    HIPCHK(hipMalloc(&dgscr, nloci * (uint64_t)gstride * 2));
-    HIPCHK(hipMalloc(&dnleft, 8));
-    HIPCHK(hipMemsetAsync(dnleft, 0, 8, s));
-    HIPCHK(hipMemsetAsync(dcnt, 0, nloci * 4, s));
-    HIPCHK(hipMemcpyAsync(c->d_gldir, dir.data(), nloci * sizeof(LocusDir), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(debeg, ebeg.data(), (nloci + 1) * 8, hipMemcpyHostToDevice, s));
-    a.dir = c->d_gldir; a.arena = c->d_glimg; a.ebeg = debeg; a.ecur = dcnt; a.ekey = dekey; a.epay = depay; a.skey = dskey; a.spay = dspay;
-    a.gscr = dgscr; a.gstride = gstride; a.nleft = dnleft;
-    LAUNCH(k_gloc_scatter, dim3(2048), dim3(256), s, a);
-    { const dbtk_status_t stp = launch_loc_place(a, nloci, s); if (stp) return stp; }
-    uint64_t nleft = 0;
-    HIPCHK(hipMemcpyAsync(bad.data(), dbad, nloci * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&nleft, dnleft, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    uint64_t nbad = 0;
-    for (uint64_t l = 0; l < nloci; ++l) if ((bad[l] || false) && dir[l].bytes) { dir[l].bytes = 0; ++nbad; }
-    // (a group left out of a GRAPH image would read as "no node": unlike the index images there is no second look-up behind a miss, so
-    // such an image is not used at all)
-    if (nleft) { for (uint64_t l = 0; l < nloci; ++l) dir[l].bytes = 0; nbad = nimg; }
-    if (nbad) HIPCHK(hipMemcpy(c->d_gldir, dir.data(), nloci * sizeof(LocusDir), hipMemcpyHostToDevice));
-    HIPCHK(hipFree(debeg)); HIPCHK(hipFree(dekey)); HIPCHK(hipFree(dskey)); HIPCHK(hipFree(depay)); HIPCHK(hipFree(dspay)); HIPCHK(hipFree(dgscr)); HIPCHK(hipFree(dnleft));
-    HIPCHK(hipFree(dcnt)); HIPCHK(hipFree(dbad));
-    c->glimg_bytes = at;
-    c->T.gldir = c->d_gldir; c->T.glimg = c->d_glimg;
-    if (getenv("DBTK_VERBOSE")) fprintf(stderr, "graph images: %llu of %llu loci, %.1f MB\n", (unsigned long long)(nimg - nbad), (unsigned long long)nloci, at / 1e6);
+    if (!g->nloci || !sh->d_gr || loc_lg_min(g->ksize) > LOC_LG_MAX) return DBTK_OK;
+    ImageBuild ib{true, LocBuildArgs{}, GLOC_SLOT_MAX, true, [](const char*) {}};
+    ib.src.gr = sh->d_gr; ib.src.gr_nslots = sh->T.gr_mask + 1;
+    ImagesBuilt im;
+    { const dbtk_status_t st = build_images(b, ib, &im); if (st) return st; }
+    if (!im.d_dir.get()) return DBTK_OK;
+    sh->d_gldir = im.d_dir.release(); sh->d_glimg = im.d_arena.release();
+    sh->T.gldir = sh->d_gldir; sh->T.glimg = sh->d_glimg;
+    sh->bytes[TB_GLIMG] = im.arena_bytes;
+    if (getenv("DBTK_VERBOSE")) fprintf(stderr, "graph images: %llu of %llu loci, %.1f MB\n", (unsigned long long)im.nimg, (unsigned long long)g->nloci, im.arena_bytes / 1e6);
     return DBTK_OK;
 }
 
-// Graph table (dbtk_tables.h: GrSlot) from graphDB's flat arrays + the TR k-mers: graph pass, then TR pass.
-dbtk_status_t build_graph_table(dbtk_ctx* c) {
-    const dbtk_rpgg* g = c->g;
-    hipStream_t s = c->stream;
+// Graph table (dbtk_tables.h: GrSlot) from graphDB's flat arrays + the TR k-mers: graph pass, then TR pass.  Into a live share: each
+// table is the share's (pointer, T, bytes) only once it is complete.
+dbtk_status_t build_graph_table(const TableBuild& b) {
+    TableShare* sh = b.sh;
+    const dbtk_rpgg* g = b.g;
+    hipStream_t s = b.stream;
     const uint64_t nloci = g->nloci, ngr = g->gr_ks.size(), ntrf = g->tr_ks.size();
     for (uint64_t l = 0; l < nloci; ++l)
         if (g->out_beg[l + 1] - g->out_beg[l] >= (1ull << (32 - GR_SLOT_SHIFT))) { set_error("a locus has more than 2^21 TR k-mers: graph table slot field too small"); return DBTK_ERR_UNSUPPORTED; }
     const uint64_t cap = pow2_at_least(ngr + ngr / 2 + 2 * ntrf + 2);  // > the entries whatever the files hold; the two strands of a node share one, so the load is ~0.2-0.35
-    HIPCHK(hipMalloc(&c->d_gr, cap * sizeof(GrSlot)));
-    c->tb_gr = cap * sizeof(GrSlot);
-    HIPCHK(hipMemsetAsync(c->d_gr, 0xFF, cap * sizeof(GrSlot), s));
-    std::vector<uint64_t> beg(nloci + 1, 0);
-    uint64_t *dks = nullptr, *dbeg = nullptr, *dslot = nullptr, *dn = nullptr;
-    uint8_t* dms = nullptr;
-    const uint64_t nmax = ngr > ntrf ? ngr : ntrf;
-    HIPCHK(hipMalloc(&dks, (nmax + 1) * 8));
-    HIPCHK(hipMalloc(&dms, ngr + 1));
-    HIPCHK(hipMalloc(&dslot, (ntrf + 1) * 8));
-    HIPCHK(hipMalloc(&dbeg, (nloci + 1) * 8));
-    HIPCHK(hipMalloc(&dn, 8));
-    HIPCHK(hipMemsetAsync(dn, 0, 8, s));
-    GrBuildArgs a{c->d_gr, cap - 1, 64 - log2u(cap), g->ksize, dks, dms, dbeg, (uint32_t)nloci, nullptr, c->d_trbeg, ngr, dn};
-    if (ngr) {
-        for (uint64_t l = 0; l < nloci; ++l) beg[l + 1] = beg[l] + g->gr_cnt[l];
-        HIPCHK(hipMemcpyAsync(dks, g->gr_ks.data(), ngr * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(dms, g->gr_ms.data(), ngr, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(dbeg, beg.data(), (nloci + 1) * 8, hipMemcpyHostToDevice, s));
-        LAUNCH(k_gr_insert, dim3(2048), dim3(256), s, a);
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    if (ntrf) {
-        for (uint64_t l = 0; l < nloci; ++l) beg[l + 1] = beg[l] + g->tr_cnt[l];
-        HIPCHK(hipMemcpyAsync(dks, g->tr_ks.data(), ntrf * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(dslot, g->out_slot.data(), ntrf * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(dbeg, beg.data(), (nloci + 1) * 8, hipMemcpyHostToDevice, s));
-        a.ms = nullptr; a.outslot = dslot; a.n = ntrf;
-        LAUNCH(k_gr_insert, dim3(2048), dim3(256), s, a);
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    HIPCHK(hipGetLastError());
     uint64_t nent = 0;  // entries of the table: the two strands of a node share one, most TR k-mers are nodes already
-    HIPCHK(hipMemcpy(&nent, dn, 8, hipMemcpyDeviceToHost));
-    if (nent == 0 || nent > ngr + ntrf) nent = ngr + ntrf;
-    HIPCHK(hipFree(dks)); HIPCHK(hipFree(dms)); HIPCHK(hipFree(dslot)); HIPCHK(hipFree(dbeg)); HIPCHK(hipFree(dn));
-    c->T.gr = c->d_gr; c->T.gr_mask = cap - 1; c->T.gr_shift = 64 - log2u(cap);
+    {
+        Scoped<GrSlot> gr;
+        HIPCHK(hipMalloc(gr.out(), cap * sizeof(GrSlot)));
+        HIPCHK(hipMemsetAsync(gr.get(), 0xFF, cap * sizeof(GrSlot), s));
+        std::vector<uint64_t> beg(nloci + 1, 0);
+        Scoped<uint64_t> dks, dbeg, dslot, dn;
+        Scoped<uint8_t> dms;
+        const uint64_t nmax = ngr > ntrf ? ngr : ntrf;
+        HIPCHK(hipMalloc(dks.out(), (nmax + 1) * 8));
+        HIPCHK(hipMalloc(dms.out(), ngr + 1));
+        HIPCHK(hipMalloc(dslot.out(), (ntrf + 1) * 8));
+        HIPCHK(hipMalloc(dbeg.out(), (nloci + 1) * 8));
+        HIPCHK(hipMalloc(dn.out(), 8));
+        HIPCHK(hipMemsetAsync(dn.get(), 0, 8, s));
+        GrBuildArgs a{gr.get(), cap - 1, 64 - log2u(cap), g->ksize, dks.get(), dms.get(), dbeg.get(), (uint32_t)nloci, nullptr, sh->d_trbeg, ngr, dn.get()};
+        if (ngr) {
+            for (uint64_t l = 0; l < nloci; ++l) beg[l + 1] = beg[l] + g->gr_cnt[l];
+            HIPCHK(hipMemcpyAsync(dks.get(), g->gr_ks.data(), ngr * 8, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(dms.get(), g->gr_ms.data(), ngr, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(dbeg.get(), beg.data(), (nloci + 1) * 8, hipMemcpyHostToDevice, s));
+            LAUNCH(k_gr_insert, dim3(2048), dim3(256), s, a);
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        if (ntrf) {
+            for (uint64_t l = 0; l < nloci; ++l) beg[l + 1] = beg[l] + g->tr_cnt[l];
+            HIPCHK(hipMemcpyAsync(dks.get(), g->tr_ks.data(), ntrf * 8, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(dslot.get(), g->out_slot.data(), ntrf * 8, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(dbeg.get(), beg.data(), (nloci + 1) * 8, hipMemcpyHostToDevice, s));
+            a.ms = nullptr; a.outslot = dslot.get(); a.n = ntrf;
+            LAUNCH(k_gr_insert, dim3(2048), dim3(256), s, a);
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy(&nent, dn.get(), 8, hipMemcpyDeviceToHost));
+        if (nent == 0 || nent > ngr + ntrf) nent = ngr + ntrf;
+        sh->d_gr = gr.release();
+        sh->bytes[TB_GR] = cap * sizeof(GrSlot);
+        sh->T.gr = sh->d_gr; sh->T.gr_mask = cap - 1; sh->T.gr_shift = 64 - log2u(cap);
+    }
     {   // the lean walk kernel's minimizer-grouped copy of the table, for the values of k its bucket form exists for (DBTK_MZ=0: do without)
         bool on = true;
         if (const char* e = getenv("DBTK_MZ")) on = atoi(e) != 0;
@@ -1079,45 +1079,51 @@ dbtk_status_t build_graph_table(dbtk_ctx* c) {
             if (const char* e = getenv("DBTK_GRMZ_SPARSITY")) { const long v = atol(e); if (v >= 1 && v <= 64) gper = (uint64_t)v; }
             uint64_t nb = pow2_at_least(nent * gper / 8 + 8);
             if (nb > (1ull << 28)) nb = 1ull << 28;
-            HIPCHK(hipMalloc(&c->d_grmz, nb * sizeof(MzBucket)));
-            c->tb_grmz = nb * sizeof(MzBucket);
-            LAUNCH(k_mz_fill, dim3(2048), dim3(256), s, reinterpret_cast<uint64_t*>(c->d_grmz), nb * 16, 1);
-            GrMzBuildArgs ga{c->d_gr, cap, c->d_grmz, (uint32_t)(nb - 1), g->ksize, m};
+            Scoped<MzBucket> grmz;
+            HIPCHK(hipMalloc(grmz.out(), nb * sizeof(MzBucket)));
+            LAUNCH(k_mz_fill, dim3(2048), dim3(256), s, reinterpret_cast<uint64_t*>(grmz.get()), nb * 16, 1);
+            GrMzBuildArgs ga{sh->d_gr, cap, grmz.get(), (uint32_t)(nb - 1), g->ksize, m};
             LAUNCH(k_grmz_insert, dim3(2048), dim3(256), s, ga);
             HIPCHK(hipStreamSynchronize(s));
-            c->T.grmz = c->d_grmz; c->T.grmz_mask = nb - 1;
+            sh->d_grmz = grmz.release();
+            sh->bytes[TB_GRMZ] = nb * sizeof(MzBucket);
+            sh->T.grmz = sh->d_grmz; sh->T.grmz_mask = nb - 1;
         }
     }
-    return build_graph_images(c);
+    return build_graph_images(b);
 }
 
-// (key, locus) -> value table from per-locus arrays (tre edges: value unused; bait: min << 8 | max)
-dbtk_status_t build_kl_table(dbtk_ctx* c, const std::vector<uint64_t>& cnt, const std::vector<uint64_t>& ks,
-                             const std::vector<uint16_t>* vals, ClsSlot** out, uint64_t* mask, uint32_t* shift) {
-    hipStream_t s = c->stream;
-    const uint64_t nloci = c->g->nloci, n = ks.size();
+// (key, locus) -> value table from per-locus arrays (tre edges: value unused; bait: min << 8 | max): *out and its place in T, once complete
+dbtk_status_t build_kl_table(const TableBuild& b, const std::vector<uint64_t>& cnt, const std::vector<uint64_t>& ks,
+                             const std::vector<uint16_t>* vals, ClsSlot** out, const ClsSlot** tout, uint64_t* mask, uint32_t* shift) {
+    hipStream_t s = b.stream;
+    const uint64_t nloci = b.g->nloci, n = ks.size();
     const uint64_t cap = pow2_at_least(2 * n + 2);
-    HIPCHK(hipMalloc(out, cap * sizeof(ClsSlot)));
-    HIPCHK(hipMemsetAsync(*out, 0xFF, cap * sizeof(ClsSlot), s));
-    *mask = cap - 1;
-    *shift = 64 - log2u(cap);
-    if (!n) { HIPCHK(hipStreamSynchronize(s)); return DBTK_OK; }
-    std::vector<uint64_t> beg(nloci + 1, 0), v64(n, 0);
-    for (uint64_t l = 0; l < nloci; ++l) beg[l + 1] = beg[l] + cnt[l];
-    if (vals) for (uint64_t i = 0; i < n; ++i) v64[i] = (*vals)[i];
-    uint64_t *dks = nullptr, *dbeg = nullptr, *dval = nullptr, *dn = nullptr;
-    HIPCHK(hipMalloc(&dks, n * 8));
-    HIPCHK(hipMalloc(&dval, n * 8));
-    HIPCHK(hipMalloc(&dbeg, (nloci + 1) * 8));
-    HIPCHK(hipMalloc(&dn, 8));
-    HIPCHK(hipMemsetAsync(dn, 0, 8, s));
-    HIPCHK(hipMemcpyAsync(dks, ks.data(), n * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dval, v64.data(), n * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dbeg, beg.data(), (nloci + 1) * 8, hipMemcpyHostToDevice, s));
-    ClsBuildArgs a{*out, cap - 1, 64 - log2u(cap), dks, dbeg, (uint32_t)nloci, dval, n, dn};
-    LAUNCH(k_cls_insert, dim3(1024), dim3(256), s, a);
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipFree(dks)); HIPCHK(hipFree(dval)); HIPCHK(hipFree(dbeg)); HIPCHK(hipFree(dn));
+    Scoped<ClsSlot> tab;
+    HIPCHK(hipMalloc(tab.out(), cap * sizeof(ClsSlot)));
+    HIPCHK(hipMemsetAsync(tab.get(), 0xFF, cap * sizeof(ClsSlot), s));
+    if (!n) {
+        HIPCHK(hipStreamSynchronize(s));
+    } else {
+        std::vector<uint64_t> beg(nloci + 1, 0), v64(n, 0);
+        for (uint64_t l = 0; l < nloci; ++l) beg[l + 1] = beg[l] + cnt[l];
+        if (vals) for (uint64_t i = 0; i < n; ++i) v64[i] = (*vals)[i];
+        Scoped<uint64_t> dks, dbeg, dval, dn;
+        HIPCHK(hipMalloc(dks.out(), n * 8));
+        HIPCHK(hipMalloc(dval.out(), n * 8));
+        HIPCHK(hipMalloc(dbeg.out(), (nloci + 1) * 8));
+        HIPCHK(hipMalloc(dn.out(), 8));
+        HIPCHK(hipMemsetAsync(dn.get(), 0, 8, s));
+        HIPCHK(hipMemcpyAsync(dks.get(), ks.data(), n * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dval.get(), v64.data(), n * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dbeg.get(), beg.data(), (nloci + 1) * 8, hipMemcpyHostToDevice, s));
+        ClsBuildArgs a{tab.get(), cap - 1, 64 - log2u(cap), dks.get(), dbeg.get(), (uint32_t)nloci, dval.get(), n, dn.get()};
+        LAUNCH(k_cls_insert, dim3(1024), dim3(256), s, a);
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    *out = tab.release();
+    *tout = *out; *mask = cap - 1; *shift = 64 - log2u(cap);
+    b.sh->bytes[TB_GATES] += cap * sizeof(ClsSlot);
     return DBTK_OK;
 }
 
@@ -1690,8 +1696,12 @@ int dbtk_ctx_table_bytes(dbtk_ctx_t* c, const char** names, uint64_t* bytes, int
     if (!c || !names || !bytes || !c->share) return 0;
     static const char* nm[13] = {"index", "presence_filter", "class_table", "index_by_minimizer", "index_overflow", "graph", "graph_by_minimizer",
                                  "index_images", "index_images:from_cache", "vv+qc+perm+trbeg", "gates(tre,bait)", "total", "graph_images"};
+    static_assert(TB_COUNT == 13, "names and order are an ABI");
+    const uint64_t* tb = c->share->bytes;
+    uint64_t total = 0;  // (every table; TB_LIMG_CACHED is a flag)
+    for (int i = 0; i < TB_COUNT; ++i) if (i != TB_LIMG_CACHED && i != TB_TOTAL) total += tb[i];
     int n = 0;
-    for (int i = 0; i < 13 && n < cap; ++i) { names[n] = nm[i]; bytes[n] = c->share->bytes[i]; ++n; }
+    for (int i = 0; i < TB_COUNT && n < cap; ++i) { names[n] = nm[i]; bytes[n] = i == TB_TOTAL ? total : tb[i]; ++n; }
     // the context's own table of novel edges (params.bubbles = DBTK_BUBBLES_TABLE): not one of the shared tables, not in "total"
     if (c->d_bub && n < cap) { names[n] = "bubble_table"; bytes[n] = c->bub_slots * sizeof(BubSlot); ++n; }
     return n;
@@ -1911,42 +1921,19 @@ static dbtk_status_t dbtk_ctx_create_impl(const dbtk_rpgg_t* h, const dbtk_param
             const auto key = std::make_pair(h->uid, device_id);
             auto it = g_shares.find(key);
             TableShare* sh = it != g_shares.end() ? it->second : nullptr;
-            auto to_share = [&](TableShare* t) {
-                t->d_idx = c->d_idx; t->d_flt = c->d_flt; t->flt_words = c->flt_words; t->d_trbeg = c->d_trbeg; t->d_cls = c->d_cls; t->d_mz = c->d_mz; t->d_ovf = c->d_ovf;
-                t->d_gr = c->d_gr; t->d_grmz = c->d_grmz; t->d_ldir = c->d_ldir; t->d_limg = c->d_limg; t->d_gldir = c->d_gldir; t->d_glimg = c->d_glimg; t->d_vv = c->d_vv; t->d_qc = c->d_qc; t->d_perm = c->d_perm; t->d_tre = c->d_tre; t->d_bait = c->d_bait;
-                t->T = c->T; t->consistent = c->consistent;
-                // HBM bytes per table: what this context built is added to what the share already holds
-                const uint64_t mine[9] = {c->tb_idx, c->tb_flt, c->tb_cls, c->tb_mz, c->tb_ovf, c->tb_gr, c->tb_grmz, c->limg_bytes, c->loc_from_cache ? 1u : 0u};
-                for (int i = 0; i < 9; ++i) if (mine[i]) t->bytes[i] = mine[i];
-                if (c->glimg_bytes) t->bytes[12] = c->glimg_bytes;
-                t->bytes[9] = (h->vv.size() + 1) * 4 + (h->qc.empty() ? 0 : h->nloci) + ((size_t)NHMAX * (NHMAX + 1) / 2 + 1) * 2 + (h->nloci + 1) * 4 + (c->d_ldir ? h->nloci * sizeof(LocusDir) : 0);
-                t->bytes[10] = (c->d_tre ? (c->T.tre_mask + 1) * sizeof(ClsSlot) : 0) + (c->d_bait ? (c->T.bait_mask + 1) * sizeof(ClsSlot) : 0);
-                t->bytes[11] = 0;
-                for (int i = 0; i < 13; ++i) if (i != 8 && i != 11) t->bytes[11] += t->bytes[i];
-            };
-            if (!sh) {
-                if ((st = build_tables(c))) break;
+            if (!sh) {  // the first context: a share of its own making, everybody's once the tables stand
                 sh = new TableShare;
-                to_share(sh);
+                if ((st = build_tables(TableBuild{sh, h, c->stream}))) { drop_share(sh); break; }
                 g_shares[key] = sh;
-            } else {
-                c->d_idx = sh->d_idx; c->d_flt = sh->d_flt; c->flt_words = sh->flt_words; c->d_trbeg = sh->d_trbeg; c->d_cls = sh->d_cls; c->d_mz = sh->d_mz; c->d_ovf = sh->d_ovf;
-                c->d_gr = sh->d_gr; c->d_grmz = sh->d_grmz; c->d_ldir = sh->d_ldir; c->d_limg = sh->d_limg; c->d_gldir = sh->d_gldir; c->d_glimg = sh->d_glimg; c->d_vv = sh->d_vv; c->d_qc = sh->d_qc; c->d_perm = sh->d_perm; c->d_tre = sh->d_tre; c->d_bait = sh->d_bait;
-                c->T = sh->T; c->consistent = sh->consistent;
             }
             c->share = sh;
             ++sh->refs;
-            // optional tables, by the first context that needs them (only a walking context pays for the graph table)
-            if (p->threading == DBTK_THREADING_V13 && !c->d_gr) { if ((st = build_graph_table(c))) break; }
-            if (p->bubbles && !c->d_tre) {
-                if ((st = build_kl_table(c, h->tre_cnt, h->tre_ks, nullptr, &c->d_tre, &c->T.tre_mask, &c->T.tre_shift))) break;
-                c->T.tre = c->d_tre;
-            }
-            if (p->bait && !c->d_bait) {
-                if ((st = build_kl_table(c, h->bt_cnt, h->bt_ks, &h->bt_vs, &c->d_bait, &c->T.bait_mask, &c->T.bait_shift))) break;
-                c->T.bait = c->d_bait;
-            }
-            to_share(sh);
+            // optional tables, by the first context that needs them (only a walking context pays for the graph table): straight into the share
+            const TableBuild b{sh, h, c->stream};
+            if (p->threading == DBTK_THREADING_V13 && !sh->d_gr) { if ((st = build_graph_table(b))) break; }
+            if (p->bubbles && !sh->d_tre) { if ((st = build_kl_table(b, h->tre_cnt, h->tre_ks, nullptr, &sh->d_tre, &sh->T.tre, &sh->T.tre_mask, &sh->T.tre_shift))) break; }
+            if (p->bait && !sh->d_bait) { if ((st = build_kl_table(b, h->bt_cnt, h->bt_ks, &h->bt_vs, &sh->d_bait, &sh->T.bait, &sh->T.bait_mask, &sh->T.bait_shift))) break; }
+            c->T = sh->T;
         }
         if (st) break;
         chk(hipStreamSynchronize(c->stream), "sync");
@@ -2122,7 +2109,7 @@ static dbtk_status_t dbtk_align_batch_impl(dbtk_ctx_t* c, const uint8_t* seq, co
 static dbtk_status_t dbtk_thread_batch_impl(dbtk_ctx_t* c, const uint8_t* seq, const uint64_t* off, const uint32_t* loci, uint64_t nreads,
                                 dbtk_thread_rec_t* recs) {
     if (!c || !off || !loci || !recs || (!seq && nreads)) { set_error("null argument"); return DBTK_ERR_ARG; }
-    if (!c->d_gr) { set_error("the RPGG handle holds no graph (DBTK_LOAD_GRAPH)"); return DBTK_ERR_ARG; }
+    if (!c->T.gr) { set_error("the RPGG handle holds no graph (DBTK_LOAD_GRAPH)"); return DBTK_ERR_ARG; }
     if (nreads >= 0x7FFFFFFFull) { set_error("too many reads"); return DBTK_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
     for (uint64_t r = 0; r < nreads; ++r) {
