@@ -673,7 +673,8 @@ class Dosage:
 
 EXPORTS_KCP = [
     "dbtk_kcp_api_version", "dbtk_kcp_create", "dbtk_kcp_free", "dbtk_kcp_add", "dbtk_kcp_count", "dbtk_kcp_read", "dbtk_kcp_write", "dbtk_kcp_reset",
-    "dbtk_kcp_stats", "dbtk_kcp_times", "dbtk_kcp_add_device",
+    "dbtk_kcp_stats", "dbtk_kcp_times", "dbtk_kcp_add_device", "dbtk_kcp_set_tp_only", "dbtk_kcp_fps_begin", "dbtk_kcp_fps_apply", "dbtk_kcp_fps_count", "dbtk_kcp_fps_read",
+    "dbtk_kcp_fps_write", "dbtk_kcp_fps_times", "dbtk_kcp_fps_free", "dbtk_kcp_text_stats",
 ]
 
 
@@ -756,10 +757,85 @@ class Kcp:
         self._lib._chk(self._lib.L.dbtk_kcp_times(self.h, C.byref(ms), C.byref(n)))
         return float(ms.value), int(n.value)
 
+    def set_tp_only(self, on):
+        """Switches the class filter between batches (what the table holds stays)."""
+        self._lib.L.dbtk_kcp_set_tp_only.argtypes = [C.c_void_p, C.c_int]
+        self._lib._chk(self._lib.L.dbtk_kcp_set_tp_only(self.h, 1 if on else 0))
+
     def close(self):
         if self.h:
             self._lib.L.dbtk_kcp_free(self.h)
             self.h = None
+
+
+class KcpFps:
+    """The FP-specific filter of include/dbtk_kcp.h (`baitBuilder v2` on the device): the FP entries of `kcp` as candidates in HBM,
+    filtered against TP tables where they lie."""
+
+    def __init__(self, kcp):
+        self._lib = kcp._lib
+        L = self._lib.L
+        u8 = C.POINTER(C.c_uint8)
+        L.dbtk_kcp_fps_begin.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.dbtk_kcp_fps_apply.argtypes = [C.c_void_p, C.c_void_p]
+        L.dbtk_kcp_fps_count.argtypes = [C.c_void_p, u64p, u64p]
+        L.dbtk_kcp_fps_read.argtypes = [C.c_void_p, u32p, u64p, u8, u8, C.c_uint64]
+        L.dbtk_kcp_fps_write.argtypes = [C.c_void_p, C.c_char_p]
+        L.dbtk_kcp_fps_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), u64p]
+        L.dbtk_kcp_fps_free.argtypes = [C.c_void_p]
+        L.dbtk_kcp_fps_free.restype = None
+        self.h = C.c_void_p()
+        self._lib._chk(L.dbtk_kcp_fps_begin(kcp.h, C.byref(self.h)))
+
+    def apply(self, kcp_tp):
+        self._lib._chk(self._lib.L.dbtk_kcp_fps_apply(self.h, kcp_tp.h))
+
+    def count(self):
+        """(candidates, of them alive)"""
+        n, a = C.c_uint64(), C.c_uint64()
+        self._lib._chk(self._lib.L.dbtk_kcp_fps_count(self.h, C.byref(n), C.byref(a)))
+        return int(n.value), int(a.value)
+
+    def read(self):
+        """{(locus, kmer): (mi, ma)} of the living candidates; the library returns them sorted by (locus, k-mer)."""
+        cap = self.count()[1]
+        loci, kmers = np.empty(cap, np.uint32), np.empty(cap, np.uint64)
+        mi, ma = np.empty(cap, np.uint8), np.empty(cap, np.uint8)
+        u8 = C.POINTER(C.c_uint8)
+        self._lib._chk(self._lib.L.dbtk_kcp_fps_read(self.h, _ptr(loci, u32p), _ptr(kmers, u64p), _ptr(mi, u8), _ptr(ma, u8), cap))
+        keys = list(zip(loci.tolist(), kmers.tolist()))
+        if keys != sorted(keys):
+            raise RuntimeError("dbtk_kcp_fps_read: candidates out of order")
+        return dict(zip(keys, zip(mi.tolist(), ma.tolist())))
+
+    def write(self, path):
+        self._lib._chk(self._lib.L.dbtk_kcp_fps_write(self.h, os.fsencode(path)))
+
+    def times(self):
+        """(milliseconds in k_kcp_fps_apply, living candidates looked up)"""
+        ms, n = C.c_double(), C.c_uint64()
+        self._lib._chk(self._lib.L.dbtk_kcp_fps_times(self.h, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
+
+    def close(self):
+        if self.h:
+            self._lib.L.dbtk_kcp_fps_free(self.h)
+            self.h = None
+
+
+def kcp_text_stats(lib, n, sm, sq, device=0):
+    """(mean, sd) as float32 arrays: the floats `ktools fps` parses from the profile line of an entry with these moments, computed
+    on the device (dbtk_kcp_text_stats)."""
+    n = np.ascontiguousarray(n, np.uint32)
+    sm = np.ascontiguousarray(sm, np.uint64)
+    sq = np.ascontiguousarray(sq, np.uint64)
+    if not (len(n) == len(sm) == len(sq)):
+        raise ValueError("one n, sum and sumsq per entry")
+    mean, sd = np.empty(len(n), np.float32), np.empty(len(n), np.float32)
+    fp = C.POINTER(C.c_float)
+    lib.L.dbtk_kcp_text_stats.argtypes = [C.c_int, u32p, u64p, u64p, C.c_uint64, fp, fp]
+    lib._chk(lib.L.dbtk_kcp_text_stats(int(device), _ptr(n, u32p), _ptr(sm, u64p), _ptr(sq, u64p), len(n), _ptr(mean, fp), _ptr(sd, fp)))
+    return mean, sd
 
 
 EXPORTS_SIM = [

@@ -7,6 +7,7 @@ NAN32 = 0xFFFFFFFF
 ABI_VERSION = 11
 KCP_API_VERSION = 1  # include/dbtk_kcp.h: DBTK_KCP_API_VERSION (a version of its own beside ABI_VERSION)
 KCP_TP_ONLY = 1      # dbtk_kcp_create flags
+KCP_FPS_MI_NONE, KCP_FPS_MA_NONE = 255, 0  # dbtk_kcp_fps_read: (mi, ma) of a living candidate that no TP table held
 SIM_API_VERSION = 1  # include/dbtk_sim.h: DBTK_SIM_API_VERSION
 BUBBLES_LOG, BUBBLES_TABLE = 1, 2  # params.bubbles: event log replayed on the host (reference order) | counts in a device table
 ALN_TEXT = 4  # params.aln | ALN_TEXT: alignment records in text form (dbtk_ctx_aln_text)

@@ -107,6 +107,8 @@ struct Opts {
     std::vector<std::string> dosage;   // --dosage IKMER.META OUT.dosage.tsv OUT.bias.tsv: the bias-corrected per-locus dosages, without the matrix
     std::string baitProfile;           // --bait-profile OUTPREF: the k-mer count profiles of the assigned pairs (-s), counted in a table in HBM
     bool tpOnly = false;               // --tp-only: the true-positive profile alone (baitBuilder's -tp)
+    std::string baitFps;               // --bait-fps OUT: the FP-specific bait k-mers (baitBuilder v2 / ktools fps), filtered in HBM from the table(s) of the run
+    std::vector<std::pair<std::string, size_t>> genomes;  // --genome NAME: (NAME, index of the first --sim that follows it)
     // --sim ASSEMBLY BED (any number of times): the reads are tiled from the assemblies on the device, sim_reads -pe -no-err's
     std::vector<std::pair<std::string, std::string>> sim;
     uint64_t simFs = 500, simRlen = 150, simC = 15, simMl = 50000;  // --sim-fs / --sim-rlen / --sim-c / --sim-ml
@@ -146,6 +148,12 @@ void usage() {
             "                         PREF.FP_pf.txt, what `baitBuilder v1.pf` makes from the kam text (input of `ktools fps`).  With -ka no kam\n"
             "                         text is written at all.  One GPU, host reader; not with --cohort, -e, -g/-gc/-gcc, --ingest-shards\n"
             "  --tp-only              with --bait-profile: PREF.TP_pf.txt alone\n"
+            "  --bait-fps <OUT>       with -s 1|2 or --sim: the FP-specific bait k-mers, the file `ktools fps` makes from the profiles (input of\n"
+            "                         `ktools serialize-bt`), filtered on the GPU from the table the profiles are counted in: no profile text is\n"
+            "                         written or parsed.  May stand beside --bait-profile; not with --tp-only or anything --bait-profile refuses\n"
+            "  --genome <NAME>        with --bait-fps and --sim: every --sim that follows belongs to genome NAME.  The first genome is counted in\n"
+            "                         both classes and its FP k-mers become the candidates; every genome's TP profile filters them in turn (one\n"
+            "                         table in HBM at a time), OUT is written after the last.  Not with --bait-profile\n"
             "Algorithm:\n"
             "  -k <INT> [21]  -kf <N> <M> [4 1]  -cth <INT> [10]  -c <INT> [40]  -qth <INT> [20]  -qc <FILE>  -b [FILE]\n"
             "Execution:\n"
@@ -420,6 +428,8 @@ int main(int argc, char* argv[]) {
         else if (a == "--bu-table") o.buTable = true;
         else if (a == "--bait-profile") o.baitProfile = need(++argi);
         else if (a == "--tp-only") o.tpOnly = true;
+        else if (a == "--bait-fps") o.baitFps = need(++argi);
+        else if (a == "--genome") o.genomes.emplace_back(need(++argi), o.sim.size());
         else if (a == "--sim") { const std::string fa = need(++argi); o.sim.emplace_back(fa, need(++argi)); }
         else if (a == "--sim-fs" || a == "--sim-rlen" || a == "--sim-c" || a == "--sim-ml") {
             if (o.simParam.empty()) o.simParam = a;
@@ -469,16 +479,28 @@ int main(int argc, char* argv[]) {
     std::vector<CohortSample> samples;
     if (o.buTable && !o.outputBubbles) refuse("--bu-table needs -bu");
     // --bait-profile: the pairs it counts are those of the kam records of -s, on the one pipeline that makes them
-    const bool profile = !o.baitProfile.empty();
-    if (o.tpOnly && !profile) refuse("--tp-only needs --bait-profile");
+    // --bait-fps: the same table, filtered where it lies at the end of the run (or, with --genome, after every genome)
+    const bool profileFiles = !o.baitProfile.empty(), baitFps = !o.baitFps.empty();
+    const bool profile = profileFiles || baitFps;
+    if (baitFps && o.tpOnly) refuse("--bait-fps cannot be combined with --tp-only: its candidates are the false-positive class");
+    if (o.tpOnly && !profileFiles) refuse("--tp-only needs --bait-profile");
+    if (!o.genomes.empty()) {
+        if (!baitFps) refuse("--genome needs --bait-fps");
+        if (!sim) refuse("--genome needs --sim: a genome is the assemblies that follow it");
+        if (profileFiles) refuse("--genome cannot be combined with --bait-profile (the table is emptied after every genome: there is no one profile to write)");
+        if (o.genomes[0].second != 0) refuse("--genome: the first --sim stands before the first --genome (every --sim belongs to the --genome before it)");
+        for (size_t g = 0; g < o.genomes.size(); ++g)
+            if ((g + 1 < o.genomes.size() ? o.genomes[g + 1].second : o.sim.size()) == o.genomes[g].second) refuse("--genome " + o.genomes[g].first + " has no --sim");
+    }
     if (profile) {
-        if (o.simmode != 1 && o.simmode != 2) refuse("--bait-profile needs -s 1 or -s 2: the titles of simulated reads carry the source locus that tells true from false positives");
-        if (cohort) refuse("--bait-profile cannot be combined with --cohort");
-        if (o.extractFastX) refuse("--bait-profile cannot be combined with -e");
-        if (o.threading) refuse("--bait-profile cannot be combined with -g/-gc/-gcc (no pair is assigned behind the threading gate)");
-        if (o.ngpus > 1) refuse("--bait-profile runs on one GPU: --gpus > 1 is not supported with it (the tables of several contexts are not merged)");
-        if (o.ingestShards > 0) refuse("--bait-profile cannot be combined with --ingest-shards");
-        if (o.parseOnly) refuse("--bait-profile cannot be combined with --parse-only");
+        const std::string pf = profileFiles ? "--bait-profile" : "--bait-fps";
+        if (o.simmode != 1 && o.simmode != 2) refuse(pf + " needs -s 1 or -s 2" + (baitFps ? " (with -fa/-fq) or --sim" : "") + ": the titles of simulated reads carry the source locus that tells true from false positives");
+        if (cohort) refuse(pf + " cannot be combined with --cohort");
+        if (o.extractFastX) refuse(pf + " cannot be combined with -e");
+        if (o.threading) refuse(pf + " cannot be combined with -g/-gc/-gcc (no pair is assigned behind the threading gate)");
+        if (o.ngpus > 1) refuse(pf + " runs on one GPU: --gpus > 1 is not supported with it (the tables of several contexts are not merged)");
+        if (o.ingestShards > 0) refuse(pf + " cannot be combined with --ingest-shards");
+        if (o.parseOnly) refuse(pf + " cannot be combined with --parse-only");
     }
     if (o.buTable && (o.extractFastX || o.threading)) refuse("--bu-table: with -e or -g/-gc/-gcc -bu does nothing (novel edges are counted on the assignment path only)");
     // (cohort mode has no place for the event log's host replay after every batch: -bu there is the table's, and is asked for as such)
@@ -827,6 +849,25 @@ int main(int argc, char* argv[]) {
     struct { std::vector<uint8_t> seq; std::vector<uint64_t> off; std::vector<uint32_t> src, dst; } kb;
     kb.off.assign(1, 0);
     double kcp_host_s = 0;
+    // --bait-fps: the candidates (the FP class of the table when the run, or its first genome, is counted) and the TP filter of the
+    // table as it stands.  One table: after a genome it is emptied and counts true positives only (dbtk_kcp_set_tp_only).
+    dbtk_kcp_fps_t* fps = nullptr;
+    double fps_s = 0;
+    auto fps_step = [&] {
+        const double t0 = wall();
+        if (!fps && dbtk_kcp_fps_begin(kcp, &fps)) die_assert(std::string("--bait-fps: ") + dbtk_last_error());
+        if (dbtk_kcp_fps_apply(fps, kcp)) die_assert(std::string("--bait-fps: ") + dbtk_last_error());
+        fps_s += wall() - t0;
+    };
+    auto genome_done = [&](size_t g) {
+        fps_step();
+        const double t0 = wall();
+        if (dbtk_kcp_reset(kcp) || dbtk_kcp_set_tp_only(kcp, 1)) die_assert(std::string("--bait-fps: ") + dbtk_last_error());
+        fps_s += wall() - t0;
+        uint64_t ncand = 0, nalive = 0;
+        if (dbtk_kcp_fps_count(fps, &ncand, &nalive)) die_assert(dbtk_last_error());
+        fprintf(stderr, "# genome %zu %s: %llu candidates, %llu alive\n", g, o.genomes[g].first.c_str(), (unsigned long long)ncand, (unsigned long long)nalive);
+    };
     bool fq = o.isFastq;  // (cohort mode: per sample)
     time1 = time(nullptr);
     fprintf(stderr, "threads created\n");
@@ -1903,7 +1944,9 @@ int main(int argc, char* argv[]) {
             }
         };
         std::string r1, r2, title;
-        for (dbtk_sim_t* S : sims) {
+        size_t genome = 0;  // --genome: the genome the assembly belongs to; its table is filtered and emptied after its last assembly
+        for (size_t si = 0; si < sims.size(); ++si) {
+            dbtk_sim_t* S = sims[si];
             if (dbtk_sim_attach(S, dev_of(0))) die_assert(std::string("--sim: ") + dbtk_last_error());
             dbtk_sim_facts_t sf;
             if (dbtk_sim_info(S, &sf)) die_assert(dbtk_last_error());
@@ -1976,6 +2019,7 @@ int main(int argc, char* argv[]) {
             if (dbtk_sim_times(S, &ms, &wb, &ub)) die_assert(std::string("--sim: ") + dbtk_last_error());
             tile_ms += ms; tile_bytes += wb; up_bytes += ub;
             dbtk_sim_free(S);  // (its arena and batch buffers: the next assembly takes their place)
+            if (!o.genomes.empty() && si + 1 == (genome + 1 < o.genomes.size() ? o.genomes[genome + 1].second : sims.size())) genome_done(genome++);
         }
         sims.clear();
         fprintf(stderr, "--sim: k_sim_tile wrote %llu bytes of reads in %.3f ms (%.1f GB/s); %llu bytes of assembly uploaded; profile feed %.3f s, titles and kam text %.3f s\n",
@@ -2223,7 +2267,20 @@ int main(int argc, char* argv[]) {
                 fwrite(&zero, 8, 1, f); fwrite(&szv, 8, 1, f);
                 fclose(f);
             }
-            if (kcp) {
+            if (baitFps) {
+                fprintf(stderr, "writing FP-specific bait k-mers...\n");
+                if (o.genomes.empty()) fps_step();  // (with --genome every table was applied when its genome ended)
+                const double tw0 = wall();
+                if (dbtk_kcp_fps_write(fps, o.baitFps.c_str())) die_assert(std::string("--bait-fps: ") + dbtk_last_error());
+                if (getenv("DBTK_VERBOSE")) {  // (tools/fps_bench.py)
+                    uint64_t ncand = 0, nalive = 0, looked = 0;
+                    double ms = 0;
+                    if (dbtk_kcp_fps_count(fps, &ncand, &nalive) || dbtk_kcp_fps_times(fps, &ms, &looked)) die_assert(dbtk_last_error());
+                    fprintf(stderr, "bait fps: %llu candidates, %llu alive; %llu look-ups in %.3f ms of the apply kernel; begin, apply and reset %.3f s, written in %.3f s\n",
+                            (unsigned long long)ncand, (unsigned long long)nalive, (unsigned long long)looked, ms, fps_s, wall() - tw0);
+                }
+            }
+            if (kcp && profileFiles) {
                 fprintf(stderr, "writing k-mer count profiles...\n");
                 const double tw0 = wall();
                 if (dbtk_kcp_write(kcp, o.baitProfile.c_str())) die_assert(std::string("--bait-profile: ") + dbtk_last_error());
@@ -2274,6 +2331,7 @@ int main(int argc, char* argv[]) {
         if (pred) dbtk_pred_free(pred);
         dbtk_dosage_free(dosage);
         dbtk_dosage_free(kms);
+        dbtk_kcp_fps_free(fps);
         dbtk_kcp_free(kcp);
         for (auto c : ctx) dbtk_ctx_free(c);
         dbtk_rpgg_free(rpgg);

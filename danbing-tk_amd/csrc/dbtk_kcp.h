@@ -117,5 +117,88 @@ inline double kcp_sd(const KcpSlot& s) {
     return sqrt((double)num / ((double)s.n * (double)s.n));
 }
 
+// ---- The statistics as `ktools fps` / baitBuilder v2 (bait.cpp:177-220) see them: not the moments but the floats strtof makes of the
+// "%.4f" text of MEAN and SD.  From a slot's integers, without text, bit for bit; for the host and for the device (no 128-bit division
+// or conversion: the device has no runtime support for either).
+
+// The integer whose digits snprintf("%.4f", v) prints, 0 <= v < 2^32 / 10^4: v * 10^4 rounded to nearest on the exact binary value of
+// v, ties to even (1/32 prints 0.0312, 3/32 prints 0.0938).  t + r is the product exactly (r: the rounding error of t, from one fma).
+// t, floor(t) and 0.5 are multiples of ulp(t), so t - floor(t) - 0.5 is zero or at least ulp(t) away from it — more than
+// |r| <= ulp(t) / 2 — and its sign (which the subtractions keep) decides alone; where it is zero the sign of r decides, and r == 0 is
+// the tie.
+DBTK_HD uint32_t kcp_dec4(double v) {
+    const double t = v * 1e4, r = fma(v, 1e4, -t);
+    const double f = floor(t), d = t - f - 0.5;
+    const uint32_t D = (uint32_t)f;
+    if (d != 0.0) return d > 0.0 ? D + 1u : D;
+    if (r != 0.0) return r > 0.0 ? D + 1u : D;
+    return D + (D & 1u);
+}
+// strtof of those digits with the point four places in: D < 2^24 is a float, 10^4 is one, and IEEE division rounds the exact quotient
+// once, which is what strtof does to the decimal number.
+DBTK_HD float kcp_text_float(uint32_t D) { return (float)D / 10000.0f; }
+
+DBTK_HD void kcp_mul64(uint64_t a, uint64_t b, uint64_t* hi, uint64_t* lo) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    *hi = __umul64hi(a, b);
+    *lo = a * b;
+#else
+    const unsigned __int128 p = (unsigned __int128)a * b;
+    *hi = (uint64_t)(p >> 64);
+    *lo = (uint64_t)p;
+#endif
+}
+// (double)(hi * 2^64 + lo), rounded once: the 64 leading bits, whatever lies below them ORed into bit 0 (eleven places under the bit
+// that rounds), converted and scaled.
+DBTK_HD double kcp_u128_to_double(uint64_t hi, uint64_t lo) {
+    if (!hi) return (double)lo;
+    const int sh = __builtin_clzll(hi);
+    uint64_t m = hi, lost = 0;
+    if (sh) { m = (hi << sh) | (lo >> (64 - sh)); lost = lo << sh; } else lost = lo;
+    if (lost) m |= 1ull;
+    return ldexp((double)m, 64 - sh);
+}
+
+DBTK_HD float kcp_mean_text(const KcpSlot& s) { return kcp_text_float(kcp_dec4((double)s.sum / (double)s.n)); }
+// kcp_sd's value: the numerator n * sumsq - sum^2 exact in two words (it can pass 2^64), rounded to double once
+DBTK_HD float kcp_sd_text(const KcpSlot& s) {
+    uint64_t ahi, alo, bhi, blo;
+    kcp_mul64((uint64_t)s.n, s.sumsq, &ahi, &alo);
+    kcp_mul64(s.sum, s.sum, &bhi, &blo);
+    const uint64_t lo = alo - blo, hi = ahi - bhi - (uint64_t)(alo < blo);
+    return kcp_text_float(kcp_dec4(sqrt(kcp_u128_to_double(hi, lo) / ((double)s.n * (double)s.n))));
+}
+// testAndFilter's test (bait.cpp:196-203), in float as the reference evaluates it: the FP mean inside the TP profile's mean +- 2 sd
+DBTK_HD bool kcp_fps_inside(float fp_mean, float tp_mean, float tp_sd) {
+    const float w = 2.0f * tp_sd;
+    return tp_mean - w <= fp_mean && fp_mean <= tp_mean + w;
+}
+
+// A candidate of the FP-specific filter (dbtk_kcp_fps_*): what stays of an FP entry, and beside it its one mutable word.
+struct KcpCand { uint64_t kmer; uint32_t locus; float mean; };
+static_assert(sizeof(KcpCand) == 16, "a candidate is one 16-byte load");
+constexpr uint32_t KCP_CAND_ALIVE = 1u << 16;  // state = mi | ma << 8 | alive << 16; fresh: 255 | 0 << 8 | alive
+DBTK_HD uint32_t kcp_cand_fresh() { return 255u | KCP_CAND_ALIVE; }
+
+// One candidate against one quiescent TP table: the walk from hash_cls ends at an empty k-mer word (absent: state unchanged) or at
+// the entry (k-mer, locus, class 0).  Inside mean +- 2 sd: dead for good (0).  Outside: (mi, ma) becomes the entry's (min, max) where
+// mi is still 255, else widens by it.  The table is only read.
+DBTK_HD uint32_t kcp_fps_step(const KcpSlot* tab, uint64_t mask, uint32_t shift, const KcpCand& c, uint32_t state) {
+    const uint32_t lc1 = kcp_lc1(c.locus, 0u);
+    uint64_t i = hash_cls(c.kmer, lc1, shift);
+    for (uint64_t p = 0; p <= mask; ++p, i = (i + 1) & mask) {
+        const KcpSlot s = tab[i];
+        if (s.kmer == NAN64) return state;
+        if (s.kmer != c.kmer || s.lc1 != lc1 || s.n == 0) continue;
+        if (kcp_fps_inside(c.mean, kcp_mean_text(s), kcp_sd_text(s))) return 0u;
+        uint32_t mi = state & 255u, ma = (state >> 8) & 255u;
+        const uint32_t tmi = s.mn & 255u, tma = s.mx & 255u;  // (uint8_t in the reference; a count per read is at most 236)
+        if (mi == 255u) { mi = tmi; ma = tma; }
+        else { mi = tmi < mi ? tmi : mi; ma = tma > ma ? tma : ma; }
+        return mi | (ma << 8) | KCP_CAND_ALIVE;
+    }
+    return state;
+}
+
 }  // namespace dbtk
 #endif

@@ -113,6 +113,42 @@ __global__ void __launch_bounds__(256) k_kcp_compact(const KcpSlot* t, uint64_t 
     }
 }
 
+// ---- the FP-specific filter (dbtk_kcp_fps_*): csrc/dbtk_kcp.h has the candidate, its state word and the step
+
+// the compacted FP entries into candidates: k-mer, locus, the FP mean as `ktools fps` would parse it; (255, 0), alive
+__global__ void __launch_bounds__(256) k_kcp_fps_begin(const KcpSlot* ent, uint64_t n, KcpCand* cand, uint32_t* state) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const KcpSlot s = ent[i];
+        cand[i] = KcpCand{s.kmer, (s.lc1 & 0x7FFFFFFFu) - 1u, kcp_mean_text(s)};
+        state[i] = kcp_cand_fresh();
+    }
+}
+
+// One lane per candidate; a dead one costs its 4-byte state word.  Every candidate has one owner and the table is only read: plain
+// loads and stores, no atomics but the two tallies at the end (words[0] += living candidates looked up, words[1] += those that died).
+__global__ void __launch_bounds__(256) k_kcp_fps_apply(const KcpCand* cand, uint32_t* state, uint64_t n, const KcpSlot* tab, uint64_t mask, uint32_t shift,
+                                                       unsigned long long* words) {
+    uint32_t looked = 0, died = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t st = state[i];
+        if (!(st & KCP_CAND_ALIVE)) continue;
+        ++looked;
+        const uint32_t nst = kcp_fps_step(tab, mask, shift, cand[i], st);
+        if (nst != st) state[i] = nst;
+        died += nst == 0u;
+    }
+    if (looked) atomicAdd(words, (unsigned long long)looked);
+    if (died) atomicAdd(words + 1, (unsigned long long)died);
+}
+
+__global__ void __launch_bounds__(256) k_kcp_text_stats(const uint32_t* n, const uint64_t* sum, const uint64_t* sumsq, uint64_t count, float* mean, float* sd) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (uint64_t)gridDim.x * blockDim.x) {
+        const KcpSlot s{0, 1u, n[i], sum[i], sumsq[i], 0u, 0u};
+        mean[i] = kcp_mean_text(s);
+        sd[i] = kcp_sd_text(s);
+    }
+}
+
 constexpr uint64_t KCP_SLOTS_DEFAULT = 1ull << 22;  // 168 MB (DBTK_KCP_SLOTS); grows by doubling
 constexpr uint64_t KCP_PIECE_MIN = 1ull << 20;      // k-mer positions of a batch's piece, where a quarter of the table is less
 
@@ -137,9 +173,24 @@ struct dbtk_kcp {
     double add_ms = 0;
 };
 
+// The candidates of the FP-specific filter: a list of its own in HBM (the handle it was begun from may be reset or freed).
+struct dbtk_kcp_fps {
+    int device = 0, num_cu = 1;
+    uint32_t k = 0;
+    uint64_t nloci = 0;
+    hipStream_t stream = nullptr;
+    KcpCand* d_cand = nullptr;
+    uint32_t* d_state = nullptr;
+    unsigned long long* d_words = nullptr;  // living candidates looked up | candidates that died, over all applies
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    uint64_t n = 0, alive = 0, lookups = 0;
+    double apply_ms = 0;
+};
+
 namespace {
 
-uint32_t grid_for(const dbtk_kcp* c, uint64_t n, uint32_t per_block) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1) / per_block, (uint64_t)c->num_cu * 8)); }
+uint32_t grid_cu(int num_cu, uint64_t n, uint32_t per_block) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1) / per_block, (uint64_t)num_cu * 8)); }
+uint32_t grid_for(const dbtk_kcp* c, uint64_t n, uint32_t per_block) { return grid_cu(c->num_cu, n, per_block); }
 
 dbtk_status_t kcp_new_table(dbtk_kcp* c, uint64_t slots, KcpSlot** out) {
     *out = nullptr;
@@ -365,34 +416,45 @@ dbtk_status_t kcp_add_impl(dbtk_kcp_t* c, const uint8_t* seq, const uint64_t* of
     return DBTK_OK;
 }
 
-// the entries of class cls, sorted by (locus, k-mer)
-dbtk_status_t kcp_entries(dbtk_kcp_t* c, uint32_t cls, std::vector<KcpSlot>* out, uint64_t* count) {
+// the entries of class cls compacted into a device array that the caller frees (want_out false: counted only, *d_out stays null)
+dbtk_status_t kcp_compact(dbtk_kcp_t* c, uint32_t cls, bool want_out, KcpSlot** d_out, uint64_t* count) {
+    *d_out = nullptr;
     if (!c || cls > 1) { set_error("bait profile: null handle or a class other than 0 (TP) and 1 (FP)"); return DBTK_ERR_ARG; }
     KCHK(hipSetDevice(c->device));
     unsigned long long w[KCP_WORDS];
     dbtk_status_t st = kcp_words(c, w);
     if (st) return st;
-    const uint64_t cap = out ? w[KCP_W_OCC] : 0;  // (no class has more entries than the table has slots taken)
+    const uint64_t cap = want_out ? w[KCP_W_OCC] : 0;  // (no class has more entries than the table has slots taken)
     unsigned long long* d_n = nullptr;
-    KcpSlot* d_out = nullptr;
     KCHK(hipMalloc((void**)&d_n, sizeof(unsigned long long)));
     unsigned long long n = 0;
     st = [&]() -> dbtk_status_t {
         KCHK(hipMemsetAsync(d_n, 0, sizeof(unsigned long long), c->stream));
-        if (cap) KCHK(hipMalloc((void**)&d_out, cap * sizeof(KcpSlot)));
-        hipLaunchKernelGGL(k_kcp_compact, dim3(grid_for(c, c->slots, 256)), dim3(256), 0, c->stream, (const KcpSlot*)c->d_tab, c->slots, cls, d_out, cap, d_n);
+        if (cap) KCHK(hipMalloc((void**)d_out, cap * sizeof(KcpSlot)));
+        hipLaunchKernelGGL(k_kcp_compact, dim3(grid_for(c, c->slots, 256)), dim3(256), 0, c->stream, (const KcpSlot*)c->d_tab, c->slots, cls, *d_out, cap, d_n);
         KCHK(hipGetLastError());
         KCHK(hipMemcpyAsync(&n, d_n, sizeof n, hipMemcpyDeviceToHost, c->stream));
         KCHK(hipStreamSynchronize(c->stream));
-        if (out) {
-            if (n > cap) { set_error("bait profile: the table holds more entries than slots taken"); return DBTK_ERR_HIP; }
-            out->resize(n);
-            if (n) KCHK(hipMemcpy(out->data(), d_out, n * sizeof(KcpSlot), hipMemcpyDeviceToHost));
-        }
+        if (want_out && n > cap) { set_error("bait profile: the table holds more entries than slots taken"); return DBTK_ERR_HIP; }
         return DBTK_OK;
     }();
-    if (d_out) (void)hipFree(d_out);
     (void)hipFree(d_n);
+    if (st && *d_out) { (void)hipFree(*d_out); *d_out = nullptr; }
+    if (!st) *count = n;
+    return st;
+}
+
+// the entries of class cls, sorted by (locus, k-mer)
+dbtk_status_t kcp_entries(dbtk_kcp_t* c, uint32_t cls, std::vector<KcpSlot>* out, uint64_t* count) {
+    KcpSlot* d_out = nullptr;
+    uint64_t n = 0;
+    dbtk_status_t st = kcp_compact(c, cls, out != nullptr, &d_out, &n);
+    if (st) return st;
+    if (out) {
+        out->resize(n);
+        if (n && hipMemcpy(out->data(), d_out, n * sizeof(KcpSlot), hipMemcpyDeviceToHost) != hipSuccess) { set_error("bait profile: copying the entries to the host failed"); st = DBTK_ERR_HIP; }
+    }
+    if (d_out) (void)hipFree(d_out);
     if (st) return st;
     if (count) *count = n;
     if (out) kcp_sort(*out, c->nloci);
@@ -432,11 +494,216 @@ dbtk_status_t kcp_write_class(dbtk_kcp_t* c, uint32_t cls, const std::string& fn
     return DBTK_OK;
 }
 
+void kcp_fps_free_impl(dbtk_kcp_fps* f) {
+    if (!f) return;
+    (void)hipSetDevice(f->device);
+    if (f->stream) (void)hipStreamSynchronize(f->stream);
+    if (f->ev0) (void)hipEventDestroy(f->ev0);
+    if (f->ev1) (void)hipEventDestroy(f->ev1);
+    if (f->d_cand) (void)hipFree(f->d_cand);
+    if (f->d_state) (void)hipFree(f->d_state);
+    if (f->d_words) (void)hipFree(f->d_words);
+    if (f->stream) (void)hipStreamDestroy(f->stream);
+    delete f;
+}
+
+dbtk_status_t kcp_fps_begin_impl(dbtk_kcp_t* c, dbtk_kcp_fps_t** out) {
+    if (!c || !out) { set_error("dbtk_kcp_fps_begin: null argument"); return DBTK_ERR_ARG; }
+    *out = nullptr;
+    if (c->flags & DBTK_KCP_TP_ONLY) { set_error("dbtk_kcp_fps_begin: the handle counts true positives only (DBTK_KCP_TP_ONLY): it has no FP class to take candidates from"); return DBTK_ERR_ARG; }
+    KcpSlot* d_ent = nullptr;
+    uint64_t n = 0;
+    dbtk_status_t st = kcp_compact(c, 1, true, &d_ent, &n);
+    if (st) return st;
+    dbtk_kcp_fps* f = new dbtk_kcp_fps;
+    f->device = c->device; f->num_cu = c->num_cu; f->k = c->k; f->nloci = c->nloci; f->n = f->alive = n;
+    st = [&]() -> dbtk_status_t {
+        KCHK(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+        KCHK(hipEventCreate(&f->ev0));
+        KCHK(hipEventCreate(&f->ev1));
+        KCHK(hipMalloc((void**)&f->d_words, 2 * sizeof(unsigned long long)));
+        KCHK(hipMemsetAsync(f->d_words, 0, 2 * sizeof(unsigned long long), f->stream));
+        if (n) {
+            if (hipMalloc((void**)&f->d_cand, n * sizeof(KcpCand)) != hipSuccess || hipMalloc((void**)&f->d_state, n * sizeof(uint32_t)) != hipSuccess) {
+                (void)hipGetLastError();
+                set_error("bait fps: no device memory for " + std::to_string(n) + " candidates (" + std::to_string(n * (sizeof(KcpCand) + sizeof(uint32_t))) + " bytes)");
+                return DBTK_ERR_NOMEM;
+            }
+            // (d_ent is complete: kcp_compact waited for the handle's stream)
+            hipLaunchKernelGGL(k_kcp_fps_begin, dim3(grid_cu(f->num_cu, n, 256)), dim3(256), 0, f->stream, (const KcpSlot*)d_ent, n, f->d_cand, f->d_state);
+            KCHK(hipGetLastError());
+        }
+        KCHK(hipStreamSynchronize(f->stream));
+        return DBTK_OK;
+    }();
+    if (d_ent) (void)hipFree(d_ent);
+    if (st) { kcp_fps_free_impl(f); return st; }
+    *out = f;
+    return DBTK_OK;
+}
+
+dbtk_status_t kcp_fps_apply_impl(dbtk_kcp_fps_t* f, dbtk_kcp_t* c) {
+    if (!f || !c) { set_error("dbtk_kcp_fps_apply: null argument"); return DBTK_ERR_ARG; }
+    if (c->device != f->device || c->k != f->k || c->nloci != f->nloci) {
+        set_error("dbtk_kcp_fps_apply: the table (device " + std::to_string(c->device) + ", k " + std::to_string(c->k) + ", " + std::to_string(c->nloci) + " loci) does not match the candidates' (device " +
+                  std::to_string(f->device) + ", k " + std::to_string(f->k) + ", " + std::to_string(f->nloci) + " loci)");
+        return DBTK_ERR_ARG;
+    }
+    KCHK(hipSetDevice(f->device));
+    unsigned long long w[KCP_WORDS];
+    const dbtk_status_t st = kcp_words(c, w);  // the table is quiescent from here on (and whole: no insert failed)
+    if (st) return st;
+    if (!f->n) return DBTK_OK;
+    KCHK(hipEventRecord(f->ev0, f->stream));
+    hipLaunchKernelGGL(k_kcp_fps_apply, dim3(grid_cu(f->num_cu, f->n, 256)), dim3(256), 0, f->stream, (const KcpCand*)f->d_cand, f->d_state, f->n, (const KcpSlot*)c->d_tab,
+                       c->slots - 1, 64 - log2u64(c->slots), f->d_words);
+    KCHK(hipGetLastError());
+    KCHK(hipEventRecord(f->ev1, f->stream));
+    unsigned long long fw[2];
+    KCHK(hipMemcpyAsync(fw, f->d_words, sizeof fw, hipMemcpyDeviceToHost, f->stream));
+    KCHK(hipStreamSynchronize(f->stream));
+    float ms = 0;
+    KCHK(hipEventElapsedTime(&ms, f->ev0, f->ev1));
+    f->apply_ms += ms;
+    f->lookups = fw[0];
+    f->alive = f->n - fw[1];
+    return DBTK_OK;
+}
+
+struct FpsLine { uint32_t locus; uint64_t kmer; uint8_t mi, ma; };
+
+// the living candidates sorted by (locus, k-mer); `seen` (where not null): the loci that had a candidate, ascending
+dbtk_status_t kcp_fps_lines(dbtk_kcp_fps_t* f, std::vector<FpsLine>* lines, std::vector<uint32_t>* seen) {
+    if (!f) { set_error("bait fps: null handle"); return DBTK_ERR_ARG; }
+    KCHK(hipSetDevice(f->device));
+    std::vector<KcpCand> cand(f->n);
+    std::vector<uint32_t> state(f->n);
+    if (f->n) {
+        KCHK(hipMemcpy(cand.data(), f->d_cand, f->n * sizeof(KcpCand), hipMemcpyDeviceToHost));
+        KCHK(hipMemcpy(state.data(), f->d_state, f->n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    lines->clear();
+    for (uint64_t i = 0; i < f->n; ++i) {
+        if (seen) seen->push_back(cand[i].locus);
+        if (state[i] & KCP_CAND_ALIVE) lines->push_back(FpsLine{cand[i].locus, cand[i].kmer, (uint8_t)(state[i] & 255u), (uint8_t)((state[i] >> 8) & 255u)});
+    }
+    std::sort(lines->begin(), lines->end(), [](const FpsLine& a, const FpsLine& b) { return a.locus != b.locus ? a.locus < b.locus : a.kmer < b.kmer; });
+    if (seen) {
+        std::sort(seen->begin(), seen->end());
+        seen->erase(std::unique(seen->begin(), seen->end()), seen->end());
+    }
+    if (lines->size() != f->alive) { set_error("bait fps: the candidate list and its tally of the living disagree"); return DBTK_ERR_HIP; }
+    return DBTK_OK;
+}
+
+dbtk_status_t kcp_text_stats_impl(int device_id, const uint32_t* n, const uint64_t* sum, const uint64_t* sumsq, uint64_t count, float* mean_out, float* sd_out) {
+    if (count && (!n || !sum || !sumsq || !mean_out || !sd_out)) { set_error("dbtk_kcp_text_stats: null argument"); return DBTK_ERR_ARG; }
+    for (uint64_t i = 0; i < count; ++i)
+        if (!n[i] || (unsigned __int128)n[i] * sumsq[i] < (unsigned __int128)sum[i] * sum[i]) {
+            set_error("dbtk_kcp_text_stats: entry " + std::to_string(i) + " is not the moments of any counts (n >= 1 and n * sumsq >= sum^2)");
+            return DBTK_ERR_ARG;
+        }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); set_error("no HIP device (the library has no CPU path)"); return DBTK_ERR_NO_DEVICE; }
+    if (device_id < 0 || device_id >= ndev) { set_error("dbtk_kcp_text_stats: device " + std::to_string(device_id) + " of " + std::to_string(ndev)); return DBTK_ERR_ARG; }
+    if (!count) return DBTK_OK;
+    KCHK(hipSetDevice(device_id));
+    hipDeviceProp_t prop;
+    KCHK(hipGetDeviceProperties(&prop, device_id));
+    // one allocation: sum | sumsq | n | mean | sd
+    uint8_t* d = nullptr;
+    KCHK(hipMalloc((void**)&d, count * 28));
+    uint64_t *d_sum = (uint64_t*)d, *d_sq = d_sum + count;
+    uint32_t* d_n = (uint32_t*)(d_sq + count);
+    float *d_mean = (float*)(d_n + count), *d_sd = d_mean + count;
+    const dbtk_status_t st = [&]() -> dbtk_status_t {
+        KCHK(hipMemcpy(d_sum, sum, count * 8, hipMemcpyHostToDevice));
+        KCHK(hipMemcpy(d_sq, sumsq, count * 8, hipMemcpyHostToDevice));
+        KCHK(hipMemcpy(d_n, n, count * 4, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_kcp_text_stats, dim3(grid_cu(std::max(1, prop.multiProcessorCount), count, 256)), dim3(256), 0, nullptr, (const uint32_t*)d_n, (const uint64_t*)d_sum,
+                           (const uint64_t*)d_sq, count, d_mean, d_sd);
+        KCHK(hipGetLastError());
+        KCHK(hipDeviceSynchronize());
+        KCHK(hipMemcpy(mean_out, d_mean, count * 4, hipMemcpyDeviceToHost));
+        KCHK(hipMemcpy(sd_out, d_sd, count * 4, hipMemcpyDeviceToHost));
+        return DBTK_OK;
+    }();
+    (void)hipFree(d);
+    return st;
+}
+
 }  // namespace
 
 extern "C" {
 
 uint32_t dbtk_kcp_api_version(void) { return DBTK_KCP_API_VERSION; }
+
+dbtk_status_t dbtk_kcp_set_tp_only(dbtk_kcp_t* c, int on) {
+    if (!c) { set_error("dbtk_kcp_set_tp_only: null argument"); return DBTK_ERR_ARG; }
+    c->flags = on ? (c->flags | DBTK_KCP_TP_ONLY) : (c->flags & ~DBTK_KCP_TP_ONLY);
+    return DBTK_OK;
+}
+
+dbtk_status_t dbtk_kcp_fps_begin(dbtk_kcp_t* c, dbtk_kcp_fps_t** out) { return guarded([&] { return kcp_fps_begin_impl(c, out); }); }
+dbtk_status_t dbtk_kcp_fps_apply(dbtk_kcp_fps_t* f, dbtk_kcp_t* c) { return guarded([&] { return kcp_fps_apply_impl(f, c); }); }
+void dbtk_kcp_fps_free(dbtk_kcp_fps_t* f) { kcp_fps_free_impl(f); }
+
+dbtk_status_t dbtk_kcp_fps_count(dbtk_kcp_fps_t* f, uint64_t* candidates, uint64_t* alive) {
+    if (!f) { set_error("dbtk_kcp_fps_count: null argument"); return DBTK_ERR_ARG; }
+    if (candidates) *candidates = f->n;
+    if (alive) *alive = f->alive;
+    return DBTK_OK;
+}
+
+dbtk_status_t dbtk_kcp_fps_read(dbtk_kcp_fps_t* f, uint32_t* loci, uint64_t* kmers, uint8_t* mi, uint8_t* ma, uint64_t cap) {
+    return guarded([&]() -> dbtk_status_t {
+        std::vector<FpsLine> v;
+        const dbtk_status_t st = kcp_fps_lines(f, &v, nullptr);
+        if (st) return st;
+        if (v.size() > cap) { set_error("dbtk_kcp_fps_read: " + std::to_string(v.size()) + " living candidates, room for " + std::to_string(cap)); return DBTK_ERR_OVERFLOW; }
+        for (size_t i = 0; i < v.size(); ++i) {
+            if (loci) loci[i] = v[i].locus;
+            if (kmers) kmers[i] = v[i].kmer;
+            if (mi) mi[i] = v[i].mi;
+            if (ma) ma[i] = v[i].ma;
+        }
+        return DBTK_OK;
+    });
+}
+
+dbtk_status_t dbtk_kcp_fps_write(dbtk_kcp_fps_t* f, const char* path) {
+    if (!f || !path) { set_error("dbtk_kcp_fps_write: null argument"); return DBTK_ERR_ARG; }
+    return guarded([&]() -> dbtk_status_t {
+        std::vector<FpsLine> v;
+        std::vector<uint32_t> seen;
+        const dbtk_status_t st = kcp_fps_lines(f, &v, &seen);
+        if (st) return st;
+        std::string text;
+        size_t i = 0;
+        for (uint32_t l : seen) {  // (a header also for a locus all of whose candidates died, as the reference writes it)
+            text += '>'; text += std::to_string(l); text += '\n';
+            for (; i < v.size() && v[i].locus == l; ++i) {
+                text += std::to_string(v[i].kmer); text += '\t'; text += std::to_string((int)v[i].mi); text += '\t'; text += std::to_string((int)v[i].ma); text += '\n';
+            }
+        }
+        FILE* out = fopen(path, "wb");
+        if (!out) { set_error(std::string("cannot create ") + path); return DBTK_ERR_IO; }
+        const bool ok = fwrite(text.data(), 1, text.size(), out) == text.size();
+        if (fclose(out) || !ok) { set_error(std::string("write error on ") + path); return DBTK_ERR_IO; }
+        return DBTK_OK;
+    });
+}
+
+dbtk_status_t dbtk_kcp_fps_times(dbtk_kcp_fps_t* f, double* apply_ms, uint64_t* lookups) {
+    if (!f) { set_error("dbtk_kcp_fps_times: null argument"); return DBTK_ERR_ARG; }
+    if (apply_ms) *apply_ms = f->apply_ms;
+    if (lookups) *lookups = f->lookups;
+    return DBTK_OK;
+}
+
+dbtk_status_t dbtk_kcp_text_stats(int device_id, const uint32_t* n, const uint64_t* sum, const uint64_t* sumsq, uint64_t count, float* mean_out, float* sd_out) {
+    return guarded([&] { return kcp_text_stats_impl(device_id, n, sum, sumsq, count, mean_out, sd_out); });
+}
 
 dbtk_status_t dbtk_kcp_create(uint32_t ksize, uint64_t nloci, int device_id, uint32_t flags, dbtk_kcp_t** out) {
     return guarded([&] { return kcp_create_impl(ksize, nloci, device_id, flags, out); });

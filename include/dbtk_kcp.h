@@ -78,6 +78,47 @@ dbtk_status_t dbtk_kcp_stats(dbtk_kcp_t* kcp, uint64_t* table_bytes, uint64_t* s
 /* Of all dbtk_kcp_add calls since creation or reset: milliseconds in the add kernel (HIP events) and first occurrences inserted. */
 dbtk_status_t dbtk_kcp_times(dbtk_kcp_t* kcp, double* add_ms, uint64_t* inserts);
 
+/* Switches the handle's class filter between batches: on != 0 as if created with DBTK_KCP_TP_ONLY (later dbtk_kcp_add calls drop
+ * the pairs with src != dst, dbtk_kcp_write writes no FP file), 0 counts both classes again.  What the table holds stays.  One
+ * handle whose filter moves, rather than a second TP-only handle beside the first: a second handle is a second table in HBM, and
+ * a run that counts genome after genome (`--bait-fps --genome`) needs one table at a time. */
+dbtk_status_t dbtk_kcp_set_tp_only(dbtk_kcp_t* kcp, int on);
+
+/* ---- The FP-specific bait k-mers (`danbing-tk --bait-fps`), filtered on the device.
+ * Replaces, in the reference:  src/bait.cpp:177-241, 254-305 (`baitBuilder v2`, here also `ktools fps`), which parse one FP profile
+ * and one TP profile per genome from text.  Here the FP entries of a table become a list of candidates in HBM, and every TP table
+ * is looked up where it lies: no profile text is written or parsed.  The comparison is the reference's, on the floats that strtof
+ * makes of the "%.4f" text of MEAN and SD; the device computes those floats from an entry's five integers, bit for bit
+ * (csrc/dbtk_kcp.h: kcp_mean_text, kcp_sd_text).
+ *
+ * A candidate: k-mer, locus, the FP mean as float, (mi, ma) = (255, 0), alive.  dbtk_kcp_fps_apply looks every living candidate up
+ * as (k-mer, locus, class 0) in one table: absent — nothing; present and tp_mean - 2 sd <= fp_mean <= tp_mean + 2 sd — the
+ * candidate dies for good; present and outside — (mi, ma) becomes the entry's (min, max) where mi is still 255, else widens by it.
+ * The result of several applies does not depend on their order. */
+typedef struct dbtk_kcp_fps dbtk_kcp_fps_t;
+
+/* The FP class of kcp's table becomes the candidate list (DBTK_ERR_ARG for a handle that is DBTK_KCP_TP_ONLY).  The list lives on its
+ * own: kcp may be reset or freed afterwards. */
+dbtk_status_t dbtk_kcp_fps_begin(dbtk_kcp_t* kcp, dbtk_kcp_fps_t** out);
+/* kcp_tp: the handle the list was begun from or any other on the same device with the same ksize and nloci (else DBTK_ERR_ARG).
+ * Its table is only read.  Returns when the kernel is done. */
+dbtk_status_t dbtk_kcp_fps_apply(dbtk_kcp_fps_t* fps, dbtk_kcp_t* kcp_tp);
+dbtk_status_t dbtk_kcp_fps_count(dbtk_kcp_fps_t* fps, uint64_t* candidates, uint64_t* alive);
+/* The living candidates sorted by (locus, k-mer) into the arrays (each may be null).  DBTK_ERR_OVERFLOW when cap is too small. */
+dbtk_status_t dbtk_kcp_fps_read(dbtk_kcp_fps_t* fps, uint32_t* loci, uint64_t* kmers, uint8_t* mi, uint8_t* ma, uint64_t cap);
+/* The file `ktools fps` writes, byte for byte: `>LOCUS` for every locus that had a candidate (also when all of them died), loci
+ * ascending, then `KMER\tMI\tMA` ascending by k-mer. */
+dbtk_status_t dbtk_kcp_fps_write(dbtk_kcp_fps_t* fps, const char* path);
+/* Of all applies: milliseconds in k_kcp_fps_apply (HIP events) and living candidates looked up. */
+dbtk_status_t dbtk_kcp_fps_times(dbtk_kcp_fps_t* fps, double* apply_ms, uint64_t* lookups);
+void dbtk_kcp_fps_free(dbtk_kcp_fps_t* fps);
+
+/* kcp_mean_text / kcp_sd_text evaluated on the device over host arrays of moments (n[i] >= 1, n[i] * sumsq[i] >= sum[i]^2, else
+ * DBTK_ERR_ARG): the floats `ktools fps` would parse from a profile line of such an entry.  For tests and bindings: moments like
+ * these cannot all be produced by adding reads. */
+dbtk_status_t dbtk_kcp_text_stats(int device_id, const uint32_t* n, const uint64_t* sum, const uint64_t* sumsq, uint64_t count, float* mean_out, float* sd_out);
+/* (All of the above were added without moving DBTK_KCP_API_VERSION: nothing that existed changed.) */
+
 #ifdef __cplusplus
 }
 #endif

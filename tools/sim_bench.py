@@ -51,9 +51,12 @@ def digits(v, width):
     return out
 
 
-def build_assembly(syn, nloci, min_bases, seed=5):
-    """[(name, uint8 array)] and the BED rows (contig index, start, end, label) — loci in order, NCTG contigs of equal locus count"""
+def build_assembly(syn, nloci, min_bases, seed=5, hap=0, mislabel=True):
+    """[(name, uint8 array)] and the BED rows (contig index, start, end, label) — loci in order, NCTG contigs of equal locus count.
+    hap: the haplotype of every locus that is laid out (its last where it has fewer); mislabel: one locus in ten under the next
+    locus' index (tools/fps_bench.py lays out further genomes with true labels)."""
     seq, hap_beg, lh0 = syn.sequences()
+    lh0 = np.array([min(int(lh0[l]) + hap, int(lh0[l + 1]) - 1) for l in range(nloci)] + [0])
     rng = np.random.default_rng(seed)
     size0 = int(sum(int(hap_beg[lh0[l] + 1] - hap_beg[lh0[l]]) for l in range(nloci)))
     gap = max(100, -(-(min_bases - size0) // nloci))
@@ -66,7 +69,7 @@ def build_assembly(syn, nloci, min_bases, seed=5):
             g = bases[rng.integers(0, 4, int(rng.integers(gap // 2, gap + gap // 2 + 1)))]
             h = seq[int(hap_beg[lh0[l]]):int(hap_beg[lh0[l] + 1])]
             pos += len(g)
-            bed.append((c, pos + FLANK, pos + len(h) - FLANK, (l + 1) % nloci if l % 10 == 0 else l))
+            bed.append((c, pos + FLANK, pos + len(h) - FLANK, (l + 1) % nloci if mislabel and l % 10 == 0 else l))
             pos += len(h)
             parts += [g, h]
         if parts:
