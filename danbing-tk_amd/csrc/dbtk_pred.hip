@@ -202,14 +202,13 @@ __global__ void __launch_bounds__(64) k_pred_wfused(const uint64_t* __restrict__
 //      + k_pred_bias (acc = 0; acc += G / ikmc; acc / n), so the result has the same bits.  Only the adds are ordered.
 // LDS: 18 KB of prefix sums (padded by one value per DS_E: the scan's 72-byte lane stride is 2-way conflicted instead of 16-way)
 // + 4 KB of terms.  No atomics: a column loaded again is simply overwritten.
-constexpr int DS_T = 256, DS_E = 8, DS_CH = DS_T * DS_E, DS_TB = 1024;
-constexpr uint32_t NOPART = 0xFFFFFFFFu;
-struct DosItem {
-    uint32_t k0, nkm;   // the item's k-mers: [k0, k0 + nkm), nkm <= DS_CH
-    uint32_t l0, nl;    // whole loci l0 .. l0 + nl - 1 lie in that range (nl = 0: a part of locus l0)
-    uint32_t part;      // NOPART, or the partial slot the range's total goes to
-    uint32_t nlb;       // loci from l0 on whose raw bias this item makes (nl; 1 for the first part of a large locus; 0 else, or without invariant k-mers)
-};
+// DosItem, DS_T, DS_E, DS_CH and the host's dosage_items: dbtk_pred_plan.h.
+using dbtk_pred_plan::DosItem;
+using dbtk_pred_plan::DS_T;
+using dbtk_pred_plan::DS_E;
+using dbtk_pred_plan::DS_CH;
+using dbtk_pred_plan::NOPART;
+constexpr int DS_TB = 1024;
 __device__ __forceinline__ int ds_pad(uint32_t k) { return (int)(k + (k >> 3)); }
 
 __global__ void __launch_bounds__(DS_T) k_dosage_sample(const uint64_t* __restrict__ counts, float depth, const DosItem* __restrict__ items,
@@ -845,30 +844,6 @@ struct dbtk_dosage {
 };
 constexpr uint64_t DS_STAGE = 16;  // samples per transfer of dbtk_dosage_load_samples (what danbing-tk-pred stages for the matrix, too)
 
-// the work list of k_dosage_sample: whole loci packed greedily into items of at most DS_CH k-mers, larger loci cut into parts
-static void dosage_items(uint64_t ntr, const uint32_t* nk_cum, const uint32_t* nik_cum, bool with_bias, std::vector<DosItem>* items, std::vector<uint32_t>* floc, std::vector<uint32_t>* fbeg) {
-    DosItem cur{0, 0, 0, 0, NOPART, 0};
-    auto flush = [&] { if (cur.nl) { cur.nlb = with_bias ? cur.nl : 0; items->push_back(cur); } cur = DosItem{0, 0, 0, 0, NOPART, 0}; };
-    uint32_t nparts = 0;
-    fbeg->push_back(0);
-    for (uint64_t t = 0; t < ntr; ++t) {
-        const LocusSpan L = locus_span(nk_cum, nik_cum, t);
-        const uint32_t a = L.si, n = L.ei - L.si;
-        if (n > (uint32_t)DS_CH) {
-            flush();
-            for (uint32_t o = 0; o < n; o += DS_CH)
-                items->push_back(DosItem{a + o, std::min<uint32_t>(DS_CH, n - o), (uint32_t)t, 0, nparts++, (with_bias && !o) ? 1u : 0u});
-            floc->push_back((uint32_t)t);
-            fbeg->push_back(nparts);
-            continue;
-        }
-        if (cur.nl && cur.nkm + n > (uint32_t)DS_CH) flush();
-        if (!cur.nl) { cur.k0 = a; cur.l0 = (uint32_t)t; }
-        cur.nkm += n; ++cur.nl;
-    }
-    flush();
-}
-
 extern "C" {
 
 void dbtk_dosage_free(dbtk_dosage_t* d) {
@@ -888,7 +863,7 @@ static dbtk_status_t dbtk_dosage_create_impl(int device_id, uint64_t ns, uint64_
     { const dbtk_status_t cs = check_ikmer_meta(device_id, ns, nk, ntr, nk_cum, nik_cum, nik, iki, ikmc); if (cs) return cs; }
     std::vector<DosItem> items;
     std::vector<uint32_t> floc, fbeg;
-    dosage_items(ntr, nk_cum, nik_cum, nik != 0, &items, &floc, &fbeg);
+    dbtk_pred_plan::dosage_items(ntr, nk_cum, nik != 0, &items, &floc, &fbeg);  // the work list of k_dosage_sample
     if (items.size() > 0x7FFFFFFFull) { set_error("too many work items for one launch"); return DBTK_ERR_ARG; }
     std::unique_ptr<dbtk_dosage, void (*)(dbtk_dosage*)> hold(new dbtk_dosage, dbtk_dosage_free);  // (freed, should a vector or a string below throw)
     dbtk_dosage* d = hold.get();
