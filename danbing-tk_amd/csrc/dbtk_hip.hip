@@ -13,7 +13,6 @@
 #include <unistd.h>
 
 #include <algorithm>
-#include <deque>
 #include <functional>
 #include <map>
 #include <atomic>
@@ -212,6 +211,7 @@ __global__ void __launch_bounds__(256) k_loc_rest(LocItemArgs a) { DevX x{nullpt
 // waves share it and the more workgroups a CU holds (4 x 4, 2 x 8, 1 x 16 waves)
 constexpr int LOC_IMGB_XS = LOC_HDR + (32 << 9) + (1 << 9), LOC_IMGB_S = LOC_HDR + (32 << 10) + (1 << 10), LOC_IMGB_L = LOC_HDR + (32 << LOC_LG_MAX) + (1 << LOC_LG_MAX);
 constexpr int LOC_NW_XS = 4, LOC_NW_S = 8, LOC_NW_L = 16;
+constexpr int LOC_NW[3] = {LOC_NW_XS, LOC_NW_S, LOC_NW_L};
 // FUSE: the kernel also resolves the usual pairs of its items (dbtk_locus.h)
 template <int NPL, int NW, int IMGB, bool FUSE = false> __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4, 8))) k_probe_locus(BatchArgs a, LocRunArgs r) {
     __shared__ LocSmemT<NPL, NW, IMGB, FUSE> sm;
@@ -303,18 +303,50 @@ static bool sync_only(const char* name) {
     static const char* pat = getenv("DBTK_SYNC_ONLY");
     return pat && *pat && strstr(name, pat) != nullptr;
 }
-#define LAUNCH(kern, grid, block, stream, ...)                                                        \
+#define LAUNCH_AS(kern, name, grid, block, stream, ...)                                               \
     do {                                                                                              \
-        if (trace_launches()) fprintf(stderr, "[launch] %s grid %u block %u\n", #kern, (unsigned)dim3(grid).x, (unsigned)dim3(block).x); \
+        if (trace_launches()) fprintf(stderr, "[launch] %s grid %u block %u\n", name, (unsigned)dim3(grid).x, (unsigned)dim3(block).x); \
         hipLaunchKernelGGL(kern, grid, block, 0, stream, __VA_ARGS__);                                \
         hipError_t e_ = hipGetLastError();                                                            \
-        if (e_ == hipSuccess && (sync_launches() || trace_launches() || sync_only(#kern))) e_ = hipStreamSynchronize(stream); \
-        if (trace_launches()) fprintf(stderr, "[launch] %s done: %s\n", #kern, hipGetErrorString(e_)); \
+        if (e_ == hipSuccess && (sync_launches() || trace_launches() || sync_only(name))) e_ = hipStreamSynchronize(stream); \
+        if (trace_launches()) fprintf(stderr, "[launch] %s done: %s\n", name, hipGetErrorString(e_)); \
         if (e_ != hipSuccess) {                                                                       \
-            set_error(std::string("kernel " #kern ": ") + hipGetErrorString(e_));                     \
+            set_error(std::string("kernel ") + name + ": " + hipGetErrorString(e_));                  \
             return DBTK_ERR_HIP;                                                                      \
         }                                                                                             \
     } while (0)
+#define LAUNCH(kern, grid, block, stream, ...) LAUNCH_AS(kern, #kern, grid, block, stream, __VA_ARGS__)
+// An instance of a kernel template and its name as LAUNCH prints it; a family's instances stand in ONE table (below the
+// kernels' parameters, in front of the context), which the occupancy queries and the launcher both index.
+template <class... A>
+struct Kern {
+    void (*fn)(A...);
+    const char* name;
+};
+#define KERN(...) {__VA_ARGS__, "(" #__VA_ARGS__ ")"}
+#define LAUNCH_K(k, grid, block, stream, ...) LAUNCH_AS((k).fn, (k).name, grid, block, stream, __VA_ARGS__)
+namespace {
+#define LOC_CLASSES(K, ...) {KERN(K<__VA_ARGS__, LOC_NW_XS, LOC_IMGB_XS>), KERN(K<__VA_ARGS__, LOC_NW_S, LOC_IMGB_S>), KERN(K<__VA_ARGS__, LOC_NW_L, LOC_IMGB_L>)}
+#define LOC_CLASSES_FUSED(K, ...) {KERN(K<__VA_ARGS__, LOC_NW_XS, LOC_IMGB_XS, true>), KERN(K<__VA_ARGS__, LOC_NW_S, LOC_IMGB_S, true>), KERN(K<__VA_ARGS__, LOC_NW_L, LOC_IMGB_L, true>)}
+const Kern<BatchArgs, LocRunArgs> K_PROBE_LOCUS[2][2][3] = {  // [fused][npl == 5][class]
+    {LOC_CLASSES(k_probe_locus, 3), LOC_CLASSES(k_probe_locus, 5)}, {LOC_CLASSES_FUSED(k_probe_locus, 3), LOC_CLASSES_FUSED(k_probe_locus, 5)}};
+const Kern<WalkArgs, LocRunArgs> K_WALK_FAST_LOCUS[2][3] = {LOC_CLASSES(k_walk_fast_locus, 3), LOC_CLASSES(k_walk_fast_locus, 5)};  // [npl == 5][class]
+const Kern<WalkArgs, LocRunArgs> K_WALK_PAIRS_LOCUS[3] = {KERN(k_walk_pairs_locus<LOC_IMGB_XS>), KERN(k_walk_pairs_locus<LOC_IMGB_S>), KERN(k_walk_pairs_locus<LOC_IMGB_L>)};  // [class]
+#undef LOC_CLASSES
+#undef LOC_CLASSES_FUSED
+#define P2_FORMS(NPL, WN) {{KERN(k_probe<NPL, WN, false, false>), KERN(k_probe<NPL, WN, false, true>)}, {KERN(k_probe<NPL, WN, true, false>), KERN(k_probe<NPL, WN, true, true>)}}
+const Kern<BatchArgs> K_PROBE[4][2][2] = {P2_FORMS(3, 7), P2_FORMS(3, 11), P2_FORMS(5, 7), P2_FORMS(5, 11)};  // [vi][sel][fused], vi: NPL 3 | 5, windows of 7 | 11
+#undef P2_FORMS
+const Kern<WalkArgs> K_WALK_FAST[2][2] = {{KERN(k_walk_fast<3, 7>), KERN(k_walk_fast<3, 11>)}, {KERN(k_walk_fast<5, 7>), KERN(k_walk_fast<5, 11>)}};  // [npl == 5][w11]
+// by nsi = 0 | 1 | 2: NS = 2 | 3 | 4 slots of 64 positions (and the kernel's flags)
+const Kern<BatchArgs> K_PROBE_GENERAL[3] = {KERN(k_probe_general<2>), KERN(k_probe_general<3>), KERN(k_probe_general<4>)};
+const Kern<BatchArgs> K_PAIR[2][3] = {{KERN(k_pair<2, false>), KERN(k_pair<3, false>), KERN(k_pair<4, false>)}, {KERN(k_pair<2, true>), KERN(k_pair<3, true>), KERN(k_pair<4, true>)}};  // [recs][nsi]
+const Kern<BatchArgs> K_PAIR_BUB[2][3] = {{KERN(k_pair_bub<2, false>), KERN(k_pair_bub<3, false>), KERN(k_pair_bub<4, false>)}, {KERN(k_pair_bub<2, true>), KERN(k_pair_bub<3, true>), KERN(k_pair_bub<4, true>)}};  // [recs][nsi]
+enum { USUAL_PLAIN, USUAL_RECS, USUAL_SEL };  // k_pair_usual: no records | records | no records, over the list the fused locus-resident kernel left
+const Kern<BatchArgs> K_PAIR_USUAL[3][3] = {{KERN(k_pair_usual<2, false>), KERN(k_pair_usual<3, false>), KERN(k_pair_usual<4, false>)},
+                                            {KERN(k_pair_usual<2, true>), KERN(k_pair_usual<3, true>), KERN(k_pair_usual<4, true>)},
+                                            {KERN(k_pair_usual<2, false, true>), KERN(k_pair_usual<3, false, true>), KERN(k_pair_usual<4, false, true>)}};  // [form][nsi]
+}  // namespace
 
 #define HIPCHK(call)                                                                                  \
     do {                                                                                              \
@@ -397,13 +429,68 @@ private:
 };
 
 constexpr uint32_t TK_INLINE = 8;  // words in front of d_small (same allocation): the chunk counters of a batch of up to three chunks
+constexpr uint32_t SMALL_WORDS = 64;  // d_small: nsurv, (unused), nrec, errflag (sticky until reported); stamps at +32
+
+// A device array that grows as batches need it: by a quarter more than asked for, the old one freed first (nothing in it is kept).
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    uint64_t cap = 0;  // elements
+    dbtk_status_t ensure(uint64_t need) {
+        if (need <= cap && p) return DBTK_OK;
+        if (p) HIPCHK(hipFree(p));
+        p = nullptr;
+        const uint64_t ncap = need + need / 4 + 64;
+        HIPCHK(hipMalloc(&p, ncap * sizeof(T)));
+        cap = ncap;
+        return DBTK_OK;
+    }
+    void free() {
+        if (p) (void)hipFree(p);
+        p = nullptr; cap = 0;
+    }
+};
+
+// Everything a batch in flight owns.  Successive batches of the device-resident entry points go round the context's lanes, each
+// with its own stream and per-batch scratch, so that one batch's VALU-bound encode kernel overlaps another's request-bound probe
+// kernel (tables and accumulators are shared; the adds are atomic).
+struct Lane {
+    hipStream_t stream = nullptr;
+    uint32_t* d_small = nullptr;  // nsurv, novf, nrec, errflag (TK_INLINE words into its allocation)
+    DevBuf<uint32_t> d_surv;      // the encode stage's survivor list | the list in locus order | keys | histogram
+    uint32_t* d_sorted = nullptr; // (inside d_surv) the sorted list of the last batch: what K2, K3 and the walk index
+    DevBuf<uint64_t> d_hitva;     // aux words of every row, then val words (4 + 4 bytes per position)
+    DevBuf<uint32_t> d_hitnk;
+    DevBuf<uint64_t> d_hitoff;
+    DevBuf<uint32_t> d_gen;       // K3a -> K3b
+    DevBuf<uint32_t> d_tickets;
+    DevBuf<uint32_t> d_walk;      // threading = 2, per survivor: destLocus [cap], then the walk's return codes [cap]
+    uint64_t* d_vote = nullptr;
+    uint32_t* d_epoch = nullptr;
+    DevBuf<uint64_t> d_edge;      // -bu: the K2 -> K3 edge buffer of a chunk
+    DevBuf<uint64_t> d_qmask;     // -b with qualities: K2 -> K3 of the same batch, like d_edge, so every lane has its own
+    // blocks of the device reader merged into one batch (dbtk_ingest_align_merged): reads back to back, offsets
+    DevBuf<uint8_t> m_flat;
+    DevBuf<uint64_t> m_off;
+    uint64_t m_bytes = 0, m_pairs = 0; uint32_t m_maxlen = 0;
+};
+
+// What lives here and not in a lane: (1) what every lane shares by design and updates with atomics — the accumulators, the counter
+// replicas, the path statistics, the pinned hint words, the -bu table with its words and spill log; (2) the buffers of the synchronous
+// entry points (d_seq, d_off, d_qual, d_recs, d_trecs, d_loci, d_aln, d_txt, d_txtidx, h_aln): a batch that uses them is waited for
+// before the next begins (run_batch_sync, dbtk_thread_batch).  Anything a batch in flight writes and a later kernel of the same batch
+// reads belongs in Lane.
 struct dbtk_ctx {
     TableShare* share = nullptr;
     const dbtk_rpgg* g = nullptr;
     uint64_t g_uid = 0;           // g->uid, kept apart: releasing the tables must not touch a handle the caller may have freed first
     dbtk_params_t P;
     int device = 0;
-    hipStream_t stream = nullptr;
+    // switch_lane steps `cur` round the ring: lane 0, 1, 2, 0, ... — the order the lanes took turns in when they were a current lane,
+    // an alternate and a queue of parked ones
+    std::vector<Lane> lanes;
+    size_t cur = 0;
+    Lane& lane() { return lanes[cur]; }
     DevTables T;                  // the share's tables as the kernels get them (a copy of share->T, taken once the optional tables are in)
     // device allocations
     int wfl_blocks[6] = {0, 0, 0, 0, 0, 0};  // workgroups of k_walk_fast_locus<3 | 5, class 0 | 1 | 2>
@@ -413,38 +500,24 @@ struct dbtk_ctx {
     uint64_t* d_accum = nullptr;  // counts | kmc | nmapread | counters
     uint64_t* d_ctr = nullptr;    // counter replicas (folded into d_accum's counters before anything reads them: sync_all)
     bool fold_pending = false;    // batches have been launched since the replicas were last folded
-    uint8_t* m_flat = nullptr; uint64_t m_flat_cap = 0;   // the current lane's merged blocks (dbtk_ingest_align_merged; Lane::m_*)
-    uint64_t* m_off = nullptr; uint64_t m_off_cap = 0;
-    uint64_t m_bytes = 0, m_pairs = 0; uint32_t m_maxlen = 0;
     uint64_t* d_pstats = nullptr; // path statistics (dbtk.h: dbtk_ctx_path_stats): which kernels took how many pairs; never part of the results
     uint64_t n_accum = 0, ntr = 0;
-    uint32_t* d_small = nullptr;  // nsurv, novf, nrec, errflag
-    uint32_t* d_surv = nullptr; uint64_t surv_cap = 0;  // the encode stage's survivor list | the list in locus order | keys | histogram
-    uint32_t* d_sorted = nullptr;                       // (inside d_surv) the sorted list of the last batch: what K2, K3 and the walk index
-    uint8_t* d_seq = nullptr; uint64_t seq_cap = 0;
-    uint64_t* d_off = nullptr; uint64_t off_cap = 0;
-    dbtk_pair_rec_t* d_recs = nullptr; uint64_t rec_cap = 0;
-    uint64_t* d_hitva = nullptr; uint64_t hitva_cap = 0;   // aux words of every row, then val words (4 + 4 bytes per position)
-    uint32_t* d_hitnk = nullptr; uint64_t hitnk_cap = 0;
-    uint64_t* d_hitoff = nullptr; uint64_t hitoff_cap = 0;
-    uint32_t* d_gen = nullptr; uint64_t gen_cap = 0;        // K3a -> K3b
-    uint32_t* d_tickets = nullptr; uint64_t tickets_cap = 0;
-    uint32_t* d_walk = nullptr; uint64_t walk_cap = 0;       // threading = 2, per survivor: destLocus [cap], then the walk's return codes [cap]
-    dbtk_thread_rec_t* d_trecs = nullptr; uint64_t trecs_cap = 0;  // thread records (function mode; pair mode with trace / -a)
-    uint32_t* d_loci = nullptr; uint64_t loci_cap = 0;       // function mode: locus per read
+    DevBuf<uint8_t> d_seq;
+    DevBuf<uint64_t> d_off;
+    DevBuf<dbtk_pair_rec_t> d_recs;
+    DevBuf<dbtk_thread_rec_t> d_trecs;  // thread records (function mode; pair mode with trace / -a)
+    DevBuf<uint32_t> d_loci;            // function mode: locus per read
     uint8_t* d_aln = nullptr; uint64_t aln_bytes = 0;        // -a / -ae: compact alignment records of the last host-buffer batch
     uint8_t* d_txt = nullptr; uint64_t txt_bytes = 0;        // -a / -ae | DBTK_ALN_TEXT: the text arena of the last host-buffer batch
-    uint32_t* d_txtidx = nullptr; uint64_t txtidx_cap = 0;   //   ... and its per-pair index
+    DevBuf<uint32_t> d_txtidx;                               //   ... and its per-pair index
     uint64_t txt_cap = 0;                                    //   bytes of the arena the last batch could use
     uint32_t aln_stride = 0, aln_cap = 0; uint64_t aln_max = 0;
     uint8_t* h_aln = nullptr; size_t h_aln_bytes = 0;  // pinned staging of dbtk_ctx_aln_records
     uint64_t last_walk_npairs = 0; bool last_walk_recs = false;  // what dbtk_ctx_walk_results may fetch
     int walk_blocks = 0, walkfast_blocks = 0;
     // optional gates
-    uint8_t* d_qual = nullptr; uint64_t qual_cap = 0;
-    uint64_t* d_edge = nullptr; uint64_t edge_cap = 0;
-    uint64_t* d_qmask = nullptr; uint64_t qmask_cap = 0;
-    BubEvent* d_events = nullptr; uint64_t events_cap = 0;
+    DevBuf<uint8_t> d_qual;
+    DevBuf<BubEvent> d_events;
     uint32_t* d_nevents = nullptr;
     // params.bubbles = DBTK_BUBBLES_TABLE (dbtk_bubtab.h): the table, and the host's pinned copy of occupancy | spill count | sticky word
     // (d_events is then the spill log, d_nevents the BUB_W_* words)
@@ -463,34 +536,9 @@ struct dbtk_ctx {
     bool timers_on = true;
     uint32_t timers_every = 1;  // event records around the kernels of every n-th batch (8 records cost ~30 us per batch)
     uint64_t batch_no = 0;
-    uint64_t* d_vote = nullptr;
-    uint32_t* d_epoch = nullptr;
     int pair_blocks[3] = {0, 0, 0}, usual_blocks[3] = {0, 0, 0}, num_cu = 0, max_pair_blocks = 0;
     int vote_rows = 0;  // rows of the vote-spill pool: the workgroups of the general resolve kernel that can be resident at once
     Timed timed[NKERN];
-    // Second lane of the device-resident entry point: successive batches alternate between two streams, each with its own
-    // per-batch scratch, so that one batch's VALU-bound encode kernel overlaps the other's request-bound probe kernel
-    // (tables and accumulators are shared; the adds are atomic).  `alt` holds the lane that is not current.
-    struct Lane {
-        hipStream_t stream = nullptr;
-        uint32_t* d_small = nullptr;
-        uint32_t* d_surv = nullptr; uint64_t surv_cap = 0; uint32_t* d_sorted = nullptr;
-        uint64_t* d_hitva = nullptr; uint64_t hitva_cap = 0;   // aux words of every row, then val words (4 + 4 bytes per position)
-        uint32_t* d_hitnk = nullptr; uint64_t hitnk_cap = 0;
-        uint64_t* d_hitoff = nullptr; uint64_t hitoff_cap = 0;
-        uint32_t* d_gen = nullptr; uint64_t gen_cap = 0;
-        uint32_t* d_tickets = nullptr; uint64_t tickets_cap = 0;
-        uint32_t* d_walk = nullptr; uint64_t walk_cap = 0;
-        uint64_t* d_vote = nullptr;
-        uint32_t* d_epoch = nullptr;
-        uint64_t* d_edge = nullptr; uint64_t edge_cap = 0;  // -bu with the device table: every lane its own K2 -> K3 edge buffer
-        // blocks of the device reader merged into one batch (dbtk_ingest_align_merged): reads back to back, offsets
-        uint8_t* m_flat = nullptr; uint64_t m_flat_cap = 0;
-        uint64_t* m_off = nullptr; uint64_t m_off_cap = 0;
-        uint64_t m_bytes = 0, m_pairs = 0; uint32_t m_maxlen = 0;
-    } alt;
-    std::deque<Lane> parked;  // lanes beyond the second (DBTK_LANES > 2): switch_lane goes round all of them
-    bool two_lanes = false;   // more than one lane
 };
 
 namespace {
@@ -501,6 +549,8 @@ uint64_t pow2_at_least(uint64_t n) {
     return c;
 }
 uint32_t log2u(uint64_t c) { return 63u - (uint32_t)__builtin_clzll(c); }
+// the grid of a grid-stride kernel of 256 threads: a block per 256 elements, at most eight per CU
+uint32_t grid256(const dbtk_ctx* c, uint64_t n) { return (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)c->num_cu * 8); }
 
 std::mutex g_share_m;
 std::map<std::pair<uint64_t, int>, TableShare*> g_shares;  // (handle's uid, device): see dbtk_rpgg::uid
@@ -519,6 +569,33 @@ void release_share(dbtk_ctx* c) {
     drop_share(sh);
 }
 
+// A lane's stream and the buffers whose size is known when the context is made, zeroed on that stream (the others grow with the
+// batches: launch_batch).  Every lane of a context is made here, the first one included.
+dbtk_status_t lane_create(const dbtk_ctx* c, Lane& l) {
+    dbtk_status_t st = DBTK_OK;
+    auto chk = [&](hipError_t e, const char* what) { if (e != hipSuccess && !st) { set_error(std::string(what) + ": " + hipGetErrorString(e)); st = DBTK_ERR_HIP; } };
+    const size_t small_bytes = 4 * (TK_INLINE + SMALL_WORDS) + 48 * 8, vote_bytes = (size_t)c->vote_rows * (c->g->nloci + 1) * 8, epoch_bytes = (size_t)c->vote_rows * 16;
+    if (hipStreamCreate(&l.stream) != hipSuccess) { set_error("hipStreamCreate failed"); return DBTK_ERR_HIP; }
+    chk(hipMalloc(&l.d_small, small_bytes), "hipMalloc small");
+    if (l.d_small) l.d_small += TK_INLINE;
+    chk(hipMalloc(&l.d_vote, vote_bytes), "hipMalloc vote scratch");
+    chk(hipMalloc(&l.d_epoch, epoch_bytes), "hipMalloc epoch");
+    if (st) return st;
+    chk(hipMemsetAsync(l.d_small - TK_INLINE, 0, small_bytes, l.stream), "memset");
+    chk(hipMemsetAsync(l.d_vote, 0, vote_bytes, l.stream), "memset");
+    chk(hipMemsetAsync(l.d_epoch, 0, epoch_bytes, l.stream), "memset");
+    return st;
+}
+void lane_free(Lane& l) {
+    if (l.d_small) (void)hipFree(l.d_small - TK_INLINE);
+    if (l.d_vote) (void)hipFree(l.d_vote);
+    if (l.d_epoch) (void)hipFree(l.d_epoch);
+    l.d_surv.free(); l.d_hitva.free(); l.d_hitnk.free(); l.d_hitoff.free(); l.d_gen.free(); l.d_tickets.free(); l.d_walk.free();
+    l.d_edge.free(); l.d_qmask.free(); l.m_flat.free(); l.m_off.free();
+    if (l.stream) (void)hipStreamDestroy(l.stream);
+    l = Lane{};
+}
+
 void free_ctx(dbtk_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
@@ -528,22 +605,13 @@ void free_ctx(dbtk_ctx* c) {
             if (c->timed[i].beg[j]) (void)hipEventDestroy(c->timed[i].beg[j]);
             if (c->timed[i].end[j]) (void)hipEventDestroy(c->timed[i].end[j]);
         }
-    void* ptrs[] = {c->m_flat, c->m_off, c->d_ctr, c->d_pstats, c->d_accum, c->d_small ? c->d_small - TK_INLINE : nullptr, c->d_surv,
-                    c->d_seq, c->d_off, c->d_recs, c->d_vote, c->d_epoch, c->d_hitva, c->d_hitnk, c->d_hitoff, c->d_gen, c->d_tickets,
-                    c->d_qual, c->d_edge, c->d_qmask, c->d_events, c->d_nevents, c->d_walk, c->d_trecs, c->d_loci, c->d_aln, c->d_txt, c->d_txtidx, c->d_bub};
+    void* ptrs[] = {c->d_ctr, c->d_pstats, c->d_accum, c->d_seq.p, c->d_off.p, c->d_recs.p, c->d_qual.p, c->d_events.p, c->d_nevents,
+                    c->d_trecs.p, c->d_loci.p, c->d_aln, c->d_txt, c->d_txtidx.p, c->d_bub};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (c->h_bub) (void)hipHostFree(c->h_bub);
     if (c->h_aln) (void)hipHostFree(c->h_aln);
     if (c->h_sortflag) (void)hipHostFree(c->h_sortflag);
-    std::vector<dbtk_ctx::Lane*> others{&c->alt};
-    for (auto& l : c->parked) others.push_back(&l);
-    for (dbtk_ctx::Lane* l : others) {
-        void* aptrs[] = {l->d_small ? l->d_small - TK_INLINE : nullptr, l->d_surv, l->d_hitva, l->d_hitnk, l->d_hitoff, l->d_gen, l->d_tickets, l->d_vote, l->d_epoch, l->d_walk, l->m_flat, l->m_off, l->d_edge};
-        for (void* p : aptrs) if (p) (void)hipFree(p);
-        if (l != &c->alt && l->stream) (void)hipStreamDestroy(l->stream);
-    }
-    if (c->alt.stream) (void)hipStreamDestroy(c->alt.stream);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    for (Lane& l : c->lanes) lane_free(l);
     delete c;
 }
 
@@ -1127,17 +1195,6 @@ dbtk_status_t build_kl_table(const TableBuild& b, const std::vector<uint64_t>& c
     return DBTK_OK;
 }
 
-template <class T>
-dbtk_status_t ensure(T** p, uint64_t* cap, uint64_t need) {
-    if (need <= *cap && *p) return DBTK_OK;
-    if (*p) HIPCHK(hipFree(*p));
-    *p = nullptr;
-    const uint64_t ncap = need + need / 4 + 64;
-    HIPCHK(hipMalloc(p, ncap * sizeof(T)));
-    *cap = ncap;
-    return DBTK_OK;
-}
-
 // fold the recorded event pairs of one kernel into its totals (stream must be idle)
 void fold_timer(Timed& t) {
     for (int j = 0; j < t.used; ++j) {
@@ -1146,36 +1203,18 @@ void fold_timer(Timed& t) {
     }
     t.used = 0;
 }
-void switch_lane(dbtk_ctx* c) {
-    std::swap(c->stream, c->alt.stream); std::swap(c->d_small, c->alt.d_small);
-    std::swap(c->d_surv, c->alt.d_surv); std::swap(c->surv_cap, c->alt.surv_cap); std::swap(c->d_sorted, c->alt.d_sorted);
-    std::swap(c->d_hitva, c->alt.d_hitva); std::swap(c->hitva_cap, c->alt.hitva_cap);
-    std::swap(c->d_hitnk, c->alt.d_hitnk); std::swap(c->hitnk_cap, c->alt.hitnk_cap);
-    std::swap(c->d_hitoff, c->alt.d_hitoff); std::swap(c->hitoff_cap, c->alt.hitoff_cap);
-    std::swap(c->d_gen, c->alt.d_gen); std::swap(c->gen_cap, c->alt.gen_cap);
-    std::swap(c->d_tickets, c->alt.d_tickets); std::swap(c->tickets_cap, c->alt.tickets_cap);
-    std::swap(c->d_walk, c->alt.d_walk); std::swap(c->walk_cap, c->alt.walk_cap);
-    std::swap(c->d_vote, c->alt.d_vote); std::swap(c->d_epoch, c->alt.d_epoch);
-    std::swap(c->d_edge, c->alt.d_edge); std::swap(c->edge_cap, c->alt.edge_cap);
-    std::swap(c->m_flat, c->alt.m_flat); std::swap(c->m_flat_cap, c->alt.m_flat_cap); std::swap(c->m_off, c->alt.m_off); std::swap(c->m_off_cap, c->alt.m_off_cap);
-    std::swap(c->m_bytes, c->alt.m_bytes); std::swap(c->m_pairs, c->alt.m_pairs); std::swap(c->m_maxlen, c->alt.m_maxlen);
-    if (!c->parked.empty()) {  // round robin: the lane just left goes to the back of the queue, the longest-parked one is next
-        c->parked.push_back(c->alt);
-        c->alt = c->parked.front();
-        c->parked.pop_front();
-    }
-}
+void switch_lane(dbtk_ctx* c) { c->cur = (c->cur + 1) % c->lanes.size(); }
 // Every reader of the accumulators comes through here (counts, the all-reduce, reset, the caller of dbtk_ctx_accum_buffer after
 // dbtk_ctx_synchronize): the counter replicas are folded into the counters once, now, instead of at the end of every batch (a launch of
 // one wave + its gap: 14 us of a 1.2-ms step).
 hipError_t sync_all(dbtk_ctx* c) {
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && c->alt.stream) e = hipStreamSynchronize(c->alt.stream);
-    for (auto& l : c->parked) if (e == hipSuccess && l.stream) e = hipStreamSynchronize(l.stream);
+    hipError_t e = hipSuccess;
+    for (Lane& l : c->lanes) if (e == hipSuccess) e = hipStreamSynchronize(l.stream);
     if (e == hipSuccess && c->fold_pending && c->d_ctr && c->d_accum) {
-        hipLaunchKernelGGL(k_fold_counters, dim3(1), dim3(64), 0, c->stream, c->d_accum + c->ntr + 2 * (uint64_t)c->g->nloci, c->d_ctr, c->d_pstats);
+        hipStream_t s = c->lane().stream;
+        hipLaunchKernelGGL(k_fold_counters, dim3(1), dim3(64), 0, s, c->d_accum + c->ntr + 2 * (uint64_t)c->g->nloci, c->d_ctr, c->d_pstats);
         e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e == hipSuccess) c->fold_pending = false;
     }
     return e;
@@ -1201,7 +1240,7 @@ dbtk_status_t bub_new_table(dbtk_ctx* c, uint64_t slots, BubSlot** out) {
         set_error("bubble table: no device memory for " + std::to_string(slots) + " slots (" + std::to_string(slots * sizeof(BubSlot)) + " bytes)");
         return DBTK_ERR_NOMEM;
     }
-    LAUNCH(k_bub_fill, dim3((uint32_t)std::min<uint64_t>((slots + 255) / 256, 4096)), dim3(256), c->stream, *out, slots);
+    LAUNCH(k_bub_fill, dim3((uint32_t)std::min<uint64_t>((slots + 255) / 256, 4096)), dim3(256), c->lane().stream, *out, slots);
     return DBTK_OK;
 }
 // A new table of twice the slots or more, the old entries and the spill log (and `extra`, a list of n_extra further entries: merge)
@@ -1209,10 +1248,10 @@ dbtk_status_t bub_new_table(dbtk_ctx* c, uint64_t slots, BubSlot** out) {
 // attempt that leaves an entry without a slot is thrown away whole and repeated with twice the slots, so nothing is counted twice.
 dbtk_status_t bub_grow(dbtk_ctx* c, uint64_t room, const BubEvent* d_extra = nullptr, uint64_t n_extra = 0) {
     // (a merge that fits under half of the slots there are gets a table of the same size: eight contexts merged must not be eight doublings)
-    hipStream_t s = c->stream;
+    hipStream_t s = c->lane().stream;
     uint32_t w[BUB_WORDS];
     HIPCHK(hipMemcpy(w, c->d_nevents, sizeof(w), hipMemcpyDeviceToHost));
-    const uint64_t nsp = std::min<uint64_t>(w[BUB_W_SPILL], c->events_cap);
+    const uint64_t nsp = std::min<uint64_t>(w[BUB_W_SPILL], c->d_events.cap);
     uint64_t cap = d_extra ? c->bub_slots : c->bub_slots * 2;
     while (2 * ((uint64_t)w[BUB_W_OCC] + nsp + n_extra + room) > cap) cap <<= 1;
     for (;;) {
@@ -1223,10 +1262,10 @@ dbtk_status_t bub_grow(dbtk_ctx* c, uint64_t room, const BubEvent* d_extra = nul
         HIPCHK(hipMemsetAsync(c->d_nevents + BUB_W_FAIL, 0, 4, s));
         const uint64_t mask = cap - 1;
         const uint32_t shift = 64 - log2u(cap);
-        const uint32_t grid = (uint32_t)std::min<uint64_t>((c->bub_slots + 255) / 256, (uint64_t)c->num_cu * 8);
+        const uint32_t grid = grid256(c, c->bub_slots);
         LAUNCH(k_bub_rehash, dim3(grid), dim3(256), s, c->d_bub, c->bub_slots, nt, mask, shift, c->d_nevents);
-        if (nsp) LAUNCH(k_bub_add, dim3((uint32_t)std::min<uint64_t>((nsp + 255) / 256, (uint64_t)c->num_cu * 8)), dim3(256), s, c->d_events, nsp, nt, mask, shift, c->d_nevents);
-        if (n_extra) LAUNCH(k_bub_add, dim3((uint32_t)std::min<uint64_t>((n_extra + 255) / 256, (uint64_t)c->num_cu * 8)), dim3(256), s, d_extra, n_extra, nt, mask, shift, c->d_nevents);
+        if (nsp) LAUNCH(k_bub_add, dim3(grid256(c, nsp)), dim3(256), s, c->d_events.p, nsp, nt, mask, shift, c->d_nevents);
+        if (n_extra) LAUNCH(k_bub_add, dim3(grid256(c, n_extra)), dim3(256), s, d_extra, n_extra, nt, mask, shift, c->d_nevents);
         HIPCHK(hipMemcpyAsync(w, c->d_nevents, sizeof(w), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         if (w[BUB_W_FAIL] == 0) {
@@ -1262,12 +1301,12 @@ dbtk_status_t bub_before_batch(dbtk_ctx* c) {
 // ceil(npairs / SURV_CAP) chunk iterations are enqueued and the kernels of a chunk past the end
 // of the list exit at once; nothing waits for the host.
 constexpr uint64_t SURV_CAP = 1ull << 23;  // at most 51 GB of hit buffers at 150 bp (allocated for the batch size actually seen): one chunk for batches of up to 8 M pairs
-constexpr uint32_t SMALL_WORDS = 64;  // d_small: nsurv, (unused), nrec, errflag (sticky until reported); stamps at +32
 
 dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_off, uint64_t seq_len, uint64_t npairs,
                            uint32_t max_read_len, dbtk_pair_rec_t* d_recs, uint32_t rec_cap, const uint8_t* d_qual = nullptr,
                            dbtk_thread_rec_t* walk_trecs = nullptr, bool walk_aln = false, bool walk_txt = false) {
-    hipStream_t s = c->stream;
+    Lane& L = c->lane();
+    hipStream_t s = L.stream;
     if (npairs >= 0xFFFFFFFFull) { set_error("batch too large (pair index is 32-bit)"); return DBTK_ERR_ARG; }
     if (npairs == 0) return DBTK_OK;
     const bool bub_table = c->P.bubbles == DBTK_BUBBLES_TABLE;
@@ -1288,17 +1327,17 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
     uint32_t split_blk = 0;  // most workgroups any locus-resident launch has: three lists of workgroup ranges behind the rest list
     for (int q = 0; q < 6; ++q) split_blk = std::max(split_blk, (uint32_t)std::max(std::max(c->loc_blocks[q], c->locf_blocks[q]), c->wfl_blocks[q]));
     const uint64_t split_at = surv_words + 3 * 4 * item_cap + npairs + 4;
-    dbtk_status_t st = ensure(&c->d_surv, &c->surv_cap, split_at + 3 * ((uint64_t)split_blk + 1));
+    dbtk_status_t st = L.d_surv.ensure(split_at + 3 * ((uint64_t)split_blk + 1));
     if (st) return st;
-    if ((st = ensure(&c->d_hitoff, &c->hitoff_cap, tcap * 4))) return st;  // offsets, then headers
-    if ((st = ensure(&c->d_hitva, &c->hitva_cap, tcap * 2 * nkp))) return st;
-    if ((st = ensure(&c->d_hitnk, &c->hitnk_cap, tcap * 2))) return st;
-    if ((st = ensure(&c->d_gen, &c->gen_cap, tcap))) return st;
+    if ((st = L.d_hitoff.ensure(tcap * 4))) return st;  // offsets, then headers
+    if ((st = L.d_hitva.ensure(tcap * 2 * nkp))) return st;
+    if ((st = L.d_hitnk.ensure(tcap * 2))) return st;
+    if ((st = L.d_gen.ensure(tcap))) return st;
     // per chunk: a ticket counter and a passed-on counter — for up to three chunks in the TK_INLINE words in front of d_small, so that they
     // and nsurv / novf / nrec are zeroed by ONE memset
     const bool tk_inline = 2 * (nchunks + 1) <= TK_INLINE;
-    if (!tk_inline && (st = ensure(&c->d_tickets, &c->tickets_cap, 2 * (nchunks + 1)))) return st;
-    uint32_t* const tickets = tk_inline ? c->d_small - 2 * (nchunks + 1) : c->d_tickets;
+    if (!tk_inline && (st = L.d_tickets.ensure(2 * (nchunks + 1)))) return st;
+    uint32_t* const tickets = tk_inline ? L.d_small - 2 * (nchunks + 1) : L.d_tickets.p;
     const bool walking = c->P.threading == DBTK_THREADING_V13;
     uint64_t slow_cap = 0, info_rows = 0;
     if (walking) {
@@ -1306,48 +1345,48 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
         // passed-on pairs' positions (rows for an eighth of the pairs — with text records, where every pair with a dirty mate is passed
         // on, for half of them; a pair beyond that is looked up again by the other kernel)
         uint64_t wf_waves = 4ull * (uint64_t)c->walkfast_blocks;
-        for (int q = 0; q < 3; ++q) wf_waves += (uint64_t)std::max(c->wfl_blocks[q], c->wfl_blocks[3 + q]) * (q == 0 ? LOC_NW_XS : q == 1 ? LOC_NW_S : LOC_NW_L);
+        for (int q = 0; q < 3; ++q) wf_waves += (uint64_t)std::max(c->wfl_blocks[q], c->wfl_blocks[3 + q]) * LOC_NW[q];
         slow_cap = npairs + WF_R * wf_waves + 8;
         info_rows = std::min<uint64_t>(slow_cap, std::max<uint64_t>(walk_txt ? npairs / 2 : npairs / 8, 4096));
         if (const char* e = getenv("DBTK_WALK_INFO_ROWS")) info_rows = std::min<uint64_t>(slow_cap, (uint64_t)std::max<long>(atol(e), 0));  // diagnostic / tests: 0 = none, a few = both ways in one batch
-        if ((st = ensure(&c->d_walk, &c->walk_cap, 2 * npairs + slow_cap + info_rows * 2 * 160))) return st;
-        HIPCHK(hipMemsetAsync(c->d_walk, 0xFF, npairs * sizeof(uint32_t), s));  // NAN32: the pair does not reach threading
-        HIPCHK(hipMemsetAsync(c->d_walk + npairs, 0, npairs * sizeof(uint32_t), s));  // walk_ret: no pair is marked WALK_PENDING
+        if ((st = L.d_walk.ensure(2 * npairs + slow_cap + info_rows * 2 * 160))) return st;
+        HIPCHK(hipMemsetAsync(L.d_walk.p, 0xFF, npairs * sizeof(uint32_t), s));  // NAN32: the pair does not reach threading
+        HIPCHK(hipMemsetAsync(L.d_walk.p + npairs, 0, npairs * sizeof(uint32_t), s));  // walk_ret: no pair is marked WALK_PENDING
     }
     // nsurv, novf, nrec; the error word (3) stays until it has been reported
     if (tk_inline) HIPCHK(hipMemsetAsync(tickets, 0, (2 * (nchunks + 1) + 3) * sizeof(uint32_t), s));
     else {
-        HIPCHK(hipMemsetAsync(c->d_small, 0, 3 * sizeof(uint32_t), s));
+        HIPCHK(hipMemsetAsync(L.d_small, 0, 3 * sizeof(uint32_t), s));
         HIPCHK(hipMemsetAsync(tickets, 0, 2 * (nchunks + 1) * sizeof(uint32_t), s));
     }
     if (c->P.bubbles) {
-        if ((st = ensure(&c->d_edge, &c->edge_cap, tcap * 2 * nkp))) return st;
+        if ((st = L.d_edge.ensure(tcap * 2 * nkp))) return st;
         if (!bub_table) {
             // every position of every kept mate could be novel; bounded so that the log stays < 6.4 GB
             const uint64_t ecap = std::min<uint64_t>(npairs * 2 * nkmax, 1ull << 28);
-            if ((st = ensure(&c->d_events, &c->events_cap, ecap))) return st;
+            if ((st = c->d_events.ensure(ecap))) return st;
             HIPCHK(hipMemsetAsync(c->d_nevents, 0, sizeof(uint32_t), s));
         }
     }
-    if (c->P.bait && d_qual && (st = ensure(&c->d_qmask, &c->qmask_cap, tcap * 2 * 4))) return st;
+    if (c->P.bait && d_qual && (st = L.d_qmask.ensure(tcap * 2 * 4))) return st;
     BatchArgs a;
     memset(&a, 0, sizeof(a));
     { static const bool k1x = !(getenv("DBTK_K1_XCD") && atoi(getenv("DBTK_K1_XCD")) == 0); a.k1_xcd = k1x ? 1u : 0u; }
     a.T = c->T; a.P = c->P; a.P.aln &= 3u;
     a.seq = d_seq; a.off = d_off; a.seq_len = seq_len; a.npairs = npairs;
-    a.surv = c->d_surv; a.nsurv = c->d_small + 0; a.nrec = c->d_small + 2; a.errflag = c->d_small + 3;
+    a.surv = L.d_surv.p; a.nsurv = L.d_small + 0; a.nrec = L.d_small + 2; a.errflag = L.d_small + 3;
     a.counts = c->d_accum;
     a.kmc = c->d_accum + c->ntr;
     a.nmapread = a.kmc + c->g->nloci;
     a.counters = a.nmapread + c->g->nloci;
     a.ctr_rep = c->d_ctr;
     a.pstats = c->d_pstats;
-    a.sortflag = c->d_small + 6; a.hint_out = c->h_sortflag;
+    a.sortflag = L.d_small + 6; a.hint_out = c->h_sortflag;
     a.recs = d_recs; a.rec_cap = rec_cap;
-    a.vote_scratch = c->d_vote; a.vote_epoch = c->d_epoch; a.vote_rows = (uint32_t)c->vote_rows;
-    a.vote_busy = reinterpret_cast<uint64_t*>(c->d_epoch + ((c->vote_rows + 1) & ~1));  // (behind the epochs, 8-byte aligned)
-    a.walk_dst = walking ? c->d_walk : nullptr;
-    a.hitaux = reinterpret_cast<uint32_t*>(c->d_hitva); a.hitval = a.hitaux + tcap * 2 * nkp; a.hitnk = c->d_hitnk; a.hitoff = c->d_hitoff; a.hithdr = c->d_hitoff + tcap * 2; a.nkp = nkp; a.pair_base = 0; a.tcap = (uint32_t)tcap;
+    a.vote_scratch = L.d_vote; a.vote_epoch = L.d_epoch; a.vote_rows = (uint32_t)c->vote_rows;
+    a.vote_busy = reinterpret_cast<uint64_t*>(L.d_epoch + ((c->vote_rows + 1) & ~1));  // (behind the epochs, 8-byte aligned)
+    a.walk_dst = walking ? L.d_walk.p : nullptr;
+    a.hitaux = reinterpret_cast<uint32_t*>(L.d_hitva.p); a.hitval = a.hitaux + tcap * 2 * nkp; a.hitnk = L.d_hitnk.p; a.hitoff = L.d_hitoff.p; a.hithdr = L.d_hitoff.p + tcap * 2; a.nkp = nkp; a.pair_base = 0; a.tcap = (uint32_t)tcap;
     // the usual-pair kernel takes the pairs it can finish and passes the rest on; it needs the class of a k-mer next to its
     // index value (consistent RPGG) and does not do the trace, bait or bubble work
     const bool usual = c->T.consistent && !c->P.trace && !c->P.bait && !c->P.bubbles;
@@ -1357,11 +1396,11 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
     static const int fuse_on = [] { const char* e = getenv("DBTK_FUSE"); return e ? atoi(e) : 3; }();
     const bool fuse = usual && !d_recs && (fuse_on & 1);
     const bool fuse_lean = usual && !d_recs && (fuse_on & 2);
-    if (c->P.bubbles) { a.edgebuf = c->d_edge; a.events = c->d_events; a.nevents = c->d_nevents; a.events_cap = (uint32_t)std::min<uint64_t>(c->events_cap, 0xFFFFFFFFull); }
+    if (c->P.bubbles) { a.edgebuf = L.d_edge.p; a.events = c->d_events.p; a.nevents = c->d_nevents; a.events_cap = (uint32_t)std::min<uint64_t>(c->d_events.cap, 0xFFFFFFFFull); }
     if (bub_table) { a.bub = c->d_bub; a.bub_mask = c->bub_slots - 1; a.bub_shift = 64 - log2u(c->bub_slots); }
-    if (c->P.bait && d_qual) { a.qual = d_qual; a.qmaskbuf = c->d_qmask; }
+    if (c->P.bait && d_qual) { a.qual = d_qual; a.qmaskbuf = L.d_qmask.p; }
 #ifdef DBTK_STAMPS
-    a.dbg = reinterpret_cast<uint64_t*>(c->d_small + 32);
+    a.dbg = reinterpret_cast<uint64_t*>(L.d_small + 32);
 #endif
     const uint64_t ntiles = (npairs + K1_TP - 1) / K1_TP;
     int e = 0;
@@ -1387,7 +1426,7 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
     // first sampled k-mer in hand, body_surv_key would look it up again — 12 M requests per 10 M all-hit reads.  Its one-sample-per-turn
     // form only: NM = 1 with the presence filter, the default.)
     const bool k1_keys = sort_hint && c->P.n_filter && c->P.nm_filter == 1 && c->T.flt && !getenv("DBTK_NO_K1_KEYS");
-    a.skey = k1_keys ? c->d_surv + 2 * (npairs + 1) : nullptr;  // (= SurvSortArgs::key below)
+    a.skey = k1_keys ? L.d_surv.p + 2 * (npairs + 1) : nullptr;  // (= SurvSortArgs::key below)
     bool k1_lazy = false;
     {   // (lazy sampling when more than half of the batch before passed subfilter — a hint like the others; DBTK_K1_LAZY=0 / 1: never / always)
         static const int lazy_env = getenv("DBTK_K1_LAZY") ? atoi(getenv("DBTK_K1_LAZY")) : -1;
@@ -1403,29 +1442,58 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
     if (sort_hint) {
         SurvSortArgs sa;
         memset(&sa, 0, sizeof(sa));
-        sa.T = c->T; sa.P = c->P; sa.seq = d_seq; sa.off = d_off; sa.surv = c->d_surv; sa.nsurv = c->d_small + 0;
-        sa.sorted = c->d_surv + (npairs + 1); sa.key = sa.sorted + (npairs + 1); sa.hist = sa.key + (npairs + 1); sa.flag = c->d_small + 6;
+        sa.T = c->T; sa.P = c->P; sa.seq = d_seq; sa.off = d_off; sa.surv = L.d_surv.p; sa.nsurv = L.d_small + 0;
+        sa.sorted = L.d_surv.p + (npairs + 1); sa.key = sa.sorted + (npairs + 1); sa.hist = sa.key + (npairs + 1); sa.flag = L.d_small + 6;
         sa.sort_min = c->h_sortflag ? SORT_MIN_PER_LOCUS : 0u;  // (no hint word = DBTK_LOCUS_ALWAYS: every batch sorted, every batch through the locus path)
         sa.have_keys = a.skey ? 1u : 0u;
         // (two arrays that live only between these kernels, in regions the locus lists take over afterwards: the items' and the rest list's)
-        sa.starts = c->d_surv + surv_words; sa.rank = c->d_surv + surv_words + 3 * 4 * item_cap;
+        sa.starts = L.d_surv.p + surv_words; sa.rank = L.d_surv.p + surv_words + 3 * 4 * item_cap;
         HIPCHK(hipMemsetAsync(sa.hist, 0, (nloci + 2) * sizeof(uint32_t), s));
-        const uint32_t gs = (uint32_t)std::min<uint64_t>((npairs + 255) / 256, (uint64_t)c->num_cu * 8);
+        const uint32_t gs = grid256(c, npairs);
         if ((st = rec_beg(5))) return st;
         LAUNCH(k_surv_key, dim3(gs), dim3(256), s, sa);
         LAUNCH(k_surv_scan, dim3(SCAN_BLOCKS), dim3(64), s, sa, 0);
         LAUNCH(k_surv_scan, dim3(SCAN_BLOCKS), dim3(64), s, sa, 1);
         LAUNCH(k_surv_scatter, dim3(gs), dim3(256), s, sa);
         if ((st = rec_end(5))) return st;
-        c->d_sorted = sa.sorted;
+        L.d_sorted = sa.sorted;
         a.surv = sa.sorted;
-    } else c->d_sorted = c->d_surv;  // (the flag says "not in locus order": the encode stage cleared it)
+    } else L.d_sorted = L.d_surv.p;  // (the flag says "not in locus order": the encode stage cleared it)
+    // The item lists of a locus-resident launch (dbtk_locus.h), from the part [t0, t0 + tn) of the list in locus order: one item = one
+    // locus' next LOC_CH pairs, per class of image; the workgroups' ranges of each list; the list of the pairs no item covers.
+    struct LocLists { LocRunArgs run[3]; uint32_t* rest; uint32_t* nrest; };
+    auto loc_lists = [&](const LocusDir* dir, const uint8_t* images, uint32_t t0, uint64_t tn, int classes, const int* nblk, uint64_t* stats, bool run_rest, LocLists* out) -> dbtk_status_t {
+        LocItemArgs ia;
+        memset(&ia, 0, sizeof(ia));
+        ia.hist = L.d_surv.p + 3 * (npairs + 1); ia.nsurv = L.d_small + 0; ia.flag = L.d_small + 6; ia.dir = dir;
+        ia.nloci = (uint32_t)nloci; ia.t0 = t0; ia.tcap = (uint32_t)tn;
+        ia.cap_bytes[0] = (classes & 1) ? LOC_IMGB_XS : 0; ia.cap_bytes[1] = (classes & 2) ? LOC_IMGB_S : 0; ia.cap_bytes[2] = (classes & 4) ? LOC_IMGB_L : 0;
+        for (int q = 0; q < 3; ++q) ia.items[q] = reinterpret_cast<uint4*>(L.d_surv.p + surv_words) + q * item_cap;
+        ia.nitems = L.d_small + 8; ia.item_cap = (uint32_t)item_cap;
+        ia.rest = L.d_surv.p + surv_words + 3 * 4 * item_cap;
+        HIPCHK(hipMemsetAsync(L.d_small + 8, 0, 4 * sizeof(uint32_t), s));
+        LAUNCH(k_loc_items, dim3((uint32_t)((nloci + 255) / 256)), dim3(256), s, ia);
+        LAUNCH(k_loc_rest, dim3(grid256(c, tn)), dim3(256), s, ia);
+        LocSplitArgs sp;
+        memset(&sp, 0, sizeof(sp));
+        for (int q = 0; q < 3; ++q) {
+            sp.items[q] = ia.items[q]; sp.starts[q] = L.d_surv.p + split_at + q * ((uint64_t)split_blk + 1);
+            sp.nblk[q] = (uint32_t)nblk[q];
+            sp.wfix[q] = 4u << q;  // (an image of the class costs about as much as that many pairs)
+        }
+        sp.nitems = L.d_small + 8; sp.item_cap = (uint32_t)item_cap; sp.stats = stats;
+        LAUNCH(k_loc_split, dim3(3), dim3(1024), s, sp);
+        out->rest = ia.rest; out->nrest = L.d_small + 11;
+        for (int q = 0; q < 3; ++q) out->run[q] = LocRunArgs{dir, images, ia.items[q], L.d_small + 8 + q, run_rest ? out->rest : nullptr, run_rest ? out->nrest : nullptr, sp.starts[q]};
+        return DBTK_OK;
+    };
     // Does the locus-resident probe kernel have anything to do?  Only in a batch with many survivors per locus (list in locus order, loci
     // with LOC_MIN_PAIRS pairs and more); a WGS-like batch (one survivor per locus) would pay its empty launches for nothing (40 us on a
     // 1.2-ms step).  Which kind a batch is, is known on the device only — so the survivor count and the sort flag of the batch BEFORE
     // come back through pinned words and decide for this one.  A hint, never a matter of results: the lean kernel looks up whatever
     // the locus path does not take.
     // (the words are written by the general resolve kernel, BatchArgs::hint_out: pinned memory is the device's to write)
+    const int nsi = ns <= 2 ? 0 : (ns == 3 ? 1 : 2);  // NS = 2 | 3 | 4 slots of 64 positions
     bool lean_fused = false;
     for (uint64_t ch = 0; ch < nchunks; ++ch) {
         a.t0 = (uint32_t)(ch * tcap);
@@ -1438,52 +1506,17 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
             const int npl = !a.T.mz || a.edgebuf || a.qmaskbuf || (wn != 7 && wn != 11) ? 0 : (max_read_len <= 32 * 3 + a.T.mz_m - 1 ? 3 : max_read_len <= 32 * 5 + a.T.mz_m - 1 ? 5 : 0);
             a.sel = nullptr; a.nsel = nullptr;
             // (the general resolve kernel's list: the usual-pair kernel appends to it — and, fused, the locus-resident probe kernel)
-            a.gen_list = usual ? c->d_gen : nullptr; a.ngen = usual ? tickets + (nchunks + 1) + ch : nullptr;
+            a.gen_list = usual ? L.d_gen.p : nullptr; a.ngen = usual ? tickets + (nchunks + 1) + ch : nullptr;
             if (npl && a.T.ldir && locus_hint) {
                 // The pairs of loci that have an image: the locus-resident kernel (dbtk_locus.h), image in LDS, one item = one locus'
                 // next LOC_CH pairs of the list; the lean kernel then takes what is left (loci without an image, pairs without a
                 // locus — and everything when the batch has too few survivors per locus for the list to be in locus order).
-                LocItemArgs ia;
-                memset(&ia, 0, sizeof(ia));
-                ia.hist = c->d_surv + 3 * (npairs + 1); ia.nsurv = c->d_small + 0; ia.flag = c->d_small + 6; ia.dir = a.T.ldir;
-                ia.nloci = (uint32_t)nloci; ia.t0 = a.t0; ia.tcap = (uint32_t)tcap;
                 static const int loc_classes = [] { const char* e = getenv("DBTK_LOC_CLASSES"); return e ? atoi(e) : 7; }();  // diagnostic: bit c = class c in use
-                ia.cap_bytes[0] = (loc_classes & 1) ? LOC_IMGB_XS : 0; ia.cap_bytes[1] = (loc_classes & 2) ? LOC_IMGB_S : 0; ia.cap_bytes[2] = (loc_classes & 4) ? LOC_IMGB_L : 0;
-                for (int q = 0; q < 3; ++q) ia.items[q] = reinterpret_cast<uint4*>(c->d_surv + surv_words) + q * item_cap;
-                ia.nitems = c->d_small + 8; ia.item_cap = (uint32_t)item_cap;
-                ia.rest = c->d_surv + surv_words + 3 * 4 * item_cap;
-                HIPCHK(hipMemsetAsync(c->d_small + 8, 0, 4 * sizeof(uint32_t), s));
-                LAUNCH(k_loc_items, dim3((uint32_t)((nloci + 255) / 256)), dim3(256), s, ia);
-                LAUNCH(k_loc_rest, dim3((uint32_t)std::min<uint64_t>((tcap + 255) / 256, (uint64_t)c->num_cu * 8)), dim3(256), s, ia);
-                LocSplitArgs sp;
-                memset(&sp, 0, sizeof(sp));
-                for (int q = 0; q < 3; ++q) {
-                    sp.items[q] = ia.items[q]; sp.starts[q] = c->d_surv + split_at + q * ((uint64_t)split_blk + 1);
-                    sp.nblk[q] = (uint32_t)(fuse ? c->locf_blocks : c->loc_blocks)[(npl == 3 ? 0 : 3) + q];
-                    sp.wfix[q] = 4u << q;  // (an image of the class costs about as much as that many pairs)
-                }
-                sp.nitems = c->d_small + 8; sp.item_cap = (uint32_t)item_cap; sp.stats = c->d_pstats;
-                LAUNCH(k_loc_split, dim3(3), dim3(1024), s, sp);
-                LocRunArgs r0{a.T.ldir, a.T.limg, ia.items[0], c->d_small + 8, ia.rest, c->d_small + 11, sp.starts[0]}, r1{a.T.ldir, a.T.limg, ia.items[1], c->d_small + 9, ia.rest, c->d_small + 11, sp.starts[1]},
-                    r2{a.T.ldir, a.T.limg, ia.items[2], c->d_small + 10, ia.rest, c->d_small + 11, sp.starts[2]};
-                if (fuse && npl == 3) {
-                    LAUNCH((k_probe_locus<3, LOC_NW_XS, LOC_IMGB_XS, true>), dim3(c->locf_blocks[0]), dim3(LOC_NW_XS * 64), s, a, r0);
-                    LAUNCH((k_probe_locus<3, LOC_NW_S, LOC_IMGB_S, true>), dim3(c->locf_blocks[1]), dim3(LOC_NW_S * 64), s, a, r1);
-                    LAUNCH((k_probe_locus<3, LOC_NW_L, LOC_IMGB_L, true>), dim3(c->locf_blocks[2]), dim3(LOC_NW_L * 64), s, a, r2);
-                } else if (fuse) {
-                    LAUNCH((k_probe_locus<5, LOC_NW_XS, LOC_IMGB_XS, true>), dim3(c->locf_blocks[3]), dim3(LOC_NW_XS * 64), s, a, r0);
-                    LAUNCH((k_probe_locus<5, LOC_NW_S, LOC_IMGB_S, true>), dim3(c->locf_blocks[4]), dim3(LOC_NW_S * 64), s, a, r1);
-                    LAUNCH((k_probe_locus<5, LOC_NW_L, LOC_IMGB_L, true>), dim3(c->locf_blocks[5]), dim3(LOC_NW_L * 64), s, a, r2);
-                } else if (npl == 3) {
-                    LAUNCH((k_probe_locus<3, LOC_NW_XS, LOC_IMGB_XS>), dim3(c->loc_blocks[0]), dim3(LOC_NW_XS * 64), s, a, r0);
-                    LAUNCH((k_probe_locus<3, LOC_NW_S, LOC_IMGB_S>), dim3(c->loc_blocks[1]), dim3(LOC_NW_S * 64), s, a, r1);
-                    LAUNCH((k_probe_locus<3, LOC_NW_L, LOC_IMGB_L>), dim3(c->loc_blocks[2]), dim3(LOC_NW_L * 64), s, a, r2);
-                } else {
-                    LAUNCH((k_probe_locus<5, LOC_NW_XS, LOC_IMGB_XS>), dim3(c->loc_blocks[3]), dim3(LOC_NW_XS * 64), s, a, r0);
-                    LAUNCH((k_probe_locus<5, LOC_NW_S, LOC_IMGB_S>), dim3(c->loc_blocks[4]), dim3(LOC_NW_S * 64), s, a, r1);
-                    LAUNCH((k_probe_locus<5, LOC_NW_L, LOC_IMGB_L>), dim3(c->loc_blocks[5]), dim3(LOC_NW_L * 64), s, a, r2);
-                }
-                a.sel = ia.rest; a.nsel = c->d_small + 11;
+                const int* nblk = (fuse ? c->locf_blocks : c->loc_blocks) + (npl == 3 ? 0 : 3);
+                LocLists ll;
+                if ((st = loc_lists(a.T.ldir, a.T.limg, a.t0, tcap, loc_classes, nblk, c->d_pstats, true, &ll))) return st;
+                for (int q = 0; q < 3; ++q) LAUNCH_K(K_PROBE_LOCUS[fuse][npl == 5][q], dim3(nblk[q]), dim3(LOC_NW[q] * 64), s, a, ll.run[q]);
+                a.sel = ll.rest; a.nsel = ll.nrest;
             }
             // (a wave of the lean form works through one contiguous range of the list: as many waves as are resident at once)
             // four forms: with / without the list the locus path left (SEL), resolving the pairs its look-ups decide itself or not (FUSE)
@@ -1503,60 +1536,22 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
                     wpc = (int)(resident * std::min<uint64_t>(8, std::max<uint64_t>(1, ((uint64_t)surv_hint + per_round - 1) / per_round)));
                 }
                 const dim3 g2((uint32_t)c->num_cu * (uint32_t)wpc);
-#define DBTK_P2_LAUNCH(NPL_, WN_) \
-                do { if (a.sel && lean_fused) LAUNCH((k_probe<NPL_, WN_, true, true>), g2, dim3(64), s, a); \
-                     else if (a.sel) LAUNCH((k_probe<NPL_, WN_, true, false>), g2, dim3(64), s, a); \
-                     else if (lean_fused) LAUNCH((k_probe<NPL_, WN_, false, true>), g2, dim3(64), s, a); \
-                     else LAUNCH((k_probe<NPL_, WN_, false, false>), g2, dim3(64), s, a); } while (0)
-                if (vi == 0) DBTK_P2_LAUNCH(3, 7); else if (vi == 1) DBTK_P2_LAUNCH(3, 11); else if (vi == 2) DBTK_P2_LAUNCH(5, 7); else DBTK_P2_LAUNCH(5, 11);
-#undef DBTK_P2_LAUNCH
+                LAUNCH_K(K_PROBE[vi][a.sel != nullptr][lean_fused], g2, dim3(64), s, a);
             }
-            else if (ns <= 2) LAUNCH((k_probe_general<2>), gpr, dim3(64), s, a);
-            else if (ns == 3) LAUNCH((k_probe_general<3>), gpr, dim3(64), s, a);
-            else LAUNCH((k_probe_general<4>), gpr, dim3(64), s, a);
+            else LAUNCH_K(K_PROBE_GENERAL[nsi], gpr, dim3(64), s, a);
         }
         if (tm) HIPCHK(hipEventRecord(c->timed[1].end[e], s));
-        // RECS = false: no record buffer (-ka without -e): record emission is compiled out
-        const int nsi = ns <= 2 ? 0 : (ns == 3 ? 1 : 2);
         if (usual && !lean_fused) {  // (the fused lean probe kernel has resolved what this kernel would, and filled the general kernel's list)
             const dim3 gu(c->usual_blocks[nsi]);
             if (tm) { if ((st = timed_slot(c, 2, &e))) return st; HIPCHK(hipEventRecord(c->timed[2].beg[e], s)); }
-            if (d_recs) {
-                if (nsi == 0) LAUNCH((k_pair_usual<2, true>), gu, dim3(64), s, a);
-                else if (nsi == 1) LAUNCH((k_pair_usual<3, true>), gu, dim3(64), s, a);
-                else LAUNCH((k_pair_usual<4, true>), gu, dim3(64), s, a);
-            } else if (fuse && a.sel) {  // (the locus-resident kernel has resolved its pairs itself: what is left is the list it did not take)
-                if (nsi == 0) LAUNCH((k_pair_usual<2, false, true>), gu, dim3(64), s, a);
-                else if (nsi == 1) LAUNCH((k_pair_usual<3, false, true>), gu, dim3(64), s, a);
-                else LAUNCH((k_pair_usual<4, false, true>), gu, dim3(64), s, a);
-            } else {
-                if (nsi == 0) LAUNCH((k_pair_usual<2, false>), gu, dim3(64), s, a);
-                else if (nsi == 1) LAUNCH((k_pair_usual<3, false>), gu, dim3(64), s, a);
-                else LAUNCH((k_pair_usual<4, false>), gu, dim3(64), s, a);
-            }
+            // (RECS: no record buffer (-ka without -e) and record emission is compiled out; SEL: the fused locus-resident kernel has resolved
+            // its pairs itself, what is left is the list it did not take)
+            LAUNCH_K(K_PAIR_USUAL[d_recs ? USUAL_RECS : fuse && a.sel ? USUAL_SEL : USUAL_PLAIN][nsi], gu, dim3(64), s, a);
             if (tm) HIPCHK(hipEventRecord(c->timed[2].end[e], s));
         }
         if (tm) { if ((st = timed_slot(c, 3, &e))) return st; HIPCHK(hipEventRecord(c->timed[3].beg[e], s)); }
         const dim3 gp(c->pair_blocks[nsi]);
-        if (bub_table) {
-            if (d_recs) {
-                if (nsi == 0) LAUNCH((k_pair_bub<2, true>), gp, dim3(64), s, a);
-                else if (nsi == 1) LAUNCH((k_pair_bub<3, true>), gp, dim3(64), s, a);
-                else LAUNCH((k_pair_bub<4, true>), gp, dim3(64), s, a);
-            } else {
-                if (nsi == 0) LAUNCH((k_pair_bub<2, false>), gp, dim3(64), s, a);
-                else if (nsi == 1) LAUNCH((k_pair_bub<3, false>), gp, dim3(64), s, a);
-                else LAUNCH((k_pair_bub<4, false>), gp, dim3(64), s, a);
-            }
-        } else if (d_recs) {
-            if (nsi == 0) LAUNCH((k_pair<2, true>), gp, dim3(64), s, a);
-            else if (nsi == 1) LAUNCH((k_pair<3, true>), gp, dim3(64), s, a);
-            else LAUNCH((k_pair<4, true>), gp, dim3(64), s, a);
-        } else {
-            if (nsi == 0) LAUNCH((k_pair<2, false>), gp, dim3(64), s, a);
-            else if (nsi == 1) LAUNCH((k_pair<3, false>), gp, dim3(64), s, a);
-            else LAUNCH((k_pair<4, false>), gp, dim3(64), s, a);
-        }
+        LAUNCH_K((bub_table ? K_PAIR_BUB : K_PAIR)[d_recs != nullptr][nsi], gp, dim3(64), s, a);
         if (tm) HIPCHK(hipEventRecord(c->timed[3].end[e], s));
     }
     if (bub_table) LAUNCH(k_bub_publish, dim3(1), dim3(64), s, c->d_nevents, c->h_bub);
@@ -1564,18 +1559,18 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
         WalkArgs w;
         memset(&w, 0, sizeof(w));
         w.T = c->T; w.P = c->P; w.P.aln &= 3u; w.seq = d_seq; w.off = d_off;
-        w.surv = c->d_sorted; w.nsurv = c->d_small + 0;
-        w.walk_dst = c->d_walk; w.walk_ret = c->d_walk + npairs;
+        w.surv = L.d_sorted; w.nsurv = L.d_small + 0;
+        w.walk_dst = L.d_walk.p; w.walk_ret = L.d_walk.p + npairs;
         w.counts = a.counts; w.counters = a.counters; w.ctr_rep = c->d_ctr; w.pstats = c->d_pstats;
-        w.trecs = walk_trecs; w.errflag = c->d_small + 3;
+        w.trecs = walk_trecs; w.errflag = L.d_small + 3;
 #ifdef DBTK_STAMPS
-        w.dbg = reinterpret_cast<uint64_t*>(c->d_small + 32);
+        w.dbg = reinterpret_cast<uint64_t*>(L.d_small + 32);
 #endif
         if (walk_txt) {  // text records: an arena sized for the worst case (two characters per entry, four strings), carved by the waves
             const uint32_t acap = std::min<uint32_t>(DBTK_THREAD_CAP, (max_read_len + max_read_len / 4 + 8 + 7) & ~7u);
             c->aln_cap = acap;
             uint64_t wfl_waves = 0;
-            for (int q = 0; q < 3; ++q) wfl_waves += (uint64_t)std::max(c->wfl_blocks[q], c->wfl_blocks[3 + q]) * (q == 0 ? LOC_NW_XS : q == 1 ? LOC_NW_S : LOC_NW_L);
+            for (int q = 0; q < 3; ++q) wfl_waves += (uint64_t)std::max(c->wfl_blocks[q], c->wfl_blocks[3 + q]) * LOC_NW[q];
             const uint64_t want = std::min<uint64_t>(npairs * (uint64_t)(8 + 8 * acap + 8) + (uint64_t)TXT_CHUNK * (c->walk_blocks + c->walkfast_blocks + wfl_waves + 2), TXT_ARENA_MAX);  // (a chunk per wave that writes: every wave of the walk kernels' launches)
             if (want > c->txt_bytes) {
                 if (c->d_txt) HIPCHK(hipFree(c->d_txt));
@@ -1583,11 +1578,11 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
                 HIPCHK(hipMalloc(&c->d_txt, want));
                 c->txt_bytes = want;
             }
-            if ((st = ensure(&c->d_txtidx, &c->txtidx_cap, npairs))) return st;
-            HIPCHK(hipMemsetAsync(c->d_txtidx, 0xFF, npairs * sizeof(uint32_t), s));
-            HIPCHK(hipMemsetAsync(c->d_small + 7, 0, 4, s));
+            if ((st = c->d_txtidx.ensure(npairs))) return st;
+            HIPCHK(hipMemsetAsync(c->d_txtidx.p, 0xFF, npairs * sizeof(uint32_t), s));
+            HIPCHK(hipMemsetAsync(L.d_small + 7, 0, 4, s));
             c->txt_cap = want;
-            w.txt = c->d_txt; w.txt_idx = c->d_txtidx; w.ntxt = c->d_small + 7; w.txt_cap = (uint32_t)want; w.aln_cap = acap;
+            w.txt = c->d_txt; w.txt_idx = c->d_txtidx.p; w.ntxt = L.d_small + 7; w.txt_cap = (uint32_t)want; w.aln_cap = acap;
         }
         if (walk_aln) {
             // a record holds, per mate, cg.es and cg.tr: the read's bases plus what deletions can add (dbtk.h: DBTK_THREAD_CAP)
@@ -1601,9 +1596,9 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
                 HIPCHK(hipMalloc(&c->d_aln, c->aln_max * c->aln_stride));
                 c->aln_bytes = c->aln_max * c->aln_stride;
             }
-            HIPCHK(hipMemsetAsync(c->d_small + 4, 0, 4, s));
+            HIPCHK(hipMemsetAsync(L.d_small + 4, 0, 4, s));
             w.aln = c->d_aln; w.aln_stride = c->aln_stride; w.aln_cap = acap; w.aln_max = (uint32_t)std::min<uint64_t>(c->aln_max, 0xFFFFFFFFull);
-            w.naln = c->d_small + 4;
+            w.naln = L.d_small + 4;
         }
         // Two kernels when nothing needs the alignment arrays of every mate (no array records, no thread records): the lean one
         // decides and counts the pairs one of whose mates threads cleanly — with text records (-a / -ae): the pairs BOTH of whose
@@ -1611,64 +1606,32 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
         const int wnpl = (walk_aln || walk_trecs) ? 0 : walkfast_npl(max_read_len, k, w.T.grmz != nullptr);
         if (tm) { if ((st = timed_slot(c, 4, &e))) return st; HIPCHK(hipEventRecord(c->timed[4].beg[e], s)); }
         if (wnpl) {
-            w.slow_list = c->d_walk + 2 * npairs; w.nslow = c->d_small + 5;
-            if (info_rows) { w.slow_info = c->d_walk + 2 * npairs + slow_cap; w.info_cap = (uint32_t)std::min<uint64_t>(info_rows, 0x7FFFFFFFull); w.info_stride = 32u * (uint32_t)wnpl; }
-            HIPCHK(hipMemsetAsync(c->d_small + 5, 0, 4, s));
+            w.slow_list = L.d_walk.p + 2 * npairs; w.nslow = L.d_small + 5;
+            if (info_rows) { w.slow_info = L.d_walk.p + 2 * npairs + slow_cap; w.info_cap = (uint32_t)std::min<uint64_t>(info_rows, 0x7FFFFFFFull); w.info_stride = 32u * (uint32_t)wnpl; }
+            HIPCHK(hipMemsetAsync(L.d_small + 5, 0, 4, s));
             // (four ranges per resident wave even out their different costs: 19.7 -> 18.7 ms per 4 M reads; not with text records, where
             // every block that writes takes a chunk of the arena)
             if (w.T.gldir && locus_hint) {
                 // the pairs of loci with a graph image: the lean kernel's locus-resident form (dbtk_walkfast.h), over the whole list;
                 // the plain form then takes what is left
-                LocItemArgs ia;
-                memset(&ia, 0, sizeof(ia));
-                ia.hist = c->d_surv + 3 * (npairs + 1); ia.nsurv = c->d_small + 0; ia.flag = c->d_small + 6; ia.dir = w.T.gldir;
-                ia.nloci = (uint32_t)nloci; ia.t0 = 0; ia.tcap = (uint32_t)npairs;
-                ia.cap_bytes[0] = LOC_IMGB_XS; ia.cap_bytes[1] = LOC_IMGB_S; ia.cap_bytes[2] = LOC_IMGB_L;
-                for (int q = 0; q < 3; ++q) ia.items[q] = reinterpret_cast<uint4*>(c->d_surv + surv_words) + q * item_cap;
-                ia.nitems = c->d_small + 8; ia.item_cap = (uint32_t)item_cap;
-                ia.rest = c->d_surv + surv_words + 3 * 4 * item_cap;
-                HIPCHK(hipMemsetAsync(c->d_small + 8, 0, 4 * sizeof(uint32_t), s));
-                LAUNCH(k_loc_items, dim3((uint32_t)((nloci + 255) / 256)), dim3(256), s, ia);
-                LAUNCH(k_loc_rest, dim3((uint32_t)std::min<uint64_t>((npairs + 255) / 256, (uint64_t)c->num_cu * 8)), dim3(256), s, ia);
-                LocSplitArgs sp;
-                memset(&sp, 0, sizeof(sp));
-                for (int q = 0; q < 3; ++q) {
-                    sp.items[q] = ia.items[q]; sp.starts[q] = c->d_surv + split_at + q * ((uint64_t)split_blk + 1);
-                    sp.nblk[q] = (uint32_t)c->wfl_blocks[(wnpl == 3 ? 0 : 3) + q];
-                    sp.wfix[q] = 4u << q;
-                }
-                sp.nitems = c->d_small + 8; sp.item_cap = (uint32_t)item_cap; sp.stats = c->d_pstats + 7;
-                LAUNCH(k_loc_split, dim3(3), dim3(1024), s, sp);
-                LocRunArgs r0{w.T.gldir, w.T.glimg, ia.items[0], c->d_small + 8, nullptr, nullptr, sp.starts[0]}, r1{w.T.gldir, w.T.glimg, ia.items[1], c->d_small + 9, nullptr, nullptr, sp.starts[1]},
-                    r2{w.T.gldir, w.T.glimg, ia.items[2], c->d_small + 10, nullptr, nullptr, sp.starts[2]};
+                const int* nblk = c->wfl_blocks + (wnpl == 3 ? 0 : 3);
+                LocLists ll;
+                if ((st = loc_lists(w.T.gldir, w.T.glimg, 0, npairs, 7, nblk, c->d_pstats + 7, false, &ll))) return st;
                 // (DBTK_WALK_LOCUS_EC=1: the pairs these cannot decide stay with their locus — marked in walk_ret, walked by k_walk_pairs_locus
                 // over the same items with the error correction's graph look-ups answered from LDS.  Built and bit-exact in round 5, and
                 // MEASURED SLOWER than the global-table kernel (walk kernels 23.0 against 16.2 ms per 10 M reads: DESIGN 4.2) — the walk is not
                 // bound by its look-ups' round trips — so it is off unless asked for; the pairs go on the other kernel's list)
                 static const bool locus_ec = [] { const char* e = getenv("DBTK_WALK_LOCUS_EC"); return e && atoi(e) != 0; }();
                 w.pend_locus = locus_ec ? 1u : 0u;
-                const int wq = wnpl == 3 ? 0 : 3;
-                if (wnpl == 3) {
-                    LAUNCH((k_walk_fast_locus<3, LOC_NW_XS, LOC_IMGB_XS>), dim3(c->wfl_blocks[0]), dim3(LOC_NW_XS * 64), s, w, r0);
-                    LAUNCH((k_walk_fast_locus<3, LOC_NW_S, LOC_IMGB_S>), dim3(c->wfl_blocks[1]), dim3(LOC_NW_S * 64), s, w, r1);
-                    LAUNCH((k_walk_fast_locus<3, LOC_NW_L, LOC_IMGB_L>), dim3(c->wfl_blocks[2]), dim3(LOC_NW_L * 64), s, w, r2);
-                } else {
-                    LAUNCH((k_walk_fast_locus<5, LOC_NW_XS, LOC_IMGB_XS>), dim3(c->wfl_blocks[3]), dim3(LOC_NW_XS * 64), s, w, r0);
-                    LAUNCH((k_walk_fast_locus<5, LOC_NW_S, LOC_IMGB_S>), dim3(c->wfl_blocks[4]), dim3(LOC_NW_S * 64), s, w, r1);
-                    LAUNCH((k_walk_fast_locus<5, LOC_NW_L, LOC_IMGB_L>), dim3(c->wfl_blocks[5]), dim3(LOC_NW_L * 64), s, w, r2);
-                }
-                if (locus_ec) {  // (the same grids: the workgroups' ranges of the item lists are the ones k_loc_split made for those launches)
-                    LAUNCH((k_walk_pairs_locus<LOC_IMGB_XS>), dim3(c->wfl_blocks[wq + 0]), dim3(WPL_NW * 64), s, w, r0);
-                    LAUNCH((k_walk_pairs_locus<LOC_IMGB_S>), dim3(c->wfl_blocks[wq + 1]), dim3(WPL_NW * 64), s, w, r1);
-                    LAUNCH((k_walk_pairs_locus<LOC_IMGB_L>), dim3(c->wfl_blocks[wq + 2]), dim3(WPL_NW * 64), s, w, r2);
-                }
+                for (int q = 0; q < 3; ++q) LAUNCH_K(K_WALK_FAST_LOCUS[wnpl == 5][q], dim3(nblk[q]), dim3(LOC_NW[q] * 64), s, w, ll.run[q]);
+                if (locus_ec)  // (the same grids: the workgroups' ranges of the item lists are the ones k_loc_split made for those launches)
+                    for (int q = 0; q < 3; ++q) LAUNCH_K(K_WALK_PAIRS_LOCUS[q], dim3(nblk[q]), dim3(WPL_NW * 64), s, w, ll.run[q]);
                 w.pend_locus = 0;
-                w.sel = ia.rest; w.nsel = c->d_small + 11;
+                w.sel = ll.rest; w.nsel = ll.nrest;
             }
             const dim3 gf(walk_txt ? c->walkfast_blocks : 4 * c->walkfast_blocks);
             const bool w11 = w.T.grmz && k - mz_m_for_k(k) + 1 == 11;  // (windows of 7 m-mers for k = 19 .. 22, of 11 for k = 23 .. 26)
-            if (wnpl == 3) { if (w11) LAUNCH((k_walk_fast<3, 11>), gf, dim3(64), s, w); else LAUNCH((k_walk_fast<3, 7>), gf, dim3(64), s, w); }
-            else { if (w11) LAUNCH((k_walk_fast<5, 11>), gf, dim3(64), s, w); else LAUNCH((k_walk_fast<5, 7>), gf, dim3(64), s, w); }
+            LAUNCH_K(K_WALK_FAST[wnpl == 5][w11], gf, dim3(64), s, w);
         }
         LAUNCH(k_walk_pairs, dim3(c->walk_blocks), dim3(64), s, w);
         if (tm) HIPCHK(hipEventRecord(c->timed[4].end[e], s));
@@ -1750,66 +1713,43 @@ static dbtk_status_t dbtk_ctx_create_impl(const dbtk_rpgg_t* h, const dbtk_param
         c->k1_blocks = c->num_cu * nb;
         if (const char* ev = getenv("DBTK_PROBE_WPC")) { const int v = atoi(ev); if (v > 0) c->probe_wpc = v; }  // probe waves per CU
         {
-            const void* k2[4] = {(const void*)k_probe<3, 7>, (const void*)k_probe<3, 11>, (const void*)k_probe<5, 7>, (const void*)k_probe<5, 11>};
-            for (int i = 0; i < 4; ++i) {
-                nb = 0;
-                // blocks per CU: eight times what the occupancy query says is resident.  A wave works through one contiguous range of
-                // the locus-ordered list, so ranges an eighth as long even out their different costs (5.42 -> 5.09 ms per all-hit launch);
-                // and a grid of EXACTLY the resident waves is a cliff: the query counts LDS in finer granules than the hardware
-                // allocates, and one block too many per CU runs alone in a second round at twice the time (measured with a 10.7-KB variant
-                // of this kernel: 15 per CU by the query, 14 in fact: 8.7 ms against 6.1).
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k2[i], 64, 0) != hipSuccess || nb <= 0) nb = 8;
-                nb *= 8;
-                if (const char* ev = getenv("DBTK_PROBE_WPC")) { const int v = atoi(ev); if (v > 0) nb = v; }
-                c->probe2_wpc[i] = nb;
-            }
-            const void* k2f[4] = {(const void*)k_probe<3, 7, false, true>, (const void*)k_probe<3, 11, false, true>, (const void*)k_probe<5, 7, false, true>, (const void*)k_probe<5, 11, false, true>};
-            for (int i = 0; i < 4; ++i) {  // (the fused forms: their own register count)
-                nb = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k2f[i], 64, 0) != hipSuccess || nb <= 0) nb = 8;
-                nb *= 8;
-                if (const char* ev = getenv("DBTK_PROBE_WPC")) { const int v = atoi(ev); if (v > 0) nb = v; }
-                c->probe2f_wpc[i] = nb;
-            }
+            for (int f = 0; f < 2; ++f)  // (the fused forms: their own register count)
+                for (int i = 0; i < 4; ++i) {
+                    nb = 0;
+                    // blocks per CU: eight times what the occupancy query says is resident.  A wave works through one contiguous range of
+                    // the locus-ordered list, so ranges an eighth as long even out their different costs (5.42 -> 5.09 ms per all-hit launch);
+                    // and a grid of EXACTLY the resident waves is a cliff: the query counts LDS in finer granules than the hardware
+                    // allocates, and one block too many per CU runs alone in a second round at twice the time (measured with a 10.7-KB variant
+                    // of this kernel: 15 per CU by the query, 14 in fact: 8.7 ms against 6.1).
+                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, K_PROBE[i][0][f].fn, 64, 0) != hipSuccess || nb <= 0) nb = 8;
+                    nb *= 8;
+                    if (const char* ev = getenv("DBTK_PROBE_WPC")) { const int v = atoi(ev); if (v > 0) nb = v; }
+                    (f ? c->probe2f_wpc : c->probe2_wpc)[i] = nb;
+                }
             if (getenv("DBTK_VERBOSE")) fprintf(stderr, "k_probe<5, 7>: %d blocks per CU\n", c->probe2_wpc[2]);
-            {   // the locus-resident kernel: as many workgroups as are resident (an item is short: the workgroups take them round robin)
-                const void* kl[6] = {(const void*)k_probe_locus<3, LOC_NW_XS, LOC_IMGB_XS>, (const void*)k_probe_locus<3, LOC_NW_S, LOC_IMGB_S>, (const void*)k_probe_locus<3, LOC_NW_L, LOC_IMGB_L>,
-                                     (const void*)k_probe_locus<5, LOC_NW_XS, LOC_IMGB_XS>, (const void*)k_probe_locus<5, LOC_NW_S, LOC_IMGB_S>, (const void*)k_probe_locus<5, LOC_NW_L, LOC_IMGB_L>};
-                const int nwv[3] = {LOC_NW_XS, LOC_NW_S, LOC_NW_L};
+            // the locus-resident kernel: as many workgroups as are resident (an item is short: the workgroups take them round robin)
+            for (int f = 0; f < 2; ++f)
                 for (int i = 0; i < 6; ++i) {
                     nb = 0;
-                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kl[i], nwv[i % 3] * 64, 0) != hipSuccess || nb <= 0) nb = 1;
+                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, K_PROBE_LOCUS[f][i / 3][i % 3].fn, LOC_NW[i % 3] * 64, 0) != hipSuccess || nb <= 0) nb = 1;
                     nb *= 2;  // (twice as many as are resident: each takes a contiguous, weight-balanced range of the items, k_loc_split, and the ones that start late even out what the weights do not see)
                     if (const char* ev = getenv("DBTK_LOC_BPC")) { const int v = atoi(ev); if (v > 0) nb = v; }
-                    c->loc_blocks[i] = c->num_cu * nb;
-                    if (getenv("DBTK_VERBOSE")) fprintf(stderr, "k_probe_locus[%d]: %d workgroups per CU\n", i, nb);
+                    (f ? c->locf_blocks : c->loc_blocks)[i] = c->num_cu * nb;
+                    if (getenv("DBTK_VERBOSE")) fprintf(stderr, "k_probe_locus[%d]%s: %d workgroups per CU\n", i, f ? " (fused)" : "", nb);
                 }
-                const void* kf[6] = {(const void*)k_probe_locus<3, LOC_NW_XS, LOC_IMGB_XS, true>, (const void*)k_probe_locus<3, LOC_NW_S, LOC_IMGB_S, true>, (const void*)k_probe_locus<3, LOC_NW_L, LOC_IMGB_L, true>,
-                                     (const void*)k_probe_locus<5, LOC_NW_XS, LOC_IMGB_XS, true>, (const void*)k_probe_locus<5, LOC_NW_S, LOC_IMGB_S, true>, (const void*)k_probe_locus<5, LOC_NW_L, LOC_IMGB_L, true>};
-                for (int i = 0; i < 6; ++i) {
-                    nb = 0;
-                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kf[i], nwv[i % 3] * 64, 0) != hipSuccess || nb <= 0) nb = 1;
-                    nb *= 2;
-                    if (const char* ev = getenv("DBTK_LOC_BPC")) { const int v = atoi(ev); if (v > 0) nb = v; }
-                    c->locf_blocks[i] = c->num_cu * nb;
-                    if (getenv("DBTK_VERBOSE")) fprintf(stderr, "k_probe_locus[%d] (fused): %d workgroups per CU\n", i, nb);
-                }
-            }
         }
         // resident waves of each resolve-kernel instance (one vote-spill scratch row per resident wave)
-        const void* kp[3] = {(const void*)k_pair<2, true>, (const void*)k_pair<3, true>, (const void*)k_pair<4, true>};
         for (int i = 0; i < 3; ++i) {
             nb = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kp[i], 64, 0) != hipSuccess || nb <= 0) nb = 8;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, K_PAIR[1][i].fn, 64, 0) != hipSuccess || nb <= 0) nb = 8;
             if (const char* e = getenv("DBTK_PAIR_WPC")) { const int v = atoi(e); if (v > 0) nb = v; }  // diagnostic: blocks per CU (the vote scratch follows)
             if (getenv("DBTK_VERBOSE")) fprintf(stderr, "k_pair<%d>: %d waves per CU\n", i + 2, nb);
             c->vote_rows = std::max(c->vote_rows, c->num_cu * nb);
             if (!getenv("DBTK_PAIR_WPC")) nb *= 4;  // (ranges a quarter as long, as for the other range kernels: 0.179 -> 0.147 ms in the headline)
             c->pair_blocks[i] = c->num_cu * nb;
             c->max_pair_blocks = std::max(c->max_pair_blocks, c->pair_blocks[i]);
-            const void* ku[3] = {(const void*)k_pair_usual<2, true>, (const void*)k_pair_usual<3, true>, (const void*)k_pair_usual<4, true>};
             nb = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ku[i], 64, 0) != hipSuccess || nb <= 0) nb = 16;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, K_PAIR_USUAL[USUAL_RECS][i].fn, 64, 0) != hipSuccess || nb <= 0) nb = 16;
             nb *= 4;  // (ranges a quarter as long, as for the probe kernel: 2.66 -> 1.93 ms per all-hit launch; eight times: 1.78, but the
                       // genome-like mix, where most survivors leave at once, then pays for the blocks' own start-up: 0.26 -> 0.40 ms)
             if (const char* e = getenv("DBTK_USUAL_WPC")) { const int v = atoi(e); if (v > 0) nb = v; }  // diagnostic: blocks per CU
@@ -1818,7 +1758,21 @@ static dbtk_status_t dbtk_ctx_create_impl(const dbtk_rpgg_t* h, const dbtk_param
     }
     dbtk_status_t st = DBTK_OK;
     do {
-        if (hipStreamCreate(&c->stream) != hipSuccess) { set_error("hipStreamCreate failed"); st = DBTK_ERR_HIP; break; }
+        // the lanes (one with the event log of -bu, params.bubbles = 1: it is replayed batch by batch on the host; one in the stamps build)
+        int nlanes = 1;
+#ifndef DBTK_STAMPS
+        {   // DBTK_LANES=1..3 (default 2; a third lane gains another 2 %, a fourth fell apart: 25 ms/step)
+            const char* e = getenv("DBTK_LANES");
+            nlanes = (e && atoi(e) >= 1 && atoi(e) <= 3) ? atoi(e) : 2;
+            if (p->bubbles == 1) nlanes = 1;  // (the device table takes inserts from every lane: atomics)
+        }
+#endif
+        c->lanes.reserve(nlanes);
+        for (int li = 0; li < nlanes && !st; ++li) {
+            c->lanes.emplace_back();
+            st = lane_create(c, c->lanes.back());
+        }
+        if (st) break;
         c->timed[0].name = "k_encode_subfilter";
         c->timed[1].name = "k_probe";
         c->timed[2].name = "k_pair_usual";
@@ -1831,14 +1785,11 @@ static dbtk_status_t dbtk_ctx_create_impl(const dbtk_rpgg_t* h, const dbtk_param
             if (const char* e = getenv("DBTK_WALK_WPC")) { const int v = atoi(e); if (v > 0) nb = v; }
             c->walk_blocks = c->num_cu * nb;
             nb = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_walk_fast<5, 7>, 64, 0) != hipSuccess || nb <= 0) nb = 16;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, K_WALK_FAST[1][0].fn, 64, 0) != hipSuccess || nb <= 0) nb = 16;
             c->walkfast_blocks = c->num_cu * nb;
-            const void* kw[6] = {(const void*)k_walk_fast_locus<3, LOC_NW_XS, LOC_IMGB_XS>, (const void*)k_walk_fast_locus<3, LOC_NW_S, LOC_IMGB_S>, (const void*)k_walk_fast_locus<3, LOC_NW_L, LOC_IMGB_L>,
-                                 (const void*)k_walk_fast_locus<5, LOC_NW_XS, LOC_IMGB_XS>, (const void*)k_walk_fast_locus<5, LOC_NW_S, LOC_IMGB_S>, (const void*)k_walk_fast_locus<5, LOC_NW_L, LOC_IMGB_L>};
-            const int nwv[3] = {LOC_NW_XS, LOC_NW_S, LOC_NW_L};
             for (int i = 0; i < 6; ++i) {
                 nb = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kw[i], nwv[i % 3] * 64, 0) != hipSuccess || nb <= 0) nb = 1;
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, K_WALK_FAST_LOCUS[i / 3][i % 3].fn, LOC_NW[i % 3] * 64, 0) != hipSuccess || nb <= 0) nb = 1;
                 nb *= 2;  // (as for k_probe_locus: contiguous weight-balanced ranges, twice the resident workgroups)
                 if (const char* ev = getenv("DBTK_WFL_BPC")) { const int v = atoi(ev); if (v > 0) nb = v; }
                 c->wfl_blocks[i] = c->num_cu * nb;
@@ -1861,13 +1812,13 @@ static dbtk_status_t dbtk_ctx_create_impl(const dbtk_rpgg_t* h, const dbtk_param
         if (p->bubbles) {
             c->bubbleDB.resize(h->nloci);
             if (hipMalloc(&c->d_nevents, 4 * BUB_WORDS) != hipSuccess) { set_error("hipMalloc nevents"); st = DBTK_ERR_HIP; break; }
-            if (hipMemsetAsync(c->d_nevents, 0, 4 * BUB_WORDS, c->stream) != hipSuccess) { set_error("memset nevents"); st = DBTK_ERR_HIP; break; }
+            if (hipMemsetAsync(c->d_nevents, 0, 4 * BUB_WORDS, c->lane().stream) != hipSuccess) { set_error("memset nevents"); st = DBTK_ERR_HIP; break; }
         }
         if (p->bubbles == DBTK_BUBBLES_TABLE) {  // the table, its spill log (fixed size) and the host's pinned words
             if ((st = bub_new_table(c, bub_slots0, &c->d_bub))) break;
             c->bub_slots = bub_slots0;
-            if (hipMalloc(&c->d_events, BUB_SPILL_CAP * sizeof(BubEvent)) != hipSuccess) { (void)hipGetLastError(); set_error("bubble table: no device memory for the spill log"); st = DBTK_ERR_NOMEM; break; }
-            c->events_cap = BUB_SPILL_CAP;
+            if (hipMalloc(&c->d_events.p, BUB_SPILL_CAP * sizeof(BubEvent)) != hipSuccess) { (void)hipGetLastError(); set_error("bubble table: no device memory for the spill log"); st = DBTK_ERR_NOMEM; break; }
+            c->d_events.cap = BUB_SPILL_CAP;
             if (hipHostMalloc((void**)&c->h_bub, 64, hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc"); st = DBTK_ERR_HIP; break; }
             memset(c->h_bub, 0, 64);
         }
@@ -1876,45 +1827,15 @@ static dbtk_status_t dbtk_ctx_create_impl(const dbtk_rpgg_t* h, const dbtk_param
         auto chk = [&](hipError_t e, const char* what) { if (e != hipSuccess && !st) { set_error(std::string(what) + ": " + hipGetErrorString(e)); st = DBTK_ERR_HIP; } };
         chk(hipMalloc(&c->d_accum, c->n_accum * 8), "hipMalloc accum");
         chk(hipMalloc(&c->d_ctr, (size_t)CTR_REP * CTR_STRIDE * 8), "hipMalloc counter replicas");
-        if (!st) chk(hipMemsetAsync(c->d_ctr, 0, (size_t)CTR_REP * CTR_STRIDE * 8, c->stream), "memset");
+        if (!st) chk(hipMemsetAsync(c->d_ctr, 0, (size_t)CTR_REP * CTR_STRIDE * 8, c->lane().stream), "memset");
         chk(hipMalloc(&c->d_pstats, DBTK_PATH_STATS * 8), "hipMalloc path statistics");
-        if (!st) chk(hipMemsetAsync(c->d_pstats, 0, DBTK_PATH_STATS * 8, c->stream), "memset");
-        chk(hipMalloc(&c->d_small, 4 * (TK_INLINE + SMALL_WORDS) + 48 * 8), "hipMalloc small");
-        if (c->d_small) c->d_small += TK_INLINE;
+        if (!st) chk(hipMemsetAsync(c->d_pstats, 0, DBTK_PATH_STATS * 8, c->lane().stream), "memset");
         if (!getenv("DBTK_LOCUS_ALWAYS")) {  // (DBTK_LOCUS_ALWAYS=1: every batch launches the locus path: tests of small batches)
             chk(hipHostMalloc((void**)&c->h_sortflag, 64, hipHostMallocDefault), "hipHostMalloc");
             if (c->h_sortflag) { c->h_sortflag[0] = 0xFFFFFFFFu; c->h_sortflag[1] = 0xFFFFFFFFu; c->h_sortflag[6] = 1u; }
         }
-        if (!st) chk(hipMemsetAsync(c->d_small - TK_INLINE, 0, 4 * (TK_INLINE + SMALL_WORDS) + 48 * 8, c->stream), "memset");
-        chk(hipMalloc(&c->d_vote, (size_t)c->vote_rows * (h->nloci + 1) * 8), "hipMalloc vote scratch");
-        chk(hipMalloc(&c->d_epoch, (size_t)c->vote_rows * 16), "hipMalloc epoch");
         if (st) break;
-        chk(hipMemsetAsync(c->d_accum, 0, c->n_accum * 8, c->stream), "memset");
-        chk(hipMemsetAsync(c->d_vote, 0, (size_t)c->vote_rows * (h->nloci + 1) * 8, c->stream), "memset");
-        chk(hipMemsetAsync(c->d_epoch, 0, (size_t)c->vote_rows * 16, c->stream), "memset");
-        // further lanes (not with the event log of -bu, params.bubbles = 1: it is replayed batch by batch on the host; not in the stamps build)
-        int nlanes = 1;
-#ifndef DBTK_STAMPS
-        {   // DBTK_LANES=1..3 (default 2; a third lane gains another 2 %, a fourth fell apart: 25 ms/step)
-            const char* e = getenv("DBTK_LANES");
-            nlanes = (e && atoi(e) >= 1 && atoi(e) <= 3) ? atoi(e) : 2;
-            if (p->bubbles == 1) nlanes = 1;  // (the device table takes inserts from every lane: atomics)
-            c->two_lanes = nlanes > 1;
-        }
-#endif
-        for (int li = 1; li < nlanes; ++li) {
-            dbtk_ctx::Lane l;
-            chk(hipStreamCreate(&l.stream), "hipStreamCreate");
-            chk(hipMalloc(&l.d_small, 4 * (TK_INLINE + SMALL_WORDS) + 48 * 8), "hipMalloc small");
-            if (l.d_small) l.d_small += TK_INLINE;
-            chk(hipMalloc(&l.d_vote, (size_t)c->vote_rows * (h->nloci + 1) * 8), "hipMalloc vote scratch");
-            chk(hipMalloc(&l.d_epoch, (size_t)c->vote_rows * 16), "hipMalloc epoch");
-            if (li == 1) c->alt = l; else c->parked.push_back(l);
-            if (st) break;
-            chk(hipMemsetAsync(l.d_small - TK_INLINE, 0, 4 * (TK_INLINE + SMALL_WORDS) + 48 * 8, c->stream), "memset");
-            chk(hipMemsetAsync(l.d_vote, 0, (size_t)c->vote_rows * (h->nloci + 1) * 8, c->stream), "memset");
-            chk(hipMemsetAsync(l.d_epoch, 0, (size_t)c->vote_rows * 16, c->stream), "memset");
-        }
+        chk(hipMemsetAsync(c->d_accum, 0, c->n_accum * 8, c->lane().stream), "memset");
         if (st) break;
         {   // the tables: shared per (handle, device)
             std::lock_guard<std::mutex> lk(g_share_m);
@@ -1923,20 +1844,20 @@ static dbtk_status_t dbtk_ctx_create_impl(const dbtk_rpgg_t* h, const dbtk_param
             TableShare* sh = it != g_shares.end() ? it->second : nullptr;
             if (!sh) {  // the first context: a share of its own making, everybody's once the tables stand
                 sh = new TableShare;
-                if ((st = build_tables(TableBuild{sh, h, c->stream}))) { drop_share(sh); break; }
+                if ((st = build_tables(TableBuild{sh, h, c->lane().stream}))) { drop_share(sh); break; }
                 g_shares[key] = sh;
             }
             c->share = sh;
             ++sh->refs;
             // optional tables, by the first context that needs them (only a walking context pays for the graph table): straight into the share
-            const TableBuild b{sh, h, c->stream};
+            const TableBuild b{sh, h, c->lane().stream};
             if (p->threading == DBTK_THREADING_V13 && !sh->d_gr) { if ((st = build_graph_table(b))) break; }
             if (p->bubbles && !sh->d_tre) { if ((st = build_kl_table(b, h->tre_cnt, h->tre_ks, nullptr, &sh->d_tre, &sh->T.tre, &sh->T.tre_mask, &sh->T.tre_shift))) break; }
             if (p->bait && !sh->d_bait) { if ((st = build_kl_table(b, h->bt_cnt, h->bt_ks, &h->bt_vs, &sh->d_bait, &sh->T.bait, &sh->T.bait_mask, &sh->T.bait_shift))) break; }
             c->T = sh->T;
         }
         if (st) break;
-        chk(hipStreamSynchronize(c->stream), "sync");
+        chk(sync_all(c), "sync");  // (every lane has zeroed its own buffers on its own stream)
     } while (0);
     if (st) { free_ctx(c); return st; }
     *out = c;
@@ -1952,7 +1873,7 @@ static dbtk_status_t run_batch_sync(dbtk_ctx_t* c, const uint8_t* d_seq, const u
                                     uint64_t npairs, uint32_t maxlen, const uint8_t* seq, const uint64_t* off, const uint8_t* qual,
                                     dbtk_pair_rec_t* recs, uint64_t rec_cap, uint64_t* nrec) {
     dbtk_status_t st;
-    hipStream_t s = c->stream;
+    hipStream_t s = c->lane().stream;
     bool want_recs = recs && rec_cap && (c->P.trace || c->P.okam || c->P.extract);
     if (c->P.trackbait && !want_recs) {  // the replay needs the bait-stage records even when the caller wants none
         c->own_recs.resize(npairs);
@@ -1964,24 +1885,24 @@ static dbtk_status_t run_batch_sync(dbtk_ctx_t* c, const uint8_t* d_seq, const u
     if (want_recs) {
         dcap = c->P.trace ? npairs : (rec_cap < npairs ? rec_cap : npairs);
         if (c->P.trace && rec_cap < npairs) { set_error("trace mode needs rec_cap >= npairs"); return DBTK_ERR_ARG; }
-        if ((st = ensure(&c->d_recs, &c->rec_cap, dcap))) return st;
+        if ((st = c->d_recs.ensure(dcap))) return st;
     }
     if (c->P.trackbait && !seq) { set_error("-tb needs the reads in host buffers"); return DBTK_ERR_UNSUPPORTED; }
     const bool walk_recs = c->P.threading == DBTK_THREADING_V13 && c->P.trace;
-    if (walk_recs && (st = ensure(&c->d_trecs, &c->trecs_cap, 2 * npairs))) return st;
+    if (walk_recs && (st = c->d_trecs.ensure(2 * npairs))) return st;
     c->last_walk_npairs = c->P.threading == DBTK_THREADING_V13 ? npairs : 0;
     c->last_walk_recs = walk_recs;
     const bool walk_txt = c->P.threading == DBTK_THREADING_V13 && (c->P.aln & 3u) && (c->P.aln & DBTK_ALN_TEXT);
     const bool walk_aln = c->P.threading == DBTK_THREADING_V13 && (c->P.aln & 3u) && !walk_txt;
     if (!walk_aln) c->aln_max = 0;
     if (!walk_txt) c->txt_cap = 0;
-    if ((st = launch_batch(c, d_seq, d_off, nbytes, npairs, maxlen, want_recs ? c->d_recs : nullptr, (uint32_t)dcap,
-                           d_qual, walk_recs ? c->d_trecs : nullptr, walk_aln, walk_txt))) return st;
+    if ((st = launch_batch(c, d_seq, d_off, nbytes, npairs, maxlen, want_recs ? c->d_recs.p : nullptr, (uint32_t)dcap,
+                           d_qual, walk_recs ? c->d_trecs.p : nullptr, walk_aln, walk_txt))) return st;
     uint32_t small[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(small, c->d_small, sizeof(small), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(small, c->lane().d_small, sizeof(small), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (small[3]) {
-        (void)hipMemsetAsync(c->d_small + 3, 0, 4, s);
+        (void)hipMemsetAsync(c->lane().d_small + 3, 0, 4, s);
         set_error("device reported an over-long read");
         return (dbtk_status_t)small[3];
     }
@@ -1991,9 +1912,9 @@ static dbtk_status_t run_batch_sync(dbtk_ctx_t* c, const uint8_t* d_seq, const u
         // (AQ.cpp:2161-2166), then merged map by map into bubbleDB (accumBubbles, AQ.cpp:1599-1606).
         uint32_t nev = 0;
         HIPCHK(hipMemcpy(&nev, c->d_nevents, 4, hipMemcpyDeviceToHost));
-        if (nev > c->events_cap) { set_error("bubble event log overflow"); return DBTK_ERR_OVERFLOW; }
+        if (nev > c->d_events.cap) { set_error("bubble event log overflow"); return DBTK_ERR_OVERFLOW; }
         std::vector<BubEvent> ev(nev);
-        if (nev) HIPCHK(hipMemcpy(ev.data(), c->d_events, (size_t)nev * sizeof(BubEvent), hipMemcpyDeviceToHost));
+        if (nev) HIPCHK(hipMemcpy(ev.data(), c->d_events.p, (size_t)nev * sizeof(BubEvent), hipMemcpyDeviceToHost));
         std::sort(ev.begin(), ev.end(), [](const BubEvent& x, const BubEvent& y) {
             if (x.pair != y.pair) return x.pair < y.pair;
             if (x.mate != y.mate) return x.mate < y.mate;
@@ -2010,7 +1931,7 @@ static dbtk_status_t run_batch_sync(dbtk_ctx_t* c, const uint8_t* d_seq, const u
         const uint64_t produced = c->P.trace ? npairs : small[2];
         if (nrec) *nrec = produced;
         const uint64_t ncopy = produced < dcap ? produced : dcap;
-        if (ncopy) HIPCHK(hipMemcpy(recs, c->d_recs, ncopy * sizeof(dbtk_pair_rec_t), hipMemcpyDeviceToHost));
+        if (ncopy) HIPCHK(hipMemcpy(recs, c->d_recs.p, ncopy * sizeof(dbtk_pair_rec_t), hipMemcpyDeviceToHost));
         if (!c->P.trace) {
             // compaction order is arbitrary on the device; the reference's order within a batch is pair order
             std::sort(recs, recs + ncopy, [](const dbtk_pair_rec_t& x, const dbtk_pair_rec_t& y) { return x.pair < y.pair; });
@@ -2084,25 +2005,25 @@ static dbtk_status_t dbtk_align_batch_impl(dbtk_ctx_t* c, const uint8_t* seq, co
     if (npairs == 0) return DBTK_OK;
     const uint64_t base = off[0], nbytes = off[nreads] - base;
     dbtk_status_t st;
-    if ((st = ensure(&c->d_seq, &c->seq_cap, nbytes + 32))) return st;
-    if ((st = ensure(&c->d_off, &c->off_cap, nreads + 1))) return st;
-    hipStream_t s = c->stream;
-    if (nbytes) HIPCHK(hipMemcpyAsync(c->d_seq, seq + base, nbytes, hipMemcpyHostToDevice, s));
+    if ((st = c->d_seq.ensure(nbytes + 32))) return st;
+    if ((st = c->d_off.ensure(nreads + 1))) return st;
+    hipStream_t s = c->lane().stream;
+    if (nbytes) HIPCHK(hipMemcpyAsync(c->d_seq.p, seq + base, nbytes, hipMemcpyHostToDevice, s));
     if (base == 0) {
-        HIPCHK(hipMemcpyAsync(c->d_off, off, (nreads + 1) * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->d_off.p, off, (nreads + 1) * 8, hipMemcpyHostToDevice, s));
     } else {
         std::vector<uint64_t> o2(nreads + 1);
         for (uint64_t r = 0; r <= nreads; ++r) o2[r] = off[r] - base;
-        HIPCHK(hipMemcpy(c->d_off, o2.data(), (nreads + 1) * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(c->d_off.p, o2.data(), (nreads + 1) * 8, hipMemcpyHostToDevice));
     }
     uint32_t maxlen = 0;
     for (uint64_t r = 0; r < nreads; ++r) maxlen = std::max<uint32_t>(maxlen, (uint32_t)(off[r + 1] - off[r]));
     const bool use_qual = c->P.bait && qual;  // base qualities only matter to the bait filter (-b with -fq)
     if (use_qual) {
-        if ((st = ensure(&c->d_qual, &c->qual_cap, nbytes + 32))) return st;
-        if (nbytes) HIPCHK(hipMemcpyAsync(c->d_qual, qual + base, nbytes, hipMemcpyHostToDevice, s));
+        if ((st = c->d_qual.ensure(nbytes + 32))) return st;
+        if (nbytes) HIPCHK(hipMemcpyAsync(c->d_qual.p, qual + base, nbytes, hipMemcpyHostToDevice, s));
     }
-    return run_batch_sync(c, c->d_seq, c->d_off, use_qual ? c->d_qual : nullptr, nbytes, npairs, maxlen, seq, off, qual, recs, rec_cap, nrec);
+    return run_batch_sync(c, c->d_seq.p, c->d_off.p, use_qual ? c->d_qual.p : nullptr, nbytes, npairs, maxlen, seq, off, qual, recs, rec_cap, nrec);
 }
 
 // Function-level entry of the graph walk (tests, and callers that want isThreadFeasible alone).
@@ -2120,24 +2041,24 @@ static dbtk_status_t dbtk_thread_batch_impl(dbtk_ctx_t* c, const uint8_t* seq, c
     if (!nreads) return DBTK_OK;
     const uint64_t base = off[0], nbytes = off[nreads] - base;
     dbtk_status_t st;
-    if ((st = ensure(&c->d_seq, &c->seq_cap, nbytes + 32))) return st;
-    if ((st = ensure(&c->d_off, &c->off_cap, nreads + 1))) return st;
-    if ((st = ensure(&c->d_loci, &c->loci_cap, nreads))) return st;
-    if ((st = ensure(&c->d_trecs, &c->trecs_cap, nreads))) return st;
-    hipStream_t s = c->stream;
+    if ((st = c->d_seq.ensure(nbytes + 32))) return st;
+    if ((st = c->d_off.ensure(nreads + 1))) return st;
+    if ((st = c->d_loci.ensure(nreads))) return st;
+    if ((st = c->d_trecs.ensure(nreads))) return st;
+    hipStream_t s = c->lane().stream;
     std::vector<uint64_t> o2(nreads + 1);
     for (uint64_t r = 0; r <= nreads; ++r) o2[r] = off[r] - base;
-    if (nbytes) HIPCHK(hipMemcpyAsync(c->d_seq, seq + base, nbytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_off, o2.data(), (nreads + 1) * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_loci, loci, nreads * 4, hipMemcpyHostToDevice, s));
+    if (nbytes) HIPCHK(hipMemcpyAsync(c->d_seq.p, seq + base, nbytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_off.p, o2.data(), (nreads + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_loci.p, loci, nreads * 4, hipMemcpyHostToDevice, s));
     WalkArgs w;
     memset(&w, 0, sizeof(w));
-    w.T = c->T; w.P = c->P; w.seq = c->d_seq; w.off = c->d_off;
-    w.read_locus = c->d_loci; w.nreads = (uint32_t)nreads; w.trecs = c->d_trecs; w.errflag = c->d_small + 3;
+    w.T = c->T; w.P = c->P; w.seq = c->d_seq.p; w.off = c->d_off.p;
+    w.read_locus = c->d_loci.p; w.nreads = (uint32_t)nreads; w.trecs = c->d_trecs.p; w.errflag = c->lane().d_small + 3;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(nreads, (uint64_t)c->walk_blocks);
     LAUNCH(k_walk_reads, dim3(grid), dim3(64), s, w);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(recs, c->d_trecs, nreads * sizeof(dbtk_thread_rec_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(recs, c->d_trecs.p, nreads * sizeof(dbtk_thread_rec_t), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return DBTK_OK;
 }
@@ -2149,15 +2070,15 @@ static dbtk_status_t dbtk_ctx_walk_results_impl(dbtk_ctx_t* c, dbtk_walk_res_t* 
     if (!c->last_walk_npairs) return DBTK_OK;
     if (trecs && !c->last_walk_recs) { set_error("thread records are only kept with params.trace"); return DBTK_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipStreamSynchronize(c->lane().stream));
     uint32_t nsurv = 0;
-    HIPCHK(hipMemcpy(&nsurv, c->d_small, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&nsurv, c->lane().d_small, 4, hipMemcpyDeviceToHost));
     const uint64_t np = c->last_walk_npairs;
     std::vector<uint32_t> dst(nsurv), ret(nsurv), surv(nsurv);
     if (nsurv) {
-        HIPCHK(hipMemcpy(dst.data(), c->d_walk, (size_t)nsurv * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(ret.data(), c->d_walk + np, (size_t)nsurv * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(surv.data(), c->d_sorted, (size_t)nsurv * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(dst.data(), c->lane().d_walk.p, (size_t)nsurv * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(ret.data(), c->lane().d_walk.p + np, (size_t)nsurv * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(surv.data(), c->lane().d_sorted, (size_t)nsurv * 4, hipMemcpyDeviceToHost));
     }
     std::vector<std::pair<uint32_t, uint32_t>> walked;  // (pair, t)
     for (uint32_t t = 0; t < nsurv; ++t) if (dst[t] != NAN32) walked.emplace_back(surv[t], t);
@@ -2167,7 +2088,7 @@ static dbtk_status_t dbtk_ctx_walk_results_impl(dbtk_ctx_t* c, dbtk_walk_res_t* 
     for (size_t i = 0; i < walked.size(); ++i) {
         const uint32_t t = walked[i].second;
         if (res) { res[i].pair = walked[i].first; res[i].dst = dst[t]; res[i].ret1 = (int8_t)(ret[t] & 0xFF); res[i].ret2 = (int8_t)((ret[t] >> 8) & 0xFF); res[i].pad[0] = res[i].pad[1] = 0; }
-        if (trecs) HIPCHK(hipMemcpy(&trecs[2 * i], &c->d_trecs[2 * (size_t)t], 2 * sizeof(dbtk_thread_rec_t), hipMemcpyDeviceToHost));
+        if (trecs) HIPCHK(hipMemcpy(&trecs[2 * i], &c->d_trecs.p[2 * (size_t)t], 2 * sizeof(dbtk_thread_rec_t), hipMemcpyDeviceToHost));
     }
     return DBTK_OK;
 }
@@ -2178,9 +2099,9 @@ static dbtk_status_t dbtk_ctx_aln_records_impl(dbtk_ctx_t* c, void* buf, uint64_
     *nrec = 0; *stride = c->aln_stride; *cap = c->aln_cap;
     if (!c->aln_max || !c->d_aln) return DBTK_OK;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipStreamSynchronize(c->lane().stream));
     uint32_t nslots = 0;
-    HIPCHK(hipMemcpy(&nslots, c->d_small + 4, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&nslots, c->lane().d_small + 4, 4, hipMemcpyDeviceToHost));
     if (nslots > c->aln_max) { set_error("alignment record buffer overflow"); return DBTK_ERR_OVERFLOW; }
     const size_t st = c->aln_stride;
     // too small for every slot handed out: say what is needed (an upper bound: some slots of a wave's last chunk stay empty), copy nothing
@@ -2224,14 +2145,14 @@ static dbtk_status_t dbtk_ctx_aln_text_impl(dbtk_ctx_t* c, uint32_t* idx, uint64
     *used = 0;
     if (!c->txt_cap || !c->d_txt) { for (uint64_t i = 0; idx && i < idx_cap; ++i) idx[i] = NAN32; return DBTK_OK; }
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipStreamSynchronize(c->lane().stream));
     uint32_t cur = 0;
-    HIPCHK(hipMemcpy(&cur, c->d_small + 7, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&cur, c->lane().d_small + 7, 4, hipMemcpyDeviceToHost));
     if (cur > c->txt_cap) { set_error("alignment text arena overflow"); return DBTK_ERR_OVERFLOW; }
     *used = cur;
     if (cur > arena_cap || (!arena && cur)) { set_error("alignment text buffer too small"); return DBTK_ERR_OVERFLOW; }
     const uint64_t np = std::min<uint64_t>(idx_cap, c->last_walk_npairs);
-    if (idx && np) HIPCHK(hipMemcpy(idx, c->d_txtidx, np * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (idx && np) HIPCHK(hipMemcpy(idx, c->d_txtidx.p, np * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (uint64_t i = np; idx && i < idx_cap; ++i) idx[i] = NAN32;
     if (cur) HIPCHK(hipMemcpy(arena, c->d_txt, cur, hipMemcpyDeviceToHost));
     return DBTK_OK;
@@ -2245,36 +2166,31 @@ dbtk_status_t dbtk_align_batch_device(dbtk_ctx_t* c, const void* d_seq, const vo
     HIPCHK(hipSetDevice(c->device));
     // d_seq is 16-byte aligned and device allocations are page-granular, so the aligned 16-byte
     // chunk holding the last base is always readable: no byte-wise tail needed (seq_len = max).
-    if (c->two_lanes) switch_lane(c);  // successive batches alternate between the two streams
+    if (c->lanes.size() > 1) switch_lane(c);  // successive batches alternate between the two streams
     return launch_batch(c, (const uint8_t*)d_seq, (const uint64_t*)d_offsets, ~0ull, npairs, max_read_len, nullptr, 0);
 }
 
 // The sticky error words of all lanes (a read longer than promised was truncated on the device: the accumulators are
 // tainted from then on).  Reported once, then cleared.
 static dbtk_status_t take_error_words(dbtk_ctx_t* c) {
-    uint32_t err = 0, err2 = 0;
-    HIPCHK(hipMemcpy(&err, c->d_small + 3, 4, hipMemcpyDeviceToHost));
-    if (c->alt.d_small) HIPCHK(hipMemcpy(&err2, c->alt.d_small + 3, 4, hipMemcpyDeviceToHost));
-    for (auto& l : c->parked) {
-        uint32_t e3 = 0;
-        if (l.d_small) HIPCHK(hipMemcpy(&e3, l.d_small + 3, 4, hipMemcpyDeviceToHost));
-        if (e3) err2 = e3;
+    uint32_t err = 0;
+    for (Lane& l : c->lanes) {
+        uint32_t e = 0;
+        HIPCHK(hipMemcpy(&e, l.d_small + 3, 4, hipMemcpyDeviceToHost));
+        if (e && !err) err = e;
     }
-    if (err || err2) {
-        (void)hipMemset(c->d_small + 3, 0, 4);
-        if (c->alt.d_small) (void)hipMemset(c->alt.d_small + 3, 0, 4);
-        for (auto& l : c->parked) if (l.d_small) (void)hipMemset(l.d_small + 3, 0, 4);
-        const uint32_t e = err ? err : err2;
-        set_error(e == DBTK_ERR_READ_TOO_LONG ? "device reported an over-long read (the accumulators include truncated reads)"
-                                              : "device reported an error during the batch");
-        return (dbtk_status_t)e;
+    if (err) {
+        for (Lane& l : c->lanes) (void)hipMemset(l.d_small + 3, 0, 4);
+        set_error(err == DBTK_ERR_READ_TOO_LONG ? "device reported an over-long read (the accumulators include truncated reads)"
+                                                : "device reported an error during the batch");
+        return (dbtk_status_t)err;
     }
     if (c->d_bub) {  // the edge table's sticky word: inserts were lost, the table is short from then on
         uint32_t ovf = 0;
         HIPCHK(hipMemcpy(&ovf, c->d_nevents + BUB_W_OVF, 4, hipMemcpyDeviceToHost));
         if (ovf) {
             (void)hipMemset(c->d_nevents + BUB_W_OVF, 0, 4);
-            set_error("bubble table overflow: " + std::to_string(c->bub_slots) + " slots filled up inside a batch and the spill log of " + std::to_string(c->events_cap) +
+            set_error("bubble table overflow: " + std::to_string(c->bub_slots) + " slots filled up inside a batch and the spill log of " + std::to_string(c->d_events.cap) +
                       " entries with them; start with more slots (DBTK_BUB_SLOTS, a power of two)");
             return DBTK_ERR_OVERFLOW;
         }
@@ -2317,19 +2233,18 @@ dbtk_status_t dbtk_ctx_reset(dbtk_ctx_t* c) {
     if (!c) { set_error("null argument"); return DBTK_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(sync_all(c));
-    HIPCHK(hipMemsetAsync(c->d_accum, 0, c->n_accum * 8, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_pstats, 0, DBTK_PATH_STATS * 8, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_small + 3, 0, 4, c->stream));  // a stale error word would be reported against the next run
-    if (c->alt.d_small) HIPCHK(hipMemsetAsync(c->alt.d_small + 3, 0, 4, c->stream));
-    for (auto& l : c->parked) if (l.d_small) HIPCHK(hipMemsetAsync(l.d_small + 3, 0, 4, c->stream));
-    // pairs appended by dbtk_ingest_align_merged and not yet aligned belong to the run that is being discarded: they must not be
-    // aligned into the fresh accumulators by the next append or flush
-    c->m_bytes = 0; c->m_pairs = 0; c->m_maxlen = 0;
-    c->alt.m_bytes = 0; c->alt.m_pairs = 0; c->alt.m_maxlen = 0;
-    for (auto& l : c->parked) { l.m_bytes = 0; l.m_pairs = 0; l.m_maxlen = 0; }
+    HIPCHK(hipMemsetAsync(c->d_accum, 0, c->n_accum * 8, c->lane().stream));
+    HIPCHK(hipMemsetAsync(c->d_pstats, 0, DBTK_PATH_STATS * 8, c->lane().stream));
+    // a stale error word would be reported against the next run; pairs appended by dbtk_ingest_align_merged and not yet aligned
+    // belong to the run that is being discarded: they must not be aligned into the fresh accumulators by the next append or flush
+    // 
+    for (Lane& l : c->lanes) {
+        HIPCHK(hipMemsetAsync(l.d_small + 3, 0, 4, c->lane().stream));
+        l.m_bytes = 0; l.m_pairs = 0; l.m_maxlen = 0;
+    }
     if (c->d_bub) {  // the edge table: empty, at the capacity it has grown to
-        LAUNCH(k_bub_fill, dim3((uint32_t)std::min<uint64_t>((c->bub_slots + 255) / 256, 4096)), dim3(256), c->stream, c->d_bub, c->bub_slots);
-        HIPCHK(hipMemsetAsync(c->d_nevents, 0, 4 * BUB_WORDS, c->stream));
+        LAUNCH(k_bub_fill, dim3((uint32_t)std::min<uint64_t>((c->bub_slots + 255) / 256, 4096)), dim3(256), c->lane().stream, c->d_bub, c->bub_slots);
+        HIPCHK(hipMemsetAsync(c->d_nevents, 0, 4 * BUB_WORDS, c->lane().stream));
         c->h_bub[0] = c->h_bub[1] = c->h_bub[2] = 0;
         c->bub_seen = 0;
     }
@@ -2348,10 +2263,10 @@ static dbtk_status_t bub_read(dbtk_ctx_t* c, uint32_t th, std::vector<BubSlot>& 
     uint32_t nsp = 0;
     HIPCHK(hipMemcpy(&nsp, c->d_nevents + BUB_W_SPILL, 4, hipMemcpyDeviceToHost));
     if (nsp) { const dbtk_status_t st = bub_grow(c, 0); if (st) return st; }
-    hipStream_t s = c->stream;
+    hipStream_t s = c->lane().stream;
     unsigned long long* d_n = nullptr;
     HIPCHK(hipMalloc(&d_n, 8));
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((c->bub_slots + 255) / 256, (uint64_t)c->num_cu * 8);
+    const uint32_t grid = grid256(c, c->bub_slots);
     unsigned long long n = 0;
     BubSlot* d_out = nullptr;
     dbtk_status_t st = [&]() -> dbtk_status_t {
@@ -2506,7 +2421,7 @@ int dbtk_ctx_kernel_times(dbtk_ctx_t* c, const char** names, double* total_ms, u
 int dbtk_debug_stamps(dbtk_ctx_t* c, uint64_t* out16) {
     (void)hipSetDevice(c->device);
     (void)sync_all(c);
-    return (int)hipMemcpy(out16, c->d_small + 32, 48 * 8, hipMemcpyDeviceToHost);
+    return (int)hipMemcpy(out16, c->lane().d_small + 32, 48 * 8, hipMemcpyDeviceToHost);
 }
 #endif
 
@@ -2562,8 +2477,8 @@ dbtk_status_t dbtk_allreduce(dbtk_ctx_t** ctxs, int n) {
         if (rep_of[i] != i) {
             dbtk_ctx* d = ctxs[rep_of[i]];
             HIPCHK(hipSetDevice(d->device));
-            LAUNCH(k_accum_add, dim3(1024), dim3(256), d->stream, d->d_accum, ctxs[i]->d_accum, d->n_accum);
-            HIPCHK(hipStreamSynchronize(d->stream));
+            LAUNCH(k_accum_add, dim3(1024), dim3(256), d->lane().stream, d->d_accum, ctxs[i]->d_accum, d->n_accum);
+            HIPCHK(hipStreamSynchronize(d->lane().stream));
         }
     const int nd = (int)rep.size();
     int rc = 0;
@@ -2586,12 +2501,12 @@ dbtk_status_t dbtk_allreduce(dbtk_ctx_t** ctxs, int n) {
         for (int q = 0; q < nd && !rc; ++q) {
             dbtk_ctx* c = ctxs[rep[q]];
             (void)hipSetDevice(c->device);
-            rc = (int)allReduce(c->d_accum, c->d_accum, c->n_accum, ncclUint64, ncclSum, comms[q], c->stream);
+            rc = (int)allReduce(c->d_accum, c->d_accum, c->n_accum, ncclUint64, ncclSum, comms[q], c->lane().stream);
         }
         rc |= (int)groupEnd();
         for (int q = 0; q < nd; ++q) {
             (void)hipSetDevice(ctxs[rep[q]]->device);
-            (void)hipStreamSynchronize(ctxs[rep[q]]->stream);
+            (void)hipStreamSynchronize(ctxs[rep[q]]->lane().stream);
             commDestroy(comms[q]);
         }
     }
@@ -2863,10 +2778,10 @@ static dbtk_status_t dbtk_ingest_align_impl(dbtk_ingest_t* g, uint32_t slot, dbt
     HIPCHK(hipSetDevice(c->device));
     if (sync) return run_batch_sync(c, S.d_flat, S.d_off, S.d_qual, ~0ull, h.nkept, (uint32_t)h.maxlen, nullptr, nullptr, nullptr, recs, rec_cap, nrec);
     if (c->P.bubbles == 1) { set_error("dbtk_ingest_align: -bu is replayed batch by batch on the host: sync = 1"); return DBTK_ERR_ARG; }
-    if (c->two_lanes) switch_lane(c);
+    if (c->lanes.size() > 1) switch_lane(c);
     const dbtk_status_t st = launch_batch(c, S.d_flat, S.d_off, ~0ull, h.nkept, (uint32_t)h.maxlen, nullptr, 0, S.d_qual);
     if (st) return st;
-    HIPCHK(hipEventRecord(S.aligned, c->stream));
+    HIPCHK(hipEventRecord(S.aligned, c->lane().stream));
     S.has_aligned = true;
     return DBTK_OK;
 }
@@ -2883,7 +2798,8 @@ static dbtk_status_t dbtk_ingest_align_merged_impl(dbtk_ingest_t* g, uint32_t sl
     { const dbtk_status_t sc = ingest_ctx(g, cx, &c); if (sc) return sc; }
     HIPCHK(hipSetDevice(c->device));
     if (c->P.bubbles == 1 || c->P.trace || (c->P.bait && g->with_qual)) { set_error("dbtk_ingest_align_merged: records, -bu and -b with qualities go block by block (dbtk_ingest_align)"); return DBTK_ERR_ARG; }
-    hipStream_t s = c->stream;
+    Lane& L = c->lane();  // (the lane the blocks are merged into; left only at the end, once its batch has been launched)
+    hipStream_t s = L.stream;
     if (slot != ~0u) {
         dbtk_ingest::Slot& S = g->slots[slot];
         if (!S.waited) { set_error("dbtk_ingest_align_merged: wait for the block first"); return DBTK_ERR_ARG; }
@@ -2900,47 +2816,47 @@ static dbtk_status_t dbtk_ingest_align_merged_impl(dbtk_ingest_t* g, uint32_t sl
             // later blocks hold longer reads.  An allocation that fails (beside 28 - 47 GB of tables) is not the end of the run: the
             // pairs merged so far are aligned now, and the block starts a new batch in the room there is.
             const uint64_t mp = std::min<uint64_t>(std::max<uint64_t>(min_pairs, 1), 1ull << 26);
-            if (c->m_bytes + nb + 64 > c->m_flat_cap || 2 * c->m_pairs + nr + 1 > c->m_off_cap) {
-                const uint64_t want_f = std::max<uint64_t>({(c->m_bytes + nb + 64) * 5 / 4, 64ull << 20, mp * 2 * h.maxlen + nb + 64});
-                const uint64_t want_o = std::max<uint64_t>({(2 * c->m_pairs + nr + 1) * 5 / 4, 1ull << 20, 2 * mp + nr + 1});
+            if (L.m_bytes + nb + 64 > L.m_flat.cap || 2 * L.m_pairs + nr + 1 > L.m_off.cap) {
+                const uint64_t want_f = std::max<uint64_t>({(L.m_bytes + nb + 64) * 5 / 4, 64ull << 20, mp * 2 * h.maxlen + nb + 64});
+                const uint64_t want_o = std::max<uint64_t>({(2 * L.m_pairs + nr + 1) * 5 / 4, 1ull << 20, 2 * mp + nr + 1});
                 uint8_t* nf = nullptr; uint64_t* no = nullptr;
-                const bool grow_f = c->m_bytes + nb + 64 > c->m_flat_cap, grow_o = 2 * c->m_pairs + nr + 1 > c->m_off_cap;
+                const bool grow_f = L.m_bytes + nb + 64 > L.m_flat.cap, grow_o = 2 * L.m_pairs + nr + 1 > L.m_off.cap;
                 bool ok = (!grow_f || hipMalloc(&nf, want_f) == hipSuccess) && (!grow_o || hipMalloc(&no, want_o * 8) == hipSuccess);
                 if (!ok) {
                     (void)hipGetLastError();
                     if (nf) (void)hipFree(nf);
                     if (no) (void)hipFree(no);
                     nf = nullptr; no = nullptr;
-                    if (c->m_pairs) {  // align what is there, wait for it, start over in the same buffers
-                        const dbtk_status_t st = launch_batch(c, c->m_flat, c->m_off, ~0ull, c->m_pairs, c->m_maxlen, nullptr, 0, nullptr);
+                    if (L.m_pairs) {  // align what is there, wait for it, start over in the same buffers
+                        const dbtk_status_t st = launch_batch(c, L.m_flat.p, L.m_off.p, ~0ull, L.m_pairs, L.m_maxlen, nullptr, 0, nullptr);
                         if (st) return st;
                         HIPCHK(hipStreamSynchronize(s));
-                        c->m_bytes = 0; c->m_pairs = 0; c->m_maxlen = 0;
+                        L.m_bytes = 0; L.m_pairs = 0; L.m_maxlen = 0;
                     }
-                    if (nb + 64 > c->m_flat_cap) { if (c->m_flat) HIPCHK(hipFree(c->m_flat)); c->m_flat = nullptr; c->m_flat_cap = 0; HIPCHK(hipMalloc(&nf, nb + 64)); c->m_flat = nf; c->m_flat_cap = nb + 64; }
-                    if (nr + 1 > c->m_off_cap) { if (c->m_off) HIPCHK(hipFree(c->m_off)); c->m_off = nullptr; c->m_off_cap = 0; HIPCHK(hipMalloc(&no, (nr + 1) * 8)); c->m_off = no; c->m_off_cap = nr + 1; }
+                    if (nb + 64 > L.m_flat.cap) { if (L.m_flat.p) HIPCHK(hipFree(L.m_flat.p)); L.m_flat.p = nullptr; L.m_flat.cap = 0; HIPCHK(hipMalloc(&nf, nb + 64)); L.m_flat.p = nf; L.m_flat.cap = nb + 64; }
+                    if (nr + 1 > L.m_off.cap) { if (L.m_off.p) HIPCHK(hipFree(L.m_off.p)); L.m_off.p = nullptr; L.m_off.cap = 0; HIPCHK(hipMalloc(&no, (nr + 1) * 8)); L.m_off.p = no; L.m_off.cap = nr + 1; }
                 } else {
-                    if (nf && c->m_bytes) HIPCHK(hipMemcpyAsync(nf, c->m_flat, c->m_bytes, hipMemcpyDeviceToDevice, s));
-                    if (no && c->m_pairs) HIPCHK(hipMemcpyAsync(no, c->m_off, (2 * c->m_pairs + 1) * 8, hipMemcpyDeviceToDevice, s));
-                    if ((nf && c->m_flat) || (no && c->m_off)) HIPCHK(hipStreamSynchronize(s));
-                    if (nf) { if (c->m_flat) HIPCHK(hipFree(c->m_flat)); c->m_flat = nf; c->m_flat_cap = want_f; }
-                    if (no) { if (c->m_off) HIPCHK(hipFree(c->m_off)); c->m_off = no; c->m_off_cap = want_o; }
+                    if (nf && L.m_bytes) HIPCHK(hipMemcpyAsync(nf, L.m_flat.p, L.m_bytes, hipMemcpyDeviceToDevice, s));
+                    if (no && L.m_pairs) HIPCHK(hipMemcpyAsync(no, L.m_off.p, (2 * L.m_pairs + 1) * 8, hipMemcpyDeviceToDevice, s));
+                    if ((nf && L.m_flat.p) || (no && L.m_off.p)) HIPCHK(hipStreamSynchronize(s));
+                    if (nf) { if (L.m_flat.p) HIPCHK(hipFree(L.m_flat.p)); L.m_flat.p = nf; L.m_flat.cap = want_f; }
+                    if (no) { if (L.m_off.p) HIPCHK(hipFree(L.m_off.p)); L.m_off.p = no; L.m_off.cap = want_o; }
                 }
             }
-            HIPCHK(hipMemcpyAsync(c->m_flat + c->m_bytes, S.d_flat, nb, hipMemcpyDeviceToDevice, s));
-            LAUNCH(k_off_rebase, dim3((uint32_t)std::min<uint64_t>((nr + 256) / 256, 1024)), dim3(256), s, c->m_off + 2 * c->m_pairs, S.d_off, nr + 1, c->m_bytes);
+            HIPCHK(hipMemcpyAsync(L.m_flat.p + L.m_bytes, S.d_flat, nb, hipMemcpyDeviceToDevice, s));
+            LAUNCH(k_off_rebase, dim3((uint32_t)std::min<uint64_t>((nr + 256) / 256, 1024)), dim3(256), s, L.m_off.p + 2 * L.m_pairs, S.d_off, nr + 1, L.m_bytes);
             HIPCHK(hipEventRecord(S.aligned, s));  // (the slot's arrays are free again once they have been copied)
             S.has_aligned = true;
-            c->m_bytes += nb; c->m_pairs += h.nkept;
-            c->m_maxlen = std::max<uint32_t>(c->m_maxlen, (uint32_t)h.maxlen);
+            L.m_bytes += nb; L.m_pairs += h.nkept;
+            L.m_maxlen = std::max<uint32_t>(L.m_maxlen, (uint32_t)h.maxlen);
         }
     }
-    if (c->m_pairs && (flush || c->m_pairs >= min_pairs)) {
-        const dbtk_status_t st = launch_batch(c, c->m_flat, c->m_off, ~0ull, c->m_pairs, c->m_maxlen, nullptr, 0, nullptr);
+    if (L.m_pairs && (flush || L.m_pairs >= min_pairs)) {
+        const dbtk_status_t st = launch_batch(c, L.m_flat.p, L.m_off.p, ~0ull, L.m_pairs, L.m_maxlen, nullptr, 0, nullptr);
         if (st) return st;
-        c->m_bytes = 0; c->m_pairs = 0; c->m_maxlen = 0;
+        L.m_bytes = 0; L.m_pairs = 0; L.m_maxlen = 0;
         // (the next blocks are merged into the OTHER lane's buffers, on its stream: this lane's kernels are reading these)
-        if (c->two_lanes) switch_lane(c);
+        if (c->lanes.size() > 1) switch_lane(c);
     }
     return DBTK_OK;
 }
@@ -2972,7 +2888,7 @@ static dbtk_status_t dbtk_ingest_aln_lines_impl(dbtk_ingest_t* g, uint32_t slot,
     struct Busy { std::atomic<int>& b; Busy(std::atomic<int>& x) : b(x) { ++b; } ~Busy() { --b; } } busy(g->lines_busy[slot]);
     if (S.pending) { set_error("dbtk_ingest_aln_lines: the slot has been submitted again"); return DBTK_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
+    hipStream_t s = c->lane().stream;
     dbtk_ingest::LinesBuf* Bp;
     {
         std::lock_guard<std::mutex> l(g->lines_m);
@@ -2996,7 +2912,7 @@ static dbtk_status_t dbtk_ingest_aln_lines_impl(dbtk_ingest_t* g, uint32_t slot,
     };
     HIPCHK(hipStreamSynchronize(s));
     uint32_t cur = 0;
-    HIPCHK(hipMemcpy(&cur, c->d_small + 7, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&cur, c->lane().d_small + 7, 4, hipMemcpyDeviceToHost));
     if (cur > c->txt_cap) { set_error("alignment text arena overflow"); return DBTK_ERR_OVERFLOW; }
     const uint64_t tcap = (uint64_t)(S.end - S.hdr.base) + cur + 24ull * nk + 64;  // every line: bytes of the block + its record + separators and dst
     const uint64_t nmem = tcap / GZ_MEMBER + 1;
@@ -3007,7 +2923,7 @@ static dbtk_status_t dbtk_ingest_aln_lines_impl(dbtk_ingest_t* g, uint32_t slot,
     HIPCHK(hipMemsetAsync(B.d_totals, 0, 4 * 8, s));
     AlnLineArgs la;
     memset(&la, 0, sizeof(la));
-    la.raw = S.d_raw; la.spans = S.d_spans; la.hdr = g->d_hdr + slot; la.txt = c->d_txt; la.txt_idx = c->d_txtidx;
+    la.raw = S.d_raw; la.spans = S.d_spans; la.hdr = g->d_hdr + slot; la.txt = c->d_txt; la.txt_idx = c->d_txtidx.p;
     la.len = B.d_linelen; la.text = B.d_text; la.total = B.d_totals;
     LAUNCH(k_aln_len, dim3(c->num_cu * 2), dim3(256), s, la);
     LAUNCH(k_aln_scan, dim3(ING_SCAN_BLOCKS), dim3(64), s, la, 0);
@@ -3156,8 +3072,8 @@ dbtk_status_t dbtk_ingest_aln_lines(dbtk_ingest_t* g, uint32_t slot, dbtk_ctx_t*
 dbtk_status_t dbtk::ctx_facts(const dbtk_ctx_t* c, dbtk::CtxFacts* out) {
     if (!c || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
     out->device = c->device; out->ntrkmers = c->ntr;
-    out->unflushed_pairs = c->m_pairs + c->alt.m_pairs;
-    for (auto& l : c->parked) out->unflushed_pairs += l.m_pairs;
+    out->unflushed_pairs = 0;
+    for (const Lane& l : c->lanes) out->unflushed_pairs += l.m_pairs;
     return DBTK_OK;
 }
 
@@ -3171,11 +3087,11 @@ dbtk_status_t dbtk::ctx_align_device(dbtk_ctx_t* c, int device, const uint8_t* d
     HIPCHK(hipSetDevice(c->device));
     if (!sync) {
         if (c->P.bubbles == 1) { set_error("-bu is replayed batch by batch on the host: sync = 1"); return DBTK_ERR_ARG; }
-        if (c->two_lanes) switch_lane(c);
+        if (c->lanes.size() > 1) switch_lane(c);
     }
-    if (ready) HIPCHK(hipStreamWaitEvent(c->stream, (hipEvent_t)ready, 0));
+    if (ready) HIPCHK(hipStreamWaitEvent(c->lane().stream, (hipEvent_t)ready, 0));
     const dbtk_status_t st = sync ? run_batch_sync(c, d_seq, d_off, nullptr, ~0ull, npairs, max_read_len, nullptr, nullptr, nullptr, recs, rec_cap, nrec)
                                   : launch_batch(c, d_seq, d_off, ~0ull, npairs, max_read_len, nullptr, 0);
-    if (done) HIPCHK(hipEventRecord((hipEvent_t)done, c->stream));
+    if (done) HIPCHK(hipEventRecord((hipEvent_t)done, c->lane().stream));
     return st;
 }
