@@ -937,6 +937,112 @@ class Sim:
             self.h = None
 
 
+EXPORTS_EVAL = [
+    "dbtk_eval_api_version", "dbtk_eval_create", "dbtk_eval_free", "dbtk_eval_truth_sim", "dbtk_eval_truth_set", "dbtk_eval_truth", "dbtk_eval_truth_reset",
+    "dbtk_eval_score_ctx", "dbtk_eval_score_device", "dbtk_eval_score_host", "dbtk_eval_sums", "dbtk_eval_columns", "dbtk_eval_write", "dbtk_eval_times",
+]
+EVAL_FIELDS = ("nk", "windows", "n1", "Sx", "Sy", "Sy1", "Sxy", "Sxx", "Syy", "Syy1")  # dbtk_eval_sums_t
+
+
+def _bind_eval(L):
+    vpp = C.POINTER(C.c_void_p)
+    L.dbtk_eval_api_version.restype = C.c_uint32
+    L.dbtk_eval_api_version.argtypes = []
+    L.dbtk_eval_create.argtypes = [C.c_void_p, C.c_int, vpp]
+    L.dbtk_eval_free.argtypes = [C.c_void_p]
+    L.dbtk_eval_free.restype = None
+    L.dbtk_eval_truth_sim.argtypes = [C.c_void_p, C.c_void_p]
+    L.dbtk_eval_truth_set.argtypes = [C.c_void_p, u64p, u64p]
+    L.dbtk_eval_truth.argtypes = [C.c_void_p, u64p, u64p]
+    L.dbtk_eval_truth_reset.argtypes = [C.c_void_p]
+    L.dbtk_eval_score_ctx.argtypes = [C.c_void_p, C.c_void_p]
+    L.dbtk_eval_score_device.argtypes = [C.c_void_p, C.c_void_p]
+    L.dbtk_eval_score_host.argtypes = [C.c_void_p, u64p]
+    L.dbtk_eval_sums.argtypes = [C.c_void_p, C.POINTER(abi.EvalSums)]
+    L.dbtk_eval_columns.argtypes = [C.POINTER(abi.EvalSums), C.c_uint64, C.POINTER(abi.EvalCols)]
+    L.dbtk_eval_write.argtypes = [C.c_void_p, C.c_char_p]
+    L.dbtk_eval_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), u64p]
+    if L.dbtk_eval_api_version() != abi.EVAL_API_VERSION:
+        raise RuntimeError("libdbtk_hip.so: dbtk_eval.h version mismatch")
+
+
+def eval_columns(lib, sums):
+    """dbtk_eval_columns over a list of dicts (or tuples in EVAL_FIELDS order): [(slope, pred, r2, pred_present, r2_present)]; no device."""
+    _bind_eval(lib.L)
+    n = len(sums)
+    arr = (abi.EvalSums * max(n, 1))()
+    for i, s in enumerate(sums):
+        for j, f in enumerate(EVAL_FIELDS):
+            setattr(arr[i], f, int(s[f] if isinstance(s, dict) else s[j]))
+    out = (abi.EvalCols * max(n, 1))()
+    lib._chk(lib.L.dbtk_eval_columns(arr, n, out))
+    return [(c.slope, c.pred, c.r2, c.pred_present, c.r2_present) for c in out[:n]]
+
+
+class Eval:
+    """The genotype score of include/dbtk_eval.h through ctypes: truth counts from attached Sim handles (or from the host), a context's
+    or any count vector scored against them per locus: exact sums, and the derived columns of kmers.linreg.py as closed forms."""
+
+    def __init__(self, lib, rpgg, device=0):
+        self._lib = lib
+        _bind_eval(lib.L)
+        self.nk, self.nloci = int(rpgg.ntrkmers), int(rpgg.nloci)
+        self.h = C.c_void_p()
+        lib._chk(lib.L.dbtk_eval_create(rpgg.h, int(device), C.byref(self.h)))
+
+    def truth_sim(self, sim):
+        self._lib._chk(self._lib.L.dbtk_eval_truth_sim(self.h, sim.h))
+
+    def truth_set(self, counts, windows=None):
+        c = np.ascontiguousarray(counts, np.uint64)
+        w = np.ascontiguousarray(windows, np.uint64) if windows is not None else None
+        assert len(c) == self.nk and (w is None or len(w) == self.nloci)
+        self._lib._chk(self._lib.L.dbtk_eval_truth_set(self.h, _ptr(c, u64p), _ptr(w, u64p)))
+
+    def truth(self):
+        """(counts[nk] in OUT.trkmc.ar order, windows[nloci])"""
+        c, w = np.zeros(self.nk, np.uint64), np.zeros(self.nloci, np.uint64)
+        self._lib._chk(self._lib.L.dbtk_eval_truth(self.h, _ptr(c, u64p), _ptr(w, u64p)))
+        return c, w
+
+    def truth_reset(self):
+        self._lib._chk(self._lib.L.dbtk_eval_truth_reset(self.h))
+
+    def score_ctx(self, ctx):
+        self._lib._chk(self._lib.L.dbtk_eval_score_ctx(self.h, ctx.h))
+        return self.sums()
+
+    def score_device(self, d_counts):
+        self._lib._chk(self._lib.L.dbtk_eval_score_device(self.h, C.c_void_p(int(d_counts))))
+        return self.sums()
+
+    def score_host(self, counts):
+        c = np.ascontiguousarray(counts, np.uint64)
+        assert len(c) == self.nk
+        self._lib._chk(self._lib.L.dbtk_eval_score_host(self.h, _ptr(c, u64p)))
+        return self.sums()
+
+    def sums(self):
+        """per locus a dict of the ten integers of dbtk_eval_sums_t"""
+        arr = (abi.EvalSums * max(self.nloci, 1))()
+        self._lib._chk(self._lib.L.dbtk_eval_sums(self.h, arr))
+        return [{f: int(getattr(arr[l], f)) for f in EVAL_FIELDS} for l in range(self.nloci)]
+
+    def write(self, prefix):
+        self._lib._chk(self._lib.L.dbtk_eval_write(self.h, os.fsencode(prefix)))
+
+    def times(self):
+        """(milliseconds in k_eval_truth, milliseconds in k_eval_sums, class-table look-ups)"""
+        ms, n = (C.c_double * 2)(), C.c_uint64()
+        self._lib._chk(self._lib.L.dbtk_eval_times(self.h, ms, C.byref(n)))
+        return float(ms[0]), float(ms[1]), int(n.value)
+
+    def close(self):
+        if self.h:
+            self._lib.L.dbtk_eval_free(self.h)
+            self.h = None
+
+
 class Synth:
     """Seeded release-scale workload generator (csrc/dbtk_synth.cpp): a flat
     RPGG + 150 bp read pairs, for bench.py and the scale tests."""

@@ -9,6 +9,7 @@ KCP_API_VERSION = 1  # include/dbtk_kcp.h: DBTK_KCP_API_VERSION (a version of it
 KCP_TP_ONLY = 1      # dbtk_kcp_create flags
 KCP_FPS_MI_NONE, KCP_FPS_MA_NONE = 255, 0  # dbtk_kcp_fps_read: (mi, ma) of a living candidate that no TP table held
 SIM_API_VERSION = 1  # include/dbtk_sim.h: DBTK_SIM_API_VERSION
+EVAL_API_VERSION = 1  # include/dbtk_eval.h: DBTK_EVAL_API_VERSION
 BUBBLES_LOG, BUBBLES_TABLE = 1, 2  # params.bubbles: event log replayed on the host (reference order) | counts in a device table
 ALN_TEXT = 4  # params.aln | ALN_TEXT: alignment records in text form (dbtk_ctx_aln_text)
 THREAD_CAP = 384
@@ -110,3 +111,13 @@ class SimFacts(C.Structure):
     """include/dbtk_sim.h: dbtk_sim_facts_t"""
     _fields_ = [(n, C.c_uint64) for n in ("ncontigs", "nskipped", "nfrags", "arena_bytes", "nbreaks")] + \
                [(n, C.c_uint32) for n in ("flen", "rlen", "shft", "ngroups")]
+
+
+class EvalSums(C.Structure):
+    """include/dbtk_eval.h: dbtk_eval_sums_t"""
+    _fields_ = [(n, C.c_uint64) for n in ("nk", "windows", "n1", "Sx", "Sy", "Sy1", "Sxy", "Sxx", "Syy", "Syy1")]
+
+
+class EvalCols(C.Structure):
+    """include/dbtk_eval.h: dbtk_eval_cols_t"""
+    _fields_ = [(n, C.c_double) for n in ("slope", "pred", "r2", "pred_present", "r2_present")]

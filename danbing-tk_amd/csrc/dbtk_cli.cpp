@@ -47,6 +47,7 @@
 #include "../../include/dbtk.h"
 #include "../../include/dbtk_pred.h"
 #include "../../include/dbtk_kcp.h"
+#include "../../include/dbtk_eval.h"
 #include "../../include/dbtk_sim.h"
 #include "dbtk_pred_io.h"
 
@@ -113,6 +114,8 @@ struct Opts {
     std::vector<std::pair<std::string, std::string>> sim;
     uint64_t simFs = 500, simRlen = 150, simC = 15, simMl = 50000;  // --sim-fs / --sim-rlen / --sim-c / --sim-ml
     std::string simParam;              // the first --sim-* flag given (they need --sim)
+    // --eval PREF: the counts of the run scored per locus against the genome's own k-mer counts (include/dbtk_eval.h): PREF.eval.tsv, PREF.pred
+    std::string eval, evalTruth, evalDumpTruth;  // --eval-truth FILE: the truth from a file (OUT.trkmc.ar layout); --eval-dump-truth FILE: the truth of --sim into one
 };
 struct CohortSample { std::string reads, prefix; float depth = 0; };
 
@@ -154,6 +157,13 @@ void usage() {
             "  --genome <NAME>        with --bait-fps and --sim: every --sim that follows belongs to genome NAME.  The first genome is counted in\n"
             "                         both classes and its FP k-mers become the candidates; every genome's TP profile filters them in turn (one\n"
             "                         table in HBM at a time), OUT is written after the last.  Not with --bait-profile\n"
+            "  --eval <PREF>          score the run's TR k-mer counts against the genome's own: per locus the regression of the counts from reads\n"
+            "                         on the truth counts (windows of the assembly's TR intervals), what kmers.linreg.py --mapkmer reports.\n"
+            "                         PREF.eval.tsv (the exact sums, slope, pred, r2) and PREF.pred (TrueDosage, PredDosage, Slope, r^2; closed forms\n"
+            "                         of the no-intercept fit, not a statsmodels run).  The truth: with --sim the assemblies of the run, counted on\n"
+            "                         the GPU; else --eval-truth.  One GPU; not with --cohort, --genome, -e, --ingest-shards, --parse-only\n"
+            "  --eval-truth <FILE>    with --eval and without --sim: the truth counts from FILE (u64 nk | u64 counts[nk], the OUT.trkmc.ar layout)\n"
+            "  --eval-dump-truth <FILE>  with --eval and --sim: write the truth counts in that layout\n"
             "Algorithm:\n"
             "  -k <INT> [21]  -kf <N> <M> [4 1]  -cth <INT> [10]  -c <INT> [40]  -qth <INT> [20]  -qc <FILE>  -b [FILE]\n"
             "Execution:\n"
@@ -436,6 +446,9 @@ int main(int argc, char* argv[]) {
             const uint64_t v = strtoull(need(++argi).c_str(), nullptr, 10);
             (a == "--sim-fs" ? o.simFs : a == "--sim-rlen" ? o.simRlen : a == "--sim-c" ? o.simC : o.simMl) = v;
         }
+        else if (a == "--eval") o.eval = need(++argi);
+        else if (a == "--eval-truth") o.evalTruth = need(++argi);
+        else if (a == "--eval-dump-truth") o.evalDumpTruth = need(++argi);
         else if (a == "--pred") { o.pred.clear(); for (int i = 0; i < 4; ++i) o.pred.push_back(need(++argi)); }
         else if (a == "--kms") o.kms = need(++argi);
         else if (a == "--dosage") { o.dosage.clear(); for (int i = 0; i < 3; ++i) o.dosage.push_back(need(++argi)); }
@@ -473,6 +486,22 @@ int main(int argc, char* argv[]) {
             for (const std::string* fn : {&fb.first, &fb.second})
                 if (!readable(*fn)) refuse("--sim: cannot open " + *fn);
         o.simmode = 2;
+    }
+    // ---- --eval: what it refuses — before the GPU is asked for anything (the nk of an --eval-truth file: once the RPGG is loaded)
+    const bool eval = !o.eval.empty();
+    if (!eval && !o.evalTruth.empty()) refuse("--eval-truth needs --eval");
+    if (!eval && !o.evalDumpTruth.empty()) refuse("--eval-dump-truth needs --eval");
+    if (eval) {
+        if (!sim && o.evalTruth.empty()) refuse("--eval needs a truth: --sim (the assemblies of the run) or --eval-truth FILE");
+        if (sim && !o.evalTruth.empty()) refuse("--eval takes its truth from --sim or from --eval-truth, not from both");
+        if (!o.evalDumpTruth.empty() && !sim) refuse("--eval-dump-truth needs --sim (with --eval-truth the truth is a file already)");
+        if (!o.cohortFn.empty()) refuse("--eval cannot be combined with --cohort");
+        if (!o.genomes.empty()) refuse("--eval cannot be combined with --genome");
+        if (o.extractFastX) refuse("--eval cannot be combined with -e (nothing is counted)");
+        if (o.ngpus > 1) refuse("--eval runs on one GPU: --gpus > 1 is not supported with it");
+        if (o.ingestShards > 0) refuse("--eval cannot be combined with --ingest-shards");
+        if (o.parseOnly) refuse("--eval cannot be combined with --parse-only");
+        if (!o.evalTruth.empty() && !readable(o.evalTruth)) refuse("--eval-truth: cannot open " + o.evalTruth);
     }
     // ---- cohort mode: what it refuses, and its manifest — all of it before the GPU is asked for anything
     const bool cohort = !o.cohortFn.empty();
@@ -695,6 +724,17 @@ int main(int argc, char* argv[]) {
         if (dbtk_rpgg_set_index_cache(rpgg, (cp + ".dbtk.idx").c_str(), 2)) die_assert(dbtk_last_error());
     }
     fprintf(stderr, "total number of loci in %s: %llu\n", o.trFname.c_str(), (unsigned long long)nloci);
+    // --eval-truth: the file's counts, refused here — before any batch — when they are not of this RPGG
+    std::vector<uint64_t> eval_truth;
+    if (!o.evalTruth.empty()) {
+        FILE* f = fopen(o.evalTruth.c_str(), "rb");
+        uint64_t nk = 0;
+        if (!f || fread(&nk, 8, 1, f) != 1) refuse("--eval-truth: cannot read " + o.evalTruth);
+        if (nk != dbtk_rpgg_ntrkmers(rpgg)) refuse("--eval-truth: " + o.evalTruth + " holds " + std::to_string(nk) + " counts, the RPGG has " + std::to_string(dbtk_rpgg_ntrkmers(rpgg)) + " TR k-mers");
+        eval_truth.resize(nk);
+        if (nk && fread(eval_truth.data(), 8, nk, f) != nk) refuse("--eval-truth: " + o.evalTruth + " ends before its " + std::to_string(nk) + " counts");
+        fclose(f);
+    }
     // --sim: the host pass over every assembly and its BED (contig table, source-locus step functions); a file that does not parse ends the run here
     std::vector<dbtk_sim_t*> sims;
     double sim_open_s = 0;
@@ -764,6 +804,15 @@ int main(int argc, char* argv[]) {
     if (!o.parseOnly)
         for (int d = 0; d < o.ngpus; ++d)
             if (dbtk_ctx_create(rpgg, &P, dev_of(d), &ctx[d])) die_assert(dbtk_last_error());
+    // --eval: truth counts and windows in HBM beside the accumulators (it shares the contexts' class table)
+    dbtk_eval_t* evl = nullptr;
+    double eval_make_s = 0, eval_truth_s = 0;
+    if (eval) {
+        const double t0 = wall();
+        if (dbtk_eval_create(rpgg, dev_of(0), &evl)) die_assert(std::string("--eval: ") + dbtk_last_error());
+        if (!o.evalTruth.empty() && dbtk_eval_truth_set(evl, eval_truth.data(), nullptr)) die_assert(std::string("--eval-truth: ") + dbtk_last_error());
+        eval_make_s = wall() - t0;
+    }
     // cohort mode: a second context on the same device (the tables are shared: it costs its accumulators and scratch) so that one
     // sample is read and aligned while the one before it is finished, and the genotype matrix of --pred — all of it before the
     // first sample, so that HBM that does not suffice ends the run before any work is done
@@ -1950,6 +1999,13 @@ int main(int argc, char* argv[]) {
             if (dbtk_sim_attach(S, dev_of(0))) die_assert(std::string("--sim: ") + dbtk_last_error());
             dbtk_sim_facts_t sf;
             if (dbtk_sim_info(S, &sf)) die_assert(dbtk_last_error());
+            // --eval: the assembly's truth, before its first batch (the contig group the pass ends on is the one that batch finds resident
+            // when the assembly is one group)
+            if (evl) {
+                const double t0 = wall();
+                if (dbtk_eval_truth_sim(evl, S)) die_assert(std::string("--eval: ") + dbtk_last_error());
+                eval_truth_s += wall() - t0;
+            }
             for (uint64_t f0 = 0; f0 < sf.nfrags; f0 += BP) {
                 const uint64_t n = std::min<uint64_t>(BP, sf.nfrags - f0);
                 const time_t t2 = time(nullptr);
@@ -2251,6 +2307,30 @@ int main(int argc, char* argv[]) {
             fprintf(stderr, "writing kmers...\n");
             if (dbtk_write_outputs(rpgg, counts.data(), kmc.data(), nmapread.data(), o.outPrefix.c_str(), o.writeKmerName))
                 die_assert(dbtk_last_error());
+            if (evl) {  // --eval: the run's counts where they lie (the sum of several contexts' from the host), against the truth in HBM
+                fprintf(stderr, "writing the genotype score...\n");
+                const double te0 = wall();
+                if (nctx == 1 ? dbtk_eval_score_ctx(evl, ctx[0]) : dbtk_eval_score_host(evl, counts.data())) die_assert(std::string("--eval: ") + dbtk_last_error());
+                if (dbtk_eval_write(evl, o.eval.c_str())) die_assert(std::string("--eval: ") + dbtk_last_error());
+                const double te1 = wall();
+                std::vector<uint64_t> tc(o.evalDumpTruth.empty() ? 0 : counts.size()), win(nloci);
+                if (dbtk_eval_truth(evl, tc.empty() ? nullptr : tc.data(), win.data())) die_assert(std::string("--eval: ") + dbtk_last_error());
+                if (!o.evalDumpTruth.empty()) {
+                    const uint64_t nk = tc.size();
+                    FILE* f = fopen(o.evalDumpTruth.c_str(), "wb");
+                    if (!f) die_assert("--eval-dump-truth: cannot create " + o.evalDumpTruth);
+                    const bool ok = fwrite(&nk, 8, 1, f) == 1 && (!nk || fwrite(tc.data(), 8, nk, f) == nk);
+                    if (fclose(f) != 0 || !ok) die_assert("--eval-dump-truth: writing " + o.evalDumpTruth + " failed");
+                }
+                double ems[2] = {0, 0};
+                uint64_t looked = 0, wsum = 0;
+                if (dbtk_eval_times(evl, ems, &looked)) die_assert(std::string("--eval: ") + dbtk_last_error());
+                for (uint64_t w : win) wsum += w;
+                fprintf(stderr, "--eval: %llu loci scored, %llu windows, %llu look-ups in %.3f ms of k_eval_truth (%.1f M/s), k_eval_sums %.3f ms (%.1f GB/s); "
+                        "handle made in %.3f s, truth passes %.3f s, scored and written in %.3f s\n", (unsigned long long)nloci,
+                        (unsigned long long)wsum, (unsigned long long)looked, ems[0], ems[0] > 0 ? looked / ems[0] / 1e3 : 0.0, ems[1], ems[1] > 0 ? 16.0 * counts.size() / ems[1] / 1e6 : 0.0,
+                        eval_make_s, eval_truth_s, te1 - te0);
+            }
             if (P.trackbait) {  // dumpBaitKmerHits, AQ.cpp:2652-2655
                 fprintf(stderr, "writing bait kmer hit statistics...\n");
                 for (int d = 1; d < nctx; ++d) if (dbtk_ctx_merge_bait_hits(ctx[0], ctx[d])) die_assert(dbtk_last_error());
@@ -2333,6 +2413,7 @@ int main(int argc, char* argv[]) {
         dbtk_dosage_free(kms);
         dbtk_kcp_fps_free(fps);
         dbtk_kcp_free(kcp);
+        dbtk_eval_free(evl);
         for (auto c : ctx) dbtk_ctx_free(c);
         dbtk_rpgg_free(rpgg);
     }

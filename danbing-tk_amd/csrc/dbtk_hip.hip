@@ -561,13 +561,15 @@ void drop_share(TableShare* sh) {
     for (void* p : ptrs) if (p) (void)hipFree(p);
     delete sh;
 }
-void release_share(dbtk_ctx* c) {
+void unref_share(TableShare* sh, uint64_t g_uid, int device) {
     std::lock_guard<std::mutex> l(g_share_m);
-    TableShare* sh = c->share;
     if (!sh || --sh->refs > 0) return;  // (no share: the context never got as far as the tables)
-    g_shares.erase(std::make_pair(c->g_uid, c->device));
+    g_shares.erase(std::make_pair(g_uid, device));
     drop_share(sh);
 }
+void release_share(dbtk_ctx* c) { unref_share(c->share, c->g_uid, c->device); }
+// a holder of a share that is not a context (dbtk_internal.h: tables_acquire)
+struct TablesRef { TableShare* sh; uint64_t g_uid; int device; };
 
 // A lane's stream and the buffers whose size is known when the context is made, zeroed on that stream (the others grow with the
 // batches: launch_batch).  Every lane of a context is made here, the first one included.
@@ -3075,6 +3077,38 @@ dbtk_status_t dbtk::ctx_facts(const dbtk_ctx_t* c, dbtk::CtxFacts* out) {
     out->unflushed_pairs = 0;
     for (const Lane& l : c->lanes) out->unflushed_pairs += l.m_pairs;
     return DBTK_OK;
+}
+
+// (dbtk_internal.h: for dbtk_eval_create)
+dbtk_status_t dbtk::tables_acquire(const dbtk_rpgg* g, int device, dbtk::ClsView* out, void** ref) {
+    if (!g || !out || !ref) { set_error("null argument"); return DBTK_ERR_ARG; }
+    *ref = nullptr;
+    HIPCHK(hipSetDevice(device));
+    std::lock_guard<std::mutex> lk(g_share_m);
+    const auto key = std::make_pair(g->uid, device);
+    const auto it = g_shares.find(key);
+    TableShare* sh = it != g_shares.end() ? it->second : nullptr;
+    if (!sh) {  // no context of this pair yet: the tables every context needs, for the contexts that follow as well
+        hipStream_t s = nullptr;
+        HIPCHK(hipStreamCreate(&s));
+        sh = new TableShare;
+        const dbtk_status_t st = build_tables(TableBuild{sh, g, s});
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+        if (st) { drop_share(sh); return st; }
+        g_shares[key] = sh;
+    }
+    ++sh->refs;
+    out->cls = sh->T.cls; out->mask = sh->T.cls_mask; out->shift = sh->T.cls_shift;
+    *ref = new TablesRef{sh, g->uid, device};
+    return DBTK_OK;
+}
+void dbtk::tables_release(void* ref) {
+    if (!ref) return;
+    TablesRef* r = static_cast<TablesRef*>(ref);
+    (void)hipSetDevice(r->device);
+    unref_share(r->sh, r->g_uid, r->device);
+    delete r;
 }
 
 // (dbtk_internal.h: for dbtk_sim_align)

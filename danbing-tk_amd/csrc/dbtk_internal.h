@@ -43,6 +43,7 @@ struct dbtk_rpgg {
     int idx_cache_mode = 0;           // 0: none; 1: load it when present and valid; 2: that, and write it after a build
 };
 
+struct dbtk_sim;
 namespace dbtk {
 void set_error(const std::string& msg);
 dbtk_status_t finish_rpgg(dbtk_rpgg* g);  // validation + output order
@@ -63,6 +64,20 @@ dbtk_status_t ctx_facts(const dbtk_ctx_t* c, CtxFacts* out);
 // dbtk_align_batch_device; sync = 1: as dbtk_ingest_align with sync = 1 (run to completion, records in pair order, no reads on the host).
 dbtk_status_t ctx_align_device(dbtk_ctx_t* c, int device, const uint8_t* d_seq, const uint64_t* d_off, uint64_t npairs, uint32_t max_read_len, int sync, void* ready,
                                void* done, dbtk_pair_rec_t* recs, uint64_t rec_cap, uint64_t* nrec);
+// ---- what the genotype score (dbtk_eval.hip) needs of the rest of the library
+// The class table of (g, device), shared with the contexts of that pair: built by whoever comes first, freed by whoever leaves last
+// (dbtk_hip.hip: the table shares).  *ref goes back to tables_release.
+struct ClsView { const void* cls; uint64_t mask; uint32_t shift; };
+dbtk_status_t tables_acquire(const dbtk_rpgg* g, int device, ClsView* out, void** ref);
+void tables_release(void* ref);
+// An attached sim handle (dbtk_sim.hip): where it lives, and its assembly group by group.  A span is one BED line clipped to its
+// contig, ctg[START, min(END, size)), as an offset into the group's arena.  sim_group_load makes group g the resident one, in the
+// order of the handle's stream (nothing is uploaded when it is resident already).
+struct SimSeam { int device; uint64_t nloci; uint32_t ngroups; void* stream; const uint8_t* d_arena; };
+struct SimSpan { uint64_t off, n; uint32_t locus; };
+dbtk_status_t sim_seam(dbtk_sim* s, SimSeam* out);
+dbtk_status_t sim_group_spans(const dbtk_sim* s, uint32_t g, std::vector<SimSpan>* out);
+dbtk_status_t sim_group_load(dbtk_sim* s, uint32_t g);
 }  // namespace dbtk
 
 #endif

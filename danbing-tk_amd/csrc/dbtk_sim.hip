@@ -142,8 +142,8 @@ __global__ void __launch_bounds__(256) k_sim_tile(const SimTile a) {
 
 constexpr uint64_t SIM_ARENA_DEFAULT = 1ull << 30;
 
-// a BED interval as the fragments see it: it covers those with beg in [from, to)
-struct SimIv { uint64_t from, to; uint32_t locus; };
+// a BED interval as the fragments see it: it covers those with beg in [from, to); beside it the line's own START and END
+struct SimIv { uint64_t from, to; uint32_t locus; uint64_t start, end; };
 
 struct HostContig {
     std::string header;          // the header line, '>' included
@@ -291,7 +291,7 @@ dbtk_status_t sim_open_impl(const char* fasta, const char* bed, uint32_t flen, u
         if (lc >= nloci) { set_error(where + "LOCUS " + std::to_string(lc) + " is not below the number of loci (" + std::to_string(nloci) + ")"); return DBTK_ERR_FORMAT; }
         const auto it = by_name.find(text.substr(b, f[1] - 1 - b));
         if (it == by_name.end()) continue;  // a contig that is absent or was skipped
-        for (uint32_t ci : it->second) ivs[ci].push_back(Iv{st + 1 > flen ? st + 1 - flen : 0, en, (uint32_t)lc});
+        for (uint32_t ci : it->second) ivs[ci].push_back(Iv{st + 1 > flen ? st + 1 - flen : 0, en, (uint32_t)lc, st, en});
     }
     // ---- the step functions: a sweep over the interval ends; a breakpoint wherever the lowest covering locus changes
     for (size_t ci = 0; ci < s->ctg.size(); ++ci) {
@@ -497,6 +497,19 @@ dbtk_status_t sim_take_times(dbtk_sim* s, bool all) {
     return DBTK_OK;
 }
 
+// group g's bases into the arena, in stream order behind the launches that read the group before it
+dbtk_status_t sim_make_resident(dbtk_sim* s, size_t g) {
+    if (s->resident == (int64_t)g) return DBTK_OK;
+    const uint32_t c0 = s->group_c0[g], c1 = s->group_c0[g + 1];
+    if (c0 == c1) return DBTK_OK;  // (an assembly without a kept contig)
+    const uint64_t b0 = s->ctg[c0].off, b1 = s->ctg[c1 - 1].off + s->ctg[c1 - 1].len;
+    if (b1 - b0 > s->arena_cap) { set_error("simulated reads: a contig group outgrew the arena"); return DBTK_ERR_HIP; }
+    if (b1 > b0) SCHK(hipMemcpyAsync(s->d_arena, s->bases.data() + b0, b1 - b0, hipMemcpyHostToDevice, s->stream));
+    s->resident = (int64_t)g;
+    s->bytes_uploaded += b1 - b0;
+    return DBTK_OK;
+}
+
 dbtk_status_t sim_batch_impl(dbtk_sim_t* s, uint64_t first, uint64_t npairs, void** d_seq, void** d_offsets, void** d_src, uint32_t* max_read_len) {
     if (!s) { set_error("dbtk_sim_batch: null argument"); return DBTK_ERR_ARG; }
     if (s->device < 0) { set_error("dbtk_sim_batch: dbtk_sim_attach first"); return DBTK_ERR_ARG; }
@@ -527,13 +540,7 @@ dbtk_status_t sim_batch_impl(dbtk_sim_t* s, uint64_t first, uint64_t npairs, voi
         const uint64_t gf0 = s->ctg[c0].first_frag, gf1 = c1 < s->ctg.size() ? s->ctg[c1].first_frag : s->nfrags;
         const uint64_t f0 = std::max(first, gf0), f1 = std::min(first + npairs, gf1);
         if (f0 < f1) {
-            if (s->resident != (int64_t)g) {
-                const uint64_t b0 = s->ctg[c0].off, b1 = s->ctg[c1 - 1].off + s->ctg[c1 - 1].len;
-                if (b1 - b0 > s->arena_cap) { set_error("simulated reads: a contig group outgrew the arena"); return DBTK_ERR_HIP; }
-                if (b1 > b0) SCHK(hipMemcpyAsync(s->d_arena, s->bases.data() + b0, b1 - b0, hipMemcpyHostToDevice, s->stream));
-                s->resident = (int64_t)g;
-                s->bytes_uploaded += b1 - b0;
-            }
+            if ((st = sim_make_resident(s, g))) return st;
             SimTile a;
             a.arena = s->d_arena; a.ctg = s->d_ctg; a.brk_pos = s->d_brk_pos; a.brk_src = s->d_brk_src;
             a.c0 = c0; a.c1 = c1; a.batch_first = first; a.q0 = f0 - first; a.q1 = f1 - first; a.npairs = npairs;
@@ -576,6 +583,33 @@ dbtk_status_t sim_align_impl(dbtk_sim_t* s, dbtk_ctx_t* ctx, int sync, dbtk_pair
 }
 
 }  // namespace
+
+// ---- dbtk_internal.h: for dbtk_eval_truth_sim
+dbtk_status_t dbtk::sim_seam(dbtk_sim* s, dbtk::SimSeam* out) {
+    if (!s || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
+    out->device = s->device; out->nloci = s->nloci; out->ngroups = s->group_c0.empty() ? 0 : (uint32_t)s->group_c0.size() - 1;
+    out->stream = (void*)s->stream; out->d_arena = s->d_arena;
+    return DBTK_OK;
+}
+dbtk_status_t dbtk::sim_group_spans(const dbtk_sim* s, uint32_t g, std::vector<dbtk::SimSpan>* out) {
+    if (!s || !out || (size_t)g + 1 >= s->group_c0.size()) { set_error("sim_group_spans: no such contig group"); return DBTK_ERR_ARG; }
+    out->clear();
+    for (uint32_t ci = s->group_c0[g]; ci < s->group_c0[g + 1]; ++ci) {
+        const HostContig& c = s->ctg[ci];
+        const uint64_t goff = c.off - s->ctg[s->group_c0[g]].off;  // (the group's contigs lie back to back, in `bases` as in the arena)
+        for (uint64_t i = c.iv0; i < c.iv1; ++i) {
+            const SimIv& v = s->ivs[i];
+            const uint64_t end = std::min(v.end, c.len);
+            if (v.start < end) out->push_back(dbtk::SimSpan{goff + v.start, end - v.start, v.locus});
+        }
+    }
+    return DBTK_OK;
+}
+dbtk_status_t dbtk::sim_group_load(dbtk_sim* s, uint32_t g) {
+    if (!s || s->device < 0 || (size_t)g + 1 >= s->group_c0.size()) { set_error("sim_group_load: an unattached handle or no such contig group"); return DBTK_ERR_ARG; }
+    SCHK(hipSetDevice(s->device));
+    return sim_make_resident(s, g);
+}
 
 extern "C" {
 
