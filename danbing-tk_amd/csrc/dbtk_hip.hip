@@ -107,10 +107,10 @@ template <int NS> __global__ void __launch_bounds__(64) __attribute__((amdgpu_wa
 #ifndef DBTK_P2_WPE
 #define DBTK_P2_WPE 4  // waves per SIMD its registers are budgeted for (its LDS allows 16 waves per CU)
 #endif
-template <int NPL, int WN, bool SEL = false, bool FUSE = false> __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DBTK_P2_WPE, 8))) k_probe(BatchArgs a) {
-    __shared__ Probe2SmemT<NPL> sm;
+template <int NPL, int WN, bool SEL, bool FUSE, bool CACHE> __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DBTK_P2_WPE, 8))) k_probe(BatchArgs a) {
+    __shared__ Probe2SmemT<NPL, CACHE> sm;
     DevX x{&sm};
-    body_probe2<NPL, WN, SEL, FUSE>(x, a);
+    body_probe2<NPL, WN, SEL, FUSE, CACHE>(x, a);
 }
 template <int NS, bool RECS, bool SEL = false> __global__ void __launch_bounds__(64) k_pair_usual(BatchArgs a) {
     __shared__ UsualSmem sm;
@@ -334,8 +334,10 @@ const Kern<WalkArgs, LocRunArgs> K_WALK_FAST_LOCUS[2][3] = {LOC_CLASSES(k_walk_f
 const Kern<WalkArgs, LocRunArgs> K_WALK_PAIRS_LOCUS[3] = {KERN(k_walk_pairs_locus<LOC_IMGB_XS>), KERN(k_walk_pairs_locus<LOC_IMGB_S>), KERN(k_walk_pairs_locus<LOC_IMGB_L>)};  // [class]
 #undef LOC_CLASSES
 #undef LOC_CLASSES_FUSED
-#define P2_FORMS(NPL, WN) {{KERN(k_probe<NPL, WN, false, false>), KERN(k_probe<NPL, WN, false, true>)}, {KERN(k_probe<NPL, WN, true, false>), KERN(k_probe<NPL, WN, true, true>)}}
-const Kern<BatchArgs> K_PROBE[4][2][2] = {P2_FORMS(3, 7), P2_FORMS(3, 11), P2_FORMS(5, 7), P2_FORMS(5, 11)};  // [vi][sel][fused], vi: NPL 3 | 5, windows of 7 | 11
+#define P2_FORMS(NPL, WN) {{KERN(k_probe<NPL, WN, false, false, true>), KERN(k_probe<NPL, WN, false, true, true>)}, {KERN(k_probe<NPL, WN, true, false, true>), KERN(k_probe<NPL, WN, true, true, true>)}, \
+                           {KERN(k_probe<NPL, WN, false, false, false>), KERN(k_probe<NPL, WN, false, true, false>)}}
+enum { P2_WHOLE, P2_SEL, P2_UNSORTED };  // the whole chunk of a list in locus order | what the locus path left of one | the whole chunk of a list that was not sorted (no cache of overflow look-ups)
+const Kern<BatchArgs> K_PROBE[4][3][2] = {P2_FORMS(3, 7), P2_FORMS(3, 11), P2_FORMS(5, 7), P2_FORMS(5, 11)};  // [vi][form][fused], vi: NPL 3 | 5, windows of 7 | 11
 #undef P2_FORMS
 const Kern<WalkArgs> K_WALK_FAST[2][2] = {{KERN(k_walk_fast<3, 7>), KERN(k_walk_fast<3, 11>)}, {KERN(k_walk_fast<5, 7>), KERN(k_walk_fast<5, 11>)}};  // [npl == 5][w11]
 // by nsi = 0 | 1 | 2: NS = 2 | 3 | 4 slots of 64 positions (and the kernel's flags)
@@ -1525,11 +1527,18 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
             lean_fused = fuse_lean && npl != 0 && (!a.sel || fuse);  // (pairs an UNFUSED locus-resident kernel took wait in their rows for the usual-pair kernel)
             if (npl) {
                 const int vi = (npl == 3 ? 0 : 2) + (wn == 7 ? 0 : 1);
+                // the wave's cache of overflow look-ups only where the sort ran: without it every pair of a wave's range is another locus
+                // (DBTK_P2_CACHE=0 / 1: never / always, for measurements and tests — the cache is never a matter of results; the list the
+                // locus path leaves is always one in locus order)
+                static const int cache_env = getenv("DBTK_P2_CACHE") ? atoi(getenv("DBTK_P2_CACHE")) : -1;
+                const bool cached = cache_env < 0 ? sort_hint : cache_env != 0;
+                const int form = a.sel ? P2_SEL : cached ? P2_WHOLE : P2_UNSORTED;
                 // blocks: eight rounds of the resident waves for a batch that leaves this kernel many pairs (see dbtk_ctx_create) — but a WGS-like
                 // batch has 100 000 survivors, three per block then, and what a block does once (its cache, its share of the counters, its entry in
                 // the general kernel's list) is then most of it (fused form, 10 M reads: 0.93 ms with 128 blocks per CU, 0.35 with 16).  So: whole
                 // rounds of the resident waves, ~32 pairs per block, by what the kernel took in the batch before (a hint, like the others: never
-                // a matter of results).
+                // a matter of results).  (Two and three rounds of shorter ranges for the form without the cache, which has less to do once per
+                // block, measured the same as one within the noise: DESIGN 4.2.)
                 const int wpc_max = (lean_fused ? c->probe2f_wpc : c->probe2_wpc)[vi];
                 int wpc = wpc_max;
                 static const bool wpc_forced = getenv("DBTK_PROBE_WPC") != nullptr;
@@ -1538,7 +1547,7 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
                     wpc = (int)(resident * std::min<uint64_t>(8, std::max<uint64_t>(1, ((uint64_t)surv_hint + per_round - 1) / per_round)));
                 }
                 const dim3 g2((uint32_t)c->num_cu * (uint32_t)wpc);
-                LAUNCH_K(K_PROBE[vi][a.sel != nullptr][lean_fused], g2, dim3(64), s, a);
+                LAUNCH_K(K_PROBE[vi][form][lean_fused], g2, dim3(64), s, a);
             }
             else LAUNCH_K(K_PROBE_GENERAL[nsi], gpr, dim3(64), s, a);
         }
@@ -1723,7 +1732,13 @@ static dbtk_status_t dbtk_ctx_create_impl(const dbtk_rpgg_t* h, const dbtk_param
                     // and a grid of EXACTLY the resident waves is a cliff: the query counts LDS in finer granules than the hardware
                     // allocates, and one block too many per CU runs alone in a second round at twice the time (measured with a 10.7-KB variant
                     // of this kernel: 15 per CU by the query, 14 in fact: 8.7 ms against 6.1).
-                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, K_PROBE[i][0][f].fn, 64, 0) != hipSuccess || nb <= 0) nb = 8;
+                    // (one figure for every form of a variant: the smaller of the form with the cache and the form without.  Both are held
+                    // to four waves per SIMD by their 128 VGPRs; the form without has the smaller LDS — 7 856 against 10 032 B —, so a grid
+                    // of the other's resident waves is never past its own: the cliff above cannot open under it.  The SEL forms share the
+                    // cached form's LDS.)
+                    int nbu = 0;
+                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, K_PROBE[i][P2_WHOLE][f].fn, 64, 0) != hipSuccess || nb <= 0) nb = 8;
+                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbu, K_PROBE[i][P2_UNSORTED][f].fn, 64, 0) == hipSuccess && nbu > 0 && nbu < nb) nb = nbu;
                     nb *= 8;
                     if (const char* ev = getenv("DBTK_PROBE_WPC")) { const int v = atoi(ev); if (v > 0) nb = v; }
                     (f ? c->probe2f_wpc : c->probe2_wpc)[i] = nb;

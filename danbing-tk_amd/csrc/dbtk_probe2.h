@@ -15,7 +15,8 @@
 //   * the keys a full bucket turned away (tandem repeats: many k-mers around few m-mers) are in the overflow table, one
 //     16-byte load per look-up — and the same few k-mers come back all along a repeat and in every read of its locus, so the
 //     wave keeps the results of its overflow look-ups in a small LDS cache: the survivor list is in locus order
-//     (body_surv_*, below) and a wave works through a CONTIGUOUS range of it, the reads of one locus one after the other;
+//     (body_surv_*, below) and a wave works through a CONTIGUOUS range of it, the reads of one locus one after the other
+//     (a list that was not sorted has its own instances without the cache: body_probe2's CACHE);
 //   * results: 4 bytes per position (`aux`), + 4 (`val`) for a read whose found k-mers are not all unique to one locus,
 //     transposed through LDS so that they leave as 16-byte stores; the per-read header (found positions, one index value or
 //     not) comes from three half-wave reductions.
@@ -43,8 +44,20 @@ struct P2FuseArgs {
                        // (thousands of blocks adding to ONE word serialize: 18 ns each)
     dbtk_params_t P;
 };
-template <int NPL>
-struct __attribute__((aligned(16))) Probe2SmemT {
+// CACHE (body_probe2): the wave's cache of overflow look-ups — part of the instances for lists in locus order only.
+// DBTK_P2_DEFAULT_CACHE: the form a driver that does not choose gets (the emulator's: tests/emu/emu_p2cache.cpp builds it a second time with
+// the cached form as the default, so that both forms run on the CPU; the device's launcher names the form of every instance)
+#ifndef DBTK_P2_DEFAULT_CACHE
+#define DBTK_P2_DEFAULT_CACHE false
+#endif
+template <bool CACHE>
+struct __attribute__((aligned(16))) P2CacheT {
+    uint4 cache[P2_CACHE];           // {k-mer, val, aux} of overflow look-ups already made (val = NOHIT: not in the index)
+    uint8_t tok[P2_CACHE];           // which lane writes an entry when several want to in one step
+};
+template <> struct P2CacheT<false> {};
+template <int NPL, bool CACHE = DBTK_P2_DEFAULT_CACHE>
+struct __attribute__((aligned(16))) Probe2SmemT : P2CacheT<CACHE> {
     uint32_t pk[2][20];              // 2-bit stream of each mate from its 4-byte-aligned start: 16 words (+ slack)
     uint16_t vd[2][40];              // validity bits of the same bases (only for a pair with a non-ACGT byte)
     uint32_t rb[64 * NPL];           // bucket of every run of the pair
@@ -52,8 +65,6 @@ struct __attribute__((aligned(16))) Probe2SmemT {
         uint4 stg[P2_RCH][P2_ROW];                                      // the buckets of a chunk of runs
         uint32_t res[2][2][32 * NPL];                                   // [mate][aux | val][position]: results on their way to 16-byte stores
     };
-    uint4 cache[P2_CACHE];           // {k-mer, val, aux} of overflow look-ups already made (val = NOHIT: not in the index)
-    uint8_t tok[P2_CACHE];           // which lane writes an entry when several want to in one step
     uint32_t gbuf[64];               // (FUSE) pairs for the general resolve kernel, not yet appended to its list
     uint32_t fc[12];                 // (FUSE) this wave's sums for the counters (kept here, not in scalar registers: the kernel has none to spare)
     P2FuseArgs fa;                   // (FUSE)
@@ -340,9 +351,14 @@ DBTK_HD_NOINLINE bool p2_resolve_shared(X& x, SM& sm_, P2Rv<NPL> rv, uint32_t nk
 // (assign_halves, dbtk_assign.h: the lanes hold the positions' states already) and the count increments; and the pair kfilter removes
 // altogether): such a pair writes no hit rows and no second kernel reads them.  Every other pair writes its rows as before and goes on
 // the general resolve kernel's list.  The launcher's conditions are body_pair_usual's: consistent RPGG, no records, no trace / -b / -bu.
-template <int NPL, int WN, bool SEL, bool FUSE, class X>
+// CACHE: the wave keeps the results of its overflow look-ups in LDS (the header of this file) — for a list in locus order.  A list that was
+// not sorted (a WGS-like batch: every pair of a wave's range another locus, a hit would be chance) goes without: no entries to set up, and per
+// pair no cache reads, no token round, no insert and none of their two syncs; pending keys go straight to
+// the overflow table, and the wave's LDS is 2 176 bytes smaller.  Never a matter of results.  (A kernel instance, not a wave-uniform
+// argument: with the argument the CACHED path of a WGS-like step measured 0.362 against 0.355 ms — DESIGN 4.2.)
+template <int NPL, int WN, bool SEL, bool FUSE, bool CACHE = DBTK_P2_DEFAULT_CACHE, class X>
 DBTK_HD void body_probe2(X& x, const BatchArgs& a) {
-    typedef Probe2SmemT<NPL> SM;
+    typedef Probe2SmemT<NPL, CACHE> SM;
     SM& sm = *x.template smem<SM>();
     const int lane = x.lane();
     const uint32_t hl = (uint32_t)lane & 31u, half = (uint32_t)lane >> 5;
@@ -380,7 +396,8 @@ DBTK_HD void body_probe2(X& x, const BatchArgs& a) {
         x.sync();
         ngb = 0;
     };
-    for (uint32_t e = (uint32_t)lane; e < (uint32_t)P2_CACHE; e += 64) sm.cache[e] = uint4{0xFFFFFFFFu, 0x3FFFFFFFu, 0u, 0u};  // MZ_EMPTY
+    if constexpr (CACHE)
+        for (uint32_t e = (uint32_t)lane; e < (uint32_t)P2_CACHE; e += 64) sm.cache[e] = uint4{0xFFFFFFFFu, 0x3FFFFFFFu, 0u, 0u};  // MZ_EMPTY
     // Three-deep fetch pipeline, all loads unconditional (clamped to something valid) so that they stay in flight:
     // while pair i is looked up, the bytes of pair i + 1 are on their way into registers, the offsets of pair i + 2
     // are being fetched, and the survivor entry of pair i + 3.
@@ -541,23 +558,32 @@ DBTK_HD void body_probe2(X& x, const BatchArgs& a) {
             if (a.P.diag & 256) anyp = false;  // diagnostic: no level-2 look-ups (wrong results)
 #endif
             if (x.ballot(anyp)) {
-                // the wave's cache first: the overflow keys are those of tandem repeats, and they come back
+                // the wave's cache first (a list in locus order): the overflow keys are those of tandem repeats, and they come back
                 uint32_t oh[NPL], oi[NPL];
                 bool glob[NPL];
-                anyp = false;
+                if constexpr (CACHE) {
+                    anyp = false;
 #pragma unroll
-                for (int j = 0; j < NPL; ++j) {
-                    oh[j] = ovf_hash(km[j]);
-                    oi[j] = oh[j] & (uint32_t)T.ovf_mask;
-                    glob[j] = false;
-                    if (pend[j]) {
-                        const uint4 c = sm.cache[(oh[j] >> 20) & (P2_CACHE - 1)];
-                        if (c.x == (uint32_t)km[j] && c.y == (uint32_t)(km[j] >> 32)) { rv[j] = ((uint64_t)c.w << 32) | c.z; pend[j] = false; }
-                        else glob[j] = true;
+                    for (int j = 0; j < NPL; ++j) {
+                        oh[j] = ovf_hash(km[j]);
+                        oi[j] = oh[j] & (uint32_t)T.ovf_mask;
+                        glob[j] = false;
+                        if (pend[j]) {
+                            const uint4 c = sm.cache[(oh[j] >> 20) & (P2_CACHE - 1)];
+                            if (c.x == (uint32_t)km[j] && c.y == (uint32_t)(km[j] >> 32)) { rv[j] = ((uint64_t)c.w << 32) | c.z; pend[j] = false; }
+                            else glob[j] = true;
+                        }
+                        anyp |= pend[j];
                     }
-                    anyp |= pend[j];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < NPL; ++j) {
+                        oh[j] = 0;
+                        oi[j] = pend[j] ? ovf_hash(km[j]) & (uint32_t)T.ovf_mask : 0u;
+                        glob[j] = false;
+                    }
                 }
-                if (x.ballot(anyp)) {
+                if (!CACHE || x.ballot(anyp)) {
                     // (the table is at most a sixteenth full: a look-up that needs a second slot, and with it a second round trip, is one in thirty)
                     uint4 q2[NPL];
                     do {
@@ -574,18 +600,20 @@ DBTK_HD void body_probe2(X& x, const BatchArgs& a) {
                             anyp |= pend[j];
                         }
                     } while (x.ballot(anyp));
-                    // what was looked up goes into the cache (the absent ones too); of the lanes that want one entry in this
-                    // step, the one whose token is left standing writes it
+                    if constexpr (CACHE) {
+                        // what was looked up goes into the cache (the absent ones too); of the lanes that want one entry in this
+                        // step, the one whose token is left standing writes it
 #pragma unroll
-                    for (int j = 0; j < NPL; ++j) if (glob[j]) sm.tok[(oh[j] >> 20) & (P2_CACHE - 1)] = (uint8_t)lane;
-                    x.sync();
+                        for (int j = 0; j < NPL; ++j) if (glob[j]) sm.tok[(oh[j] >> 20) & (P2_CACHE - 1)] = (uint8_t)lane;
+                        x.sync();
 #pragma unroll
-                    for (int j = 0; j < NPL; ++j) {  // (two of a lane's own positions on one entry: both pass, the later write stands)
-                        const uint32_t ce = (oh[j] >> 20) & (P2_CACHE - 1);
-                        if (glob[j] && sm.tok[ce] == (uint8_t)lane)
-                            sm.cache[ce] = uint4{(uint32_t)km[j], (uint32_t)(km[j] >> 32), (uint32_t)rv[j], (uint32_t)(rv[j] >> 32)};
+                        for (int j = 0; j < NPL; ++j) {  // (two of a lane's own positions on one entry: both pass, the later write stands)
+                            const uint32_t ce = (oh[j] >> 20) & (P2_CACHE - 1);
+                            if (glob[j] && sm.tok[ce] == (uint8_t)lane)
+                                sm.cache[ce] = uint4{(uint32_t)km[j], (uint32_t)(km[j] >> 32), (uint32_t)rv[j], (uint32_t)(rv[j] >> 32)};
+                        }
+                        x.sync();
                     }
-                    x.sync();
                 }
             }
             DBTK_STAMP(41);  // level 2
