@@ -30,6 +30,7 @@
 #include "dbtk_kernels.h"
 #include "dbtk_ingest.h"
 #include "dbtk_gz.h"
+#include "dbtk_slices.h"
 
 using namespace dbtk;
 
@@ -493,6 +494,19 @@ struct dbtk_ctx {
     std::vector<Lane> lanes;
     size_t cur = 0;
     Lane& lane() { return lanes[cur]; }
+    // `ring` lanes (DBTK_LANES) take turns; a one-lane context that slices a batch (dbtk_align_batch_device) makes itself a second
+    // lane for the slices alone, behind the ring: every loop over `lanes` covers it, no other entry point ever stands on it
+    size_t ring = 1;
+    // Slices of large device batches (dbtk_slices.h).  slice_pairs: DBTK_SLICE_PAIRS or the default, 0 = never; slice_forced: set by
+    // the environment, so batches are cut whatever the hint words say.  `sliced`: the batches before looked WGS-like and were cut.
+    // Whole launches report to the hint words [0 .. 7], slices to [8 .. 15] (a slice reports its own survivors: 1/S of a batch's), and
+    // each kind reads what its own kind wrote; *_hint_pairs = pairs of the last launch that reports to those words.
+    uint64_t slice_pairs = 0;
+    bool slice_forced = false, sliced = false;
+    uint64_t whole_hint_pairs = 0, slice_hint_pairs = 0;
+    size_t slice_turn = 0;        // one-lane context: the lane the last slice went to (0 | 1), kept from batch to batch
+    bool timed_last = false;      // the device batch before had event records round its kernels
+    uint64_t enqueued = 0;        // batches that got as far as their first enqueue (launch_batch)
     DevTables T;                  // the share's tables as the kernels get them (a copy of share->T, taken once the optional tables are in)
     // device allocations
     int wfl_blocks[6] = {0, 0, 0, 0, 0, 0};  // workgroups of k_walk_fast_locus<3 | 5, class 0 | 1 | 2>
@@ -1207,13 +1221,13 @@ void fold_timer(Timed& t) {
     }
     t.used = 0;
 }
-void switch_lane(dbtk_ctx* c) { c->cur = (c->cur + 1) % c->lanes.size(); }
+void switch_lane(dbtk_ctx* c) { c->cur = (c->cur + 1) % c->ring; }
 // Every reader of the accumulators comes through here (counts, the all-reduce, reset, the caller of dbtk_ctx_accum_buffer after
 // dbtk_ctx_synchronize): the counter replicas are folded into the counters once, now, instead of at the end of every batch (a launch of
 // one wave + its gap: 14 us of a 1.2-ms step).
 hipError_t sync_all(dbtk_ctx* c) {
     hipError_t e = hipSuccess;
-    for (Lane& l : c->lanes) if (e == hipSuccess) e = hipStreamSynchronize(l.stream);
+    for (Lane& l : c->lanes) if (e == hipSuccess && l.stream) e = hipStreamSynchronize(l.stream);
     if (e == hipSuccess && c->fold_pending && c->d_ctr && c->d_accum) {
         hipStream_t s = c->lane().stream;
         hipLaunchKernelGGL(k_fold_counters, dim3(1), dim3(64), 0, s, c->d_accum + c->ntr + 2 * (uint64_t)c->g->nloci, c->d_ctr, c->d_pstats);
@@ -1305,10 +1319,18 @@ dbtk_status_t bub_before_batch(dbtk_ctx* c) {
 // ceil(npairs / SURV_CAP) chunk iterations are enqueued and the kernels of a chunk past the end
 // of the list exit at once; nothing waits for the host.
 constexpr uint64_t SURV_CAP = 1ull << 23;  // at most 51 GB of hit buffers at 150 bp (allocated for the batch size actually seen): one chunk for batches of up to 8 M pairs
+// `timed`: event records round this batch's kernels (-1: decided here, every timers_every-th batch; dbtk_align_batch_device decides
+// once per call, for all slices).  `hint_set`: which of the pinned hint words the batch reads and reports to — a whole batch's, a
+// slice's, or (a batch's shorter last slice, whose survivors would be scaled by the wrong size) read a slice's and report nothing.
+enum { HINT_WHOLE = 0, HINT_SLICE = 1, HINT_SLICE_MUTE = 2 };
+constexpr int HINT_SLICE_AT = 8;  // (words of the 16 pinned ones)
+constexpr uint64_t SLICE_PAIRS_DEFAULT = 1ull << 19;  // fewest pairs of a slice of a large device batch (DBTK_SLICE_PAIRS; of 2^19, 2^20, 2^21 the smallest, and still a gain: DESIGN 4.2)
+bool next_batch_timed(dbtk_ctx* c) { return c->timers_on && (c->batch_no++ % c->timers_every) == 0; }
 
 dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_off, uint64_t seq_len, uint64_t npairs,
                            uint32_t max_read_len, dbtk_pair_rec_t* d_recs, uint32_t rec_cap, const uint8_t* d_qual = nullptr,
-                           dbtk_thread_rec_t* walk_trecs = nullptr, bool walk_aln = false, bool walk_txt = false) {
+                           dbtk_thread_rec_t* walk_trecs = nullptr, bool walk_aln = false, bool walk_txt = false,
+                           int timed = -1, int hint_set = HINT_WHOLE) {
     Lane& L = c->lane();
     hipStream_t s = L.stream;
     if (npairs >= 0xFFFFFFFFull) { set_error("batch too large (pair index is 32-bit)"); return DBTK_ERR_ARG; }
@@ -1357,6 +1379,7 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
         HIPCHK(hipMemsetAsync(L.d_walk.p, 0xFF, npairs * sizeof(uint32_t), s));  // NAN32: the pair does not reach threading
         HIPCHK(hipMemsetAsync(L.d_walk.p + npairs, 0, npairs * sizeof(uint32_t), s));  // walk_ret: no pair is marked WALK_PENDING
     }
+    ++c->enqueued;  // (a counting context has all its scratch by now: a batch that fails before this line has put nothing on the stream)
     // nsurv, novf, nrec; the error word (3) stays until it has been reported
     if (tk_inline) HIPCHK(hipMemsetAsync(tickets, 0, (2 * (nchunks + 1) + 3) * sizeof(uint32_t), s));
     else {
@@ -1385,7 +1408,10 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
     a.counters = a.nmapread + c->g->nloci;
     a.ctr_rep = c->d_ctr;
     a.pstats = c->d_pstats;
-    a.sortflag = L.d_small + 6; a.hint_out = c->h_sortflag;
+    uint32_t* const hint_in = c->h_sortflag ? c->h_sortflag + (hint_set == HINT_WHOLE ? 0 : HINT_SLICE_AT) : nullptr;
+    a.sortflag = L.d_small + 6; a.hint_out = hint_set == HINT_SLICE_MUTE ? nullptr : hint_in;
+    if (hint_set == HINT_WHOLE) c->whole_hint_pairs = npairs;
+    else if (hint_set == HINT_SLICE) c->slice_hint_pairs = npairs;
     a.recs = d_recs; a.rec_cap = rec_cap;
     a.vote_scratch = L.d_vote; a.vote_epoch = L.d_epoch; a.vote_rows = (uint32_t)c->vote_rows;
     a.vote_busy = reinterpret_cast<uint64_t*>(L.d_epoch + ((c->vote_rows + 1) & ~1));  // (behind the epochs, 8-byte aligned)
@@ -1408,7 +1434,7 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
 #endif
     const uint64_t ntiles = (npairs + K1_TP - 1) / K1_TP;
     int e = 0;
-    const bool tm = c->timers_on && (c->batch_no++ % c->timers_every) == 0;
+    const bool tm = timed < 0 ? next_batch_timed(c) : timed != 0;
     auto rec_beg = [&](int kslot) -> dbtk_status_t { if (!tm) return DBTK_OK; dbtk_status_t r = timed_slot(c, kslot, &e); if (r) return r; HIPCHK(hipEventRecord(c->timed[kslot].beg[e], s)); return DBTK_OK; };
     auto rec_end = [&](int kslot) -> dbtk_status_t { if (tm) HIPCHK(hipEventRecord(c->timed[kslot].end[e], s)); return DBTK_OK; };
     // The survivor list in locus order (dbtk_probe2.h: body_surv_*): what every later kernel indexes.  A batch with few survivors per locus (a
@@ -1417,8 +1443,8 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
     // step).  A hint like the one below: the order of the list is never a matter of results.
     bool sort_hint = true, locus_hint = true;
     uint32_t surv_hint = 0xFFFFFFFFu;  // pairs the lean probe kernel took in the batch before (no hint: "many")
-    if (c->h_sortflag) {  // (both hints from ONE reading of the pinned words: the copy of the batch before may land at any time)
-        volatile uint32_t* hh = c->h_sortflag;
+    if (hint_in) {  // (both hints from ONE reading of the pinned words: the copy of the batch before may land at any time)
+        volatile uint32_t* hh = hint_in;
         const uint32_t prev_surv = hh[0], prev_flag = hh[6];
         surv_hint = hh[1];  // (pairs the lean probe kernel took)
         sort_hint = prev_flag != 0 || 2 * (uint64_t)prev_surv >= (uint64_t)SORT_MIN_PER_LOCUS * nloci;
@@ -1435,7 +1461,7 @@ dbtk_status_t launch_batch(dbtk_ctx* c, const uint8_t* d_seq, const uint64_t* d_
     {   // (lazy sampling when more than half of the batch before passed subfilter — a hint like the others; DBTK_K1_LAZY=0 / 1: never / always)
         static const int lazy_env = getenv("DBTK_K1_LAZY") ? atoi(getenv("DBTK_K1_LAZY")) : -1;
         bool lazy = lazy_env == 1;
-        if (lazy_env < 0 && c->h_sortflag) { const uint32_t prev_surv = ((volatile uint32_t*)c->h_sortflag)[0]; lazy = prev_surv != 0xFFFFFFFFu && 2 * (uint64_t)prev_surv >= npairs; }
+        if (lazy_env < 0 && hint_in) { const uint32_t prev_surv = ((volatile uint32_t*)hint_in)[0]; lazy = prev_surv != 0xFFFFFFFFu && 2 * (uint64_t)prev_surv >= npairs; }
         k1_lazy = lazy;
     }
     if ((st = rec_beg(0))) return st;
@@ -1784,12 +1810,21 @@ static dbtk_status_t dbtk_ctx_create_impl(const dbtk_rpgg_t* h, const dbtk_param
             if (p->bubbles == 1) nlanes = 1;  // (the device table takes inserts from every lane: atomics)
         }
 #endif
-        c->lanes.reserve(nlanes);
+        c->lanes.reserve(nlanes + 1);
         for (int li = 0; li < nlanes && !st; ++li) {
             c->lanes.emplace_back();
             st = lane_create(c, c->lanes.back());
         }
         if (st) break;
+        c->ring = (size_t)nlanes;
+#ifndef DBTK_STAMPS
+        {   // DBTK_SLICE_PAIRS: pairs per slice of a large device batch (dbtk_align_batch_device).  0: never; N: batches of two slices
+            // and more are cut whatever the hint words say; unset: SLICE_PAIRS_DEFAULT, for batches the hint words call WGS-like
+            const char* e = getenv("DBTK_SLICE_PAIRS");
+            c->slice_forced = e && atoll(e) > 0;
+            c->slice_pairs = e ? (uint64_t)std::max<long long>(atoll(e), 0) : SLICE_PAIRS_DEFAULT;
+        }
+#endif
         c->timed[0].name = "k_encode_subfilter";
         c->timed[1].name = "k_probe";
         c->timed[2].name = "k_pair_usual";
@@ -1849,7 +1884,8 @@ static dbtk_status_t dbtk_ctx_create_impl(const dbtk_rpgg_t* h, const dbtk_param
         if (!st) chk(hipMemsetAsync(c->d_pstats, 0, DBTK_PATH_STATS * 8, c->lane().stream), "memset");
         if (!getenv("DBTK_LOCUS_ALWAYS")) {  // (DBTK_LOCUS_ALWAYS=1: every batch launches the locus path: tests of small batches)
             chk(hipHostMalloc((void**)&c->h_sortflag, 64, hipHostMallocDefault), "hipHostMalloc");
-            if (c->h_sortflag) { c->h_sortflag[0] = 0xFFFFFFFFu; c->h_sortflag[1] = 0xFFFFFFFFu; c->h_sortflag[6] = 1u; }
+            if (c->h_sortflag)
+                for (int w = 0; w <= HINT_SLICE_AT; w += HINT_SLICE_AT) { c->h_sortflag[w] = 0xFFFFFFFFu; c->h_sortflag[w + 1] = 0xFFFFFFFFu; c->h_sortflag[w + 6] = 1u; }
         }
         if (st) break;
         chk(hipMemsetAsync(c->d_accum, 0, c->n_accum * 8, c->lane().stream), "memset");
@@ -2175,6 +2211,51 @@ static dbtk_status_t dbtk_ctx_aln_text_impl(dbtk_ctx_t* c, uint32_t* idx, uint64
     return DBTK_OK;
 }
 
+// Is this device batch one to cut into slices (dbtk_slices.h)?  Only in a context that does nothing but count — no walk, no -bu, no
+// trace, no bait: where launch_batch fuses the lean probe kernel — and, unless DBTK_SLICE_PAIRS forces it, only while the hint words
+// call the batches WGS-like: list not sorted, fewer survivors than a sorted list has, encode stage not lazy.  A slice reports its
+// own survivors, so they are scaled to this batch's pairs before they meet the thresholds of a batch: a context whose batches turn
+// dense goes back to whole ones, and one whose whole batches are sorted or take the locus path never leaves them.  A hint like the
+// others: never a matter of results.
+//   Without DBTK_SLICE_PAIRS a batch is cut in two at the most, one slice per stream, and only on a ring of one lane.  Measured (DESIGN
+// 4.2): every launch of the probe and resolve kernels has a floor of its own — k_pair takes 70 us for 20 000 survivors as for
+// 100 000 — and a stream runs its slices' kernels one after the other, so 5 M pairs in five slices are slower than whole (1.16 ms
+// against 1.045) and in two halves faster (0.98); and a ring of two or three lanes overlaps successive whole batches already, which
+// beats any slices (0.93 ms whole on two lanes).  DBTK_SLICE_PAIRS is then the smallest slice worth a launch: a batch of twice as
+// many pairs is cut.
+static uint64_t slice_cap(const dbtk_ctx_t* c) { return c->slice_forced ? dbtk_slices::MAX_SLICES : 2; }
+// Back to whole batches, and to "no hint" until one of them has reported (a stale "WGS-like" must not send the context straight back).
+// for_good: the context never slices again (what its slices need could not be had).
+static void slices_off(dbtk_ctx_t* c, bool for_good) {
+    if (c->h_sortflag) { volatile uint32_t* hw = c->h_sortflag; hw[0] = dbtk_slices::NO_HINT; hw[1] = dbtk_slices::NO_HINT; hw[6] = 1u; }
+    c->sliced = false;
+    if (for_good) { c->slice_pairs = 0; c->slice_forced = false; }
+}
+static dbtk_status_t wants_slices(dbtk_ctx_t* c, uint64_t npairs, bool* cut) {
+    *cut = false;
+    if (!c->slice_pairs || !dbtk_slices::slice_size(npairs, c->slice_pairs, slice_cap(c))) return DBTK_OK;
+    if (c->P.threading == DBTK_THREADING_V13 || c->P.bubbles || c->P.trace || c->P.bait || !c->T.consistent) return DBTK_OK;
+    if (c->slice_forced) { *cut = true; return DBTK_OK; }
+    if (!c->h_sortflag || c->ring > 1) return DBTK_OK;  // (no hint words = DBTK_LOCUS_ALWAYS: every batch sorted, every batch through the locus path)
+    // (the first large batch of such a context is waited for, once, so that the second is cut or not by what the first was — and not
+    // the tenth, whenever the words happen to land: a caller's warm-up then covers the slices' lane and scratch too)
+    if (!c->sliced && c->whole_hint_pairs && ((volatile uint32_t*)c->h_sortflag)[0] == dbtk_slices::NO_HINT) HIPCHK(hipStreamSynchronize(c->lanes[0].stream));
+    volatile uint32_t* hh = c->h_sortflag + (c->sliced ? HINT_SLICE_AT : 0);
+    const dbtk_slices::Hint h{hh[0], hh[1], hh[6]};
+    const uint64_t of = c->sliced ? c->slice_hint_pairs : c->whole_hint_pairs;
+    bool reseed = false, forget = false;
+    *cut = dbtk_slices::decide(c->sliced, h, of, npairs, c->g->nloci, SORT_MIN_PER_LOCUS, &reseed, &forget);
+    if (reseed) {  // the first slices' hints: the whole batch's, scaled down
+        const uint64_t sz = dbtk_slices::slice_size(npairs, c->slice_pairs, slice_cap(c));
+        const dbtk_slices::Hint s = dbtk_slices::seed_slice_hint(h, of, sz);
+        volatile uint32_t* hs = c->h_sortflag + HINT_SLICE_AT;
+        hs[0] = s.surv; hs[1] = s.took; hs[6] = s.flag;
+        c->slice_hint_pairs = sz;
+        c->sliced = true;
+    } else if (forget) slices_off(c, false);
+    return DBTK_OK;
+}
+
 dbtk_status_t dbtk_align_batch_device(dbtk_ctx_t* c, const void* d_seq, const void* d_offsets, uint64_t npairs,
                                       uint32_t max_read_len) {
     if (!c || !d_seq || !d_offsets) { set_error("null argument"); return DBTK_ERR_ARG; }
@@ -2183,8 +2264,54 @@ dbtk_status_t dbtk_align_batch_device(dbtk_ctx_t* c, const void* d_seq, const vo
     HIPCHK(hipSetDevice(c->device));
     // d_seq is 16-byte aligned and device allocations are page-granular, so the aligned 16-byte
     // chunk holding the last base is always readable: no byte-wise tail needed (seq_len = max).
-    if (c->lanes.size() > 1) switch_lane(c);  // successive batches alternate between the two streams
-    return launch_batch(c, (const uint8_t*)d_seq, (const uint64_t*)d_offsets, ~0ull, npairs, max_read_len, nullptr, 0);
+    auto whole = [&](int timed) {
+        if (c->ring > 1) switch_lane(c);  // successive batches alternate between the two streams
+        return launch_batch(c, (const uint8_t*)d_seq, (const uint64_t*)d_offsets, ~0ull, npairs, max_read_len, nullptr, 0, nullptr, nullptr, false, false, timed);
+    };
+    if (npairs == 0 || npairs >= 0xFFFFFFFFull) return whole(-1);  // (nothing to do, or refused: neither counts as a batch for the timers' every-n-th)
+    const bool tm = next_batch_timed(c);  // (once per call: a batch with event records round its kernels runs whole, so their times stay a batch's)
+    bool cut = false;
+    if (!tm) { const dbtk_status_t ws = wants_slices(c, npairs, &cut); if (ws) return ws; }
+    uint64_t sz = cut ? dbtk_slices::slice_size(npairs, c->slice_pairs, slice_cap(c)) : 0;
+    // In slices: each one the complete batch it is (offsets are absolute, the encode kernel takes its readable length from the slice's
+    // last offset), on the lane after the one the slice before went to, so slice i + 1's encode kernel runs beside slice i's probe
+    // and resolve kernels.  Nothing orders two slices but their streams; all they share they add to atomically.
+    if (sz && c->ring == 1 && c->lanes.size() == 1) {  // a one-lane context's second lane, for slices alone
+        c->lanes.emplace_back();
+        if (lane_create(c, c->lanes.back()) != DBTK_OK) {  // (no room for it: slicing is a hint, the batch runs whole and the context stays whole)
+            (void)hipGetLastError();
+            lane_free(c->lanes.back()); c->lanes.pop_back();
+            slices_off(c, true);
+            sz = 0;
+        }
+    }
+    if (sz && c->ring == 1 && !c->lanes[1].stream && hipStreamCreate(&c->lanes[1].stream) != hipSuccess) {  // (given back by sync_all)
+        (void)hipGetLastError();
+        c->lanes[1].stream = nullptr;
+        slices_off(c, true);
+        sz = 0;
+    }
+    // (a one-lane context that has sliced: a timed batch must not run beside a slice on the other stream — its kernels' times would be
+    // two kernels' — so the host waits for the slices before it, and for it before the slices after it)
+    if (c->ring == 1 && c->lanes.size() > 1 && (tm || (sz && c->timed_last)) && c->lanes[tm ? 1 : 0].stream) HIPCHK(hipStreamSynchronize(c->lanes[tm ? 1 : 0].stream));
+    c->timed_last = tm;
+    if (!sz) return whole(tm);
+    dbtk_status_t st = DBTK_OK;
+    const uint64_t enq0 = c->enqueued;
+    for (const dbtk_slices::Slice& sl : dbtk_slices::plan(npairs, c->slice_pairs, slice_cap(c))) {
+        if (c->ring > 1) switch_lane(c);
+        else c->cur = c->slice_turn = c->slice_turn ^ 1;
+        st = launch_batch(c, (const uint8_t*)d_seq, (const uint64_t*)d_offsets + 2 * sl.p0, ~0ull, sl.n, max_read_len, nullptr, 0, nullptr, nullptr, false, false,
+                          0, sl.n == sz ? HINT_SLICE : HINT_SLICE_MUTE);
+        if (st) break;
+    }
+    if (c->ring == 1) c->cur = 0;  // (every other entry point of a one-lane context stands on lane 0)
+    if (st && c->enqueued == enq0) {  // the first slice found no room for its scratch and nothing is on a stream yet: whole, from now on
+        (void)hipGetLastError();
+        slices_off(c, true);
+        return whole(0);
+    }
+    return st;
 }
 
 // The sticky error words of all lanes (a read longer than promised was truncated on the device: the accumulators are
@@ -2795,7 +2922,7 @@ static dbtk_status_t dbtk_ingest_align_impl(dbtk_ingest_t* g, uint32_t slot, dbt
     HIPCHK(hipSetDevice(c->device));
     if (sync) return run_batch_sync(c, S.d_flat, S.d_off, S.d_qual, ~0ull, h.nkept, (uint32_t)h.maxlen, nullptr, nullptr, nullptr, recs, rec_cap, nrec);
     if (c->P.bubbles == 1) { set_error("dbtk_ingest_align: -bu is replayed batch by batch on the host: sync = 1"); return DBTK_ERR_ARG; }
-    if (c->lanes.size() > 1) switch_lane(c);
+    if (c->ring > 1) switch_lane(c);
     const dbtk_status_t st = launch_batch(c, S.d_flat, S.d_off, ~0ull, h.nkept, (uint32_t)h.maxlen, nullptr, 0, S.d_qual);
     if (st) return st;
     HIPCHK(hipEventRecord(S.aligned, c->lane().stream));
@@ -2873,7 +3000,7 @@ static dbtk_status_t dbtk_ingest_align_merged_impl(dbtk_ingest_t* g, uint32_t sl
         if (st) return st;
         L.m_bytes = 0; L.m_pairs = 0; L.m_maxlen = 0;
         // (the next blocks are merged into the OTHER lane's buffers, on its stream: this lane's kernels are reading these)
-        if (c->lanes.size() > 1) switch_lane(c);
+        if (c->ring > 1) switch_lane(c);
     }
     return DBTK_OK;
 }
@@ -3136,7 +3263,7 @@ dbtk_status_t dbtk::ctx_align_device(dbtk_ctx_t* c, int device, const uint8_t* d
     HIPCHK(hipSetDevice(c->device));
     if (!sync) {
         if (c->P.bubbles == 1) { set_error("-bu is replayed batch by batch on the host: sync = 1"); return DBTK_ERR_ARG; }
-        if (c->lanes.size() > 1) switch_lane(c);
+        if (c->ring > 1) switch_lane(c);
     }
     if (ready) HIPCHK(hipStreamWaitEvent(c->lane().stream, (hipEvent_t)ready, 0));
     const dbtk_status_t st = sync ? run_batch_sync(c, d_seq, d_off, nullptr, ~0ull, npairs, max_read_len, nullptr, nullptr, nullptr, recs, rec_cap, nrec)

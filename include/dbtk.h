@@ -308,7 +308,25 @@ dbtk_status_t dbtk_ctx_aln_text(dbtk_ctx_t* ctx, uint32_t* idx, uint64_t idx_cap
  * d_seq must be 16-byte aligned and readable up to the end of the last read
  * rounded up to a multiple of 16 (any hipMalloc'd buffer is).  Asynchronous on
  * the context's streams (successive batches go round DBTK_LANES of them);
- * records are not produced.  A read longer than max_read_len (or than
+ * records are not produced.  A large batch may be enqueued in slices of whole
+ * pairs, each the complete batch it is, on alternating streams, so that one
+ * slice's encode kernel runs beside the other's probe and resolve kernels
+ * (DBTK_SLICE_PAIRS): only in a context that does nothing but
+ * count (no threading, -bu, trace or bait), only a batch without kernel timers
+ * (dbtk_ctx_timers_enable: a timed batch runs whole) and, unless the
+ * environment forces it, only on one lane while the batches before were
+ * WGS-like; a one-lane context then makes itself a second stream and its
+ * scratch at its first such batch (no room for either: the batch runs whole
+ * and the context never slices again — slicing is a hint, it never turns a
+ * batch that would have run into an error).  Results are the same bit for bit.
+ * The call blocks the host in two places, both on a one-lane context with
+ * slicing on, both reporting a failed stream as DBTK_ERR_HIP: once per
+ * context, its second large batch waits for the first, so that what the first
+ * was decides (a caller's warm-up then covers the second stream and its
+ * scratch); and once such a context has sliced, a batch with kernel timers
+ * waits for the slices before it and is waited for by the slices after it, so
+ * that the times recorded are one kernel's.  With DBTK_SLICE_PAIRS=0, or on
+ * more than one lane, the call never waits.  A read longer than max_read_len (or than
  * DBTK_MAX_READ_LEN) is not validated on the host here: the device truncates it
  * to what was promised and raises an error word that the next
  * dbtk_ctx_synchronize / dbtk_ctx_counts / dbtk_allreduce returns, once, as
