@@ -1043,6 +1043,132 @@ class Eval:
             self.h = None
 
 
+EXPORTS_ASSOC = [
+    "dbtk_assoc_api_version", "dbtk_assoc_create", "dbtk_assoc_free", "dbtk_assoc_set_pairs", "dbtk_assoc_scan_device", "dbtk_assoc_scan_pred",
+    "dbtk_assoc_scan_dosage", "dbtk_assoc_best", "dbtk_assoc_hits", "dbtk_assoc_write", "dbtk_assoc_times", "dbtk_assoc_pvalue", "dbtk_assoc_bh",
+    "dbtk_assoc_r2_threshold",
+]
+
+
+def _bind_assoc(L):
+    dp = C.POINTER(C.c_double)
+    L.dbtk_assoc_api_version.restype = C.c_uint32
+    L.dbtk_assoc_api_version.argtypes = []
+    L.dbtk_assoc_create.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, u64p, dp, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
+    L.dbtk_assoc_free.argtypes = [C.c_void_p]
+    L.dbtk_assoc_free.restype = None
+    L.dbtk_assoc_set_pairs.argtypes = [C.c_void_p, C.c_uint64, u64p, u32p]
+    L.dbtk_assoc_scan_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, u32p, C.c_double]
+    L.dbtk_assoc_scan_pred.argtypes = [C.c_void_p, C.c_void_p, C.c_double]
+    L.dbtk_assoc_scan_dosage.argtypes = [C.c_void_p, C.c_void_p, C.c_double]
+    L.dbtk_assoc_best.argtypes = [C.c_void_p, C.POINTER(abi.AssocBest)]
+    L.dbtk_assoc_hits.argtypes = [C.c_void_p, C.POINTER(abi.AssocHit), C.c_uint64, u64p]
+    L.dbtk_assoc_write.argtypes = [C.c_void_p, C.c_char_p]
+    L.dbtk_assoc_times.argtypes = [C.c_void_p, dp]
+    L.dbtk_assoc_pvalue.argtypes = [C.c_double, C.c_uint64, dp]
+    L.dbtk_assoc_bh.argtypes = [dp, C.c_uint64, dp]
+    L.dbtk_assoc_r2_threshold.argtypes = [C.c_double, C.c_uint64, dp]
+    if L.dbtk_assoc_api_version() != abi.ASSOC_API_VERSION:
+        raise RuntimeError("libdbtk_hip.so: dbtk_assoc.h version mismatch")
+
+
+def assoc_pvalue(lib, r, n):
+    """dbtk_assoc_pvalue: the two-sided Student-t tail of a correlation r over n samples; no device."""
+    _bind_assoc(lib.L)
+    p = C.c_double()
+    lib._chk(lib.L.dbtk_assoc_pvalue(float(r), int(n), C.byref(p)))
+    return p.value
+
+
+def assoc_bh(lib, p):
+    """dbtk_assoc_bh: Benjamini-Hochberg q-values of p, clipped at 1; no device."""
+    _bind_assoc(lib.L)
+    p = np.ascontiguousarray(p, np.float64)
+    q = np.zeros(len(p), np.float64)
+    lib._chk(lib.L.dbtk_assoc_bh(p.ctypes.data_as(C.POINTER(C.c_double)), len(p), q.ctypes.data_as(C.POINTER(C.c_double))))
+    return q
+
+
+def assoc_r2_threshold(lib, p_threshold, n):
+    """dbtk_assoc_r2_threshold: the r^2 the scan kernel compares with for a p-value threshold; no device."""
+    _bind_assoc(lib.L)
+    r2 = C.c_double()
+    lib._chk(lib.L.dbtk_assoc_r2_threshold(float(p_threshold), int(n), C.byref(r2)))
+    return r2.value
+
+
+ASSOC_BEST_FIELDS = ("n_tests", "skipped", "row", "locus", "r", "se", "t", "p", "p_bonf", "q")  # dbtk_assoc_best_t
+
+
+class Assoc:
+    """The association scan of include/dbtk_assoc.h through ctypes: a phenotype table (P x n float64 over the samples sample_of) against
+    the rows of a Pred, a Dosage or any float32 [nrows][ns] matrix in device memory; best row per phenotype and the hit list."""
+
+    def __init__(self, lib, ns, sample_of, pheno, names=None, device=0):
+        self._lib = lib
+        _bind_assoc(lib.L)
+        self.sample_of = np.ascontiguousarray(sample_of, np.uint64)
+        self.pheno = np.ascontiguousarray(pheno, np.float64)
+        if self.pheno.ndim == 1:
+            self.pheno = self.pheno.reshape(1, -1)
+        self.P, self.n = self.pheno.shape
+        assert self.n == len(self.sample_of)
+        cnames = None
+        if names is not None:
+            assert len(names) == self.P
+            cnames = (C.c_char_p * self.P)(*[os.fsencode(s) for s in names])
+        self.h = C.c_void_p()
+        lib._chk(lib.L.dbtk_assoc_create(int(device), int(ns), self.P, self.n, _ptr(self.sample_of, u64p), self.pheno.ctypes.data_as(C.POINTER(C.c_double)),
+                                         cnames, C.byref(self.h)))
+
+    def set_pairs(self, off, pheno_idx):
+        """CSR over the loci: off[ntr + 1], pheno_idx[off[ntr]]; set_pairs([], []) removes the list."""
+        off = np.ascontiguousarray(off, np.uint64)
+        idx = np.ascontiguousarray(pheno_idx, np.uint32)
+        ntr = max(len(off) - 1, 0)
+        self._lib._chk(self._lib.L.dbtk_assoc_set_pairs(self.h, ntr, _ptr(off, u64p) if ntr else None, _ptr(idx, u32p) if len(idx) else None))
+
+    def scan_device(self, d_rows, nrows, nk_cum=None, p_threshold=-1.0):
+        """d_rows: address of float32 [nrows][ns] in device memory (an int, a ctypes c_void_p, or anything with data_ptr())."""
+        ptr = d_rows.data_ptr() if hasattr(d_rows, "data_ptr") else d_rows.value if isinstance(d_rows, C.c_void_p) else int(d_rows)
+        nkc = np.ascontiguousarray(nk_cum, np.uint32) if nk_cum is not None else None
+        self._lib._chk(self._lib.L.dbtk_assoc_scan_device(self.h, C.c_void_p(ptr), int(nrows), len(nkc) if nkc is not None else 0, _ptr(nkc, u32p), float(p_threshold)))
+
+    def scan_pred(self, pred, p_threshold=-1.0):
+        self._lib._chk(self._lib.L.dbtk_assoc_scan_pred(self.h, pred.h, float(p_threshold)))
+
+    def scan_dosage(self, dosage, p_threshold=-1.0):
+        self._lib._chk(self._lib.L.dbtk_assoc_scan_dosage(self.h, dosage.h, float(p_threshold)))
+
+    def best(self):
+        """per phenotype a dict of dbtk_assoc_best_t"""
+        arr = (abi.AssocBest * self.P)()
+        self._lib._chk(self._lib.L.dbtk_assoc_best(self.h, arr))
+        return [{f: getattr(arr[p], f) for f in ASSOC_BEST_FIELDS} for p in range(self.P)]
+
+    def hits(self):
+        """[(pheno, locus, row, r, t, p)] sorted by (pheno, row)"""
+        n = C.c_uint64()
+        self._lib._chk(self._lib.L.dbtk_assoc_hits(self.h, None, 0, C.byref(n)))
+        arr = (abi.AssocHit * max(n.value, 1))()
+        self._lib._chk(self._lib.L.dbtk_assoc_hits(self.h, arr, n.value, C.byref(n)))
+        return [(h.pheno, h.locus, h.row, h.r, h.t, h.p) for h in arr[:n.value]]
+
+    def write(self, prefix):
+        self._lib._chk(self._lib.L.dbtk_assoc_write(self.h, os.fsencode(prefix)))
+
+    def times(self):
+        """(milliseconds in k_assoc_scan, milliseconds in the host fold) of the last scan"""
+        ms = (C.c_double * 2)()
+        self._lib._chk(self._lib.L.dbtk_assoc_times(self.h, ms))
+        return float(ms[0]), float(ms[1])
+
+    def close(self):
+        if self.h:
+            self._lib.L.dbtk_assoc_free(self.h)
+            self.h = None
+
+
 class Synth:
     """Seeded release-scale workload generator (csrc/dbtk_synth.cpp): a flat
     RPGG + 150 bp read pairs, for bench.py and the scale tests."""

@@ -10,6 +10,9 @@ KCP_TP_ONLY = 1      # dbtk_kcp_create flags
 KCP_FPS_MI_NONE, KCP_FPS_MA_NONE = 255, 0  # dbtk_kcp_fps_read: (mi, ma) of a living candidate that no TP table held
 SIM_API_VERSION = 1  # include/dbtk_sim.h: DBTK_SIM_API_VERSION
 EVAL_API_VERSION = 1  # include/dbtk_eval.h: DBTK_EVAL_API_VERSION
+ASSOC_API_VERSION = 1  # include/dbtk_assoc.h: DBTK_ASSOC_API_VERSION
+ASSOC_ALL_PAIRS_MAX = 64  # phenotypes up to which a table may be scanned without a pair list
+ASSOC_NONE = 0xFFFFFFFF  # row / locus of a phenotype without tests
 BUBBLES_LOG, BUBBLES_TABLE = 1, 2  # params.bubbles: event log replayed on the host (reference order) | counts in a device table
 ALN_TEXT = 4  # params.aln | ALN_TEXT: alignment records in text form (dbtk_ctx_aln_text)
 THREAD_CAP = 384
@@ -121,3 +124,14 @@ class EvalSums(C.Structure):
 class EvalCols(C.Structure):
     """include/dbtk_eval.h: dbtk_eval_cols_t"""
     _fields_ = [(n, C.c_double) for n in ("slope", "pred", "r2", "pred_present", "r2_present")]
+
+
+class AssocBest(C.Structure):
+    """include/dbtk_assoc.h: dbtk_assoc_best_t"""
+    _fields_ = [("n_tests", C.c_uint64), ("skipped", C.c_uint64), ("row", C.c_uint32), ("locus", C.c_uint32)] + \
+               [(n, C.c_double) for n in ("r", "se", "t", "p", "p_bonf", "q")]
+
+
+class AssocHit(C.Structure):
+    """include/dbtk_assoc.h: dbtk_assoc_hit_t"""
+    _fields_ = [(n, C.c_uint32) for n in ("pheno", "locus", "row", "pad")] + [(n, C.c_double) for n in ("r", "t", "p")]

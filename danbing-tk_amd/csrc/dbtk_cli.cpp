@@ -49,6 +49,7 @@
 #include "../../include/dbtk_kcp.h"
 #include "../../include/dbtk_eval.h"
 #include "../../include/dbtk_sim.h"
+#include "dbtk_assoc_cli.h"
 #include "dbtk_pred_io.h"
 
 namespace {
@@ -115,6 +116,7 @@ struct Opts {
     uint64_t simFs = 500, simRlen = 150, simC = 15, simMl = 50000;  // --sim-fs / --sim-rlen / --sim-c / --sim-ml
     std::string simParam;              // the first --sim-* flag given (they need --sim)
     // --eval PREF: the counts of the run scored per locus against the genome's own k-mer counts (include/dbtk_eval.h): PREF.eval.tsv, PREF.pred
+    dbtk_assoc_cli::Options assoc;  // --assoc PHENO.tsv OUTPREF ...: the association scans of the cohort's matrix or dosage table (dbtk_assoc_cli.h)
     std::string eval, evalTruth, evalDumpTruth;  // --eval-truth FILE: the truth from a file (OUT.trkmc.ar layout); --eval-dump-truth FILE: the truth of --sim into one
 };
 struct CohortSample { std::string reads, prefix; float depth = 0; };
@@ -196,6 +198,10 @@ void usage() {
             "                         locus has no invariant k-mers), and the bias table of --pred; neither needs the genotype matrix,\n"
             "                         so the cohort's size is not bounded by it\n"
             "  --no-trkmc             with --pred, --kms or --dosage: write no per-sample files at all\n"
+            "  --assoc <PHENO.tsv> <OUTPREF> [--assoc-pairs <PAIRS.tsv>] [--assoc-p <X>] [--assoc-raw]\n"
+            "                         with --cohort and --pred or --dosage: after the last sample, what danbing-tk-pred --assoc makes of the\n"
+            "                         matrix (with --pred) or of the dosage values: OUTPREF.assoc.best.tsv, with --assoc-p OUTPREF.assoc.hits.tsv;\n"
+            "                         the group may be repeated\n"
             "Developer:\n"
             "  -s <1|2>  -e <1|2>  -v <INT>  -g|-gc|-gcc <INT> [INT]  -a  -ae  -tb  -ik  -t <INT>  -m <FILE>  -au\n\n");
 }
@@ -452,6 +458,13 @@ int main(int argc, char* argv[]) {
         else if (a == "--pred") { o.pred.clear(); for (int i = 0; i < 4; ++i) o.pred.push_back(need(++argi)); }
         else if (a == "--kms") o.kms = need(++argi);
         else if (a == "--dosage") { o.dosage.clear(); for (int i = 0; i < 3; ++i) o.dosage.push_back(need(++argi)); }
+        else if (a.compare(0, 7, "--assoc") == 0) {
+            std::string err;
+            const int used = dbtk_assoc_cli::take_flag(&o.assoc, argc, argv, (int)argi, &err);
+            if (used < 0) refuse(err);
+            if (!used) { fprintf(stderr, "invalid option: %s\n", a.c_str()); abort(); }
+            argi += (size_t)used - 1;
+        }
         else {
             fprintf(stderr, "invalid option: %s\n", a.c_str());
             abort();  // the reference does `throw;` with no active exception -> std::terminate
@@ -543,6 +556,7 @@ int main(int argc, char* argv[]) {
         if (!o.kms.empty()) refuse("--kms needs --cohort (for count files that exist already there are ktools sum and danbing-tk-pred --dosage --kms)");
         if (!o.dosage.empty()) refuse("--dosage needs --cohort (for count files that exist already there is danbing-tk-pred --dosage)");
         if (o.noTrkmc) refuse("--no-trkmc needs --cohort and --pred, --kms or --dosage");
+        if (o.assoc.any()) refuse("--assoc needs --cohort and --pred or --dosage (for count files that exist already there is danbing-tk-pred --assoc)");
     } else {
         if (!o.fastxFname.empty()) refuse("--cohort takes the place of -fa/-fq: the reads files are in the manifest");
         if (!o.outPrefix.empty()) refuse("--cohort takes the place of -o/-on: the output prefixes are in the manifest (--cohort-names for the -on form)");
@@ -600,6 +614,11 @@ int main(int argc, char* argv[]) {
                 fclose(f);
                 (void)unlink(o.pred[i].c_str());
             }
+        }
+        if (o.assoc.any()) {  // the tables are read and checked now; with --pred the matrix is what is scanned, otherwise the dosage values
+            if (o.pred.empty() && o.dosage.empty()) refuse("--assoc needs --pred or --dosage: it scans the matrix or the dosage table they leave in HBM");
+            std::string err;
+            if (!dbtk_assoc_cli::load(&o.assoc, o.pred.empty(), &err)) refuse(err);
         }
         // ... and the files of --dosage and --kms, in the same way
         if (!o.dosage.empty() && !readable(o.dosage[0])) refuse("--dosage: cannot open " + o.dosage[0]);
@@ -2214,11 +2233,14 @@ int main(int argc, char* argv[]) {
             std::string err;
             if (dbtk_pred_matrix(pred, mat.data())) die_assert(dbtk_last_error());
             if (!dbtk_pred_io::save_matrix(o.pred[1], mat.data(), ns, ntrk, stderr, &err)) die_assert(err);
+            auto scan = [&](dbtk_assoc_t* h, double p) { return dbtk_assoc_scan_pred(h, pred, p); };
+            if (!dbtk_assoc_cli::run(&o.assoc, true, dev_of(0), ns, ntr, scan, stderr, &err)) die_assert(err);
             if (dbtk_pred_correct(pred)) die_assert(dbtk_last_error());
             if (dbtk_pred_matrix(pred, mat.data())) die_assert(dbtk_last_error());
             if (!dbtk_pred_io::save_matrix(o.pred[2], mat.data(), ns, ntrk, stderr, &err)) die_assert(err);
             if (dbtk_pred_bias(pred, bias.data())) die_assert(dbtk_last_error());
             if (!dbtk_pred_io::save_bias_tsv(o.pred[3], bias.data(), ns, ntr, stderr, &err)) die_assert(err);
+            if (!dbtk_assoc_cli::run(&o.assoc, false, dev_of(0), ns, ntr, scan, stderr, &err)) die_assert(err);
         }
         if (dosage) {  // what `danbing-tk-pred --dosage` writes from the samples' count files
             const uint64_t ns = samples.size(), ntr = dbtk_dosage_ntr(dosage);
@@ -2229,6 +2251,7 @@ int main(int argc, char* argv[]) {
             if (!dbtk_pred_io::save_bias_tsv(o.dosage[1], tab.data(), ns, ntr, stderr, &err)) die_assert(err);
             if (dbtk_dosage_bias(dosage, tab.data())) die_assert(dbtk_last_error());
             if (!dbtk_pred_io::save_bias_tsv(o.dosage[2], tab.data(), ns, ntr, stderr, &err)) die_assert(err);
+            if (!pred && !dbtk_assoc_cli::run(&o.assoc, false, dev_of(0), ns, ntr, [&](dbtk_assoc_t* h, double p) { return dbtk_assoc_scan_dosage(h, dosage, p); }, stderr, &err)) die_assert(err);
         }
         if (kms) {
             const uint64_t ns = samples.size(), ntr = dbtk_dosage_ntr(kms);

@@ -80,4 +80,15 @@ dbtk_status_t sim_group_spans(const dbtk_sim* s, uint32_t g, std::vector<SimSpan
 dbtk_status_t sim_group_load(dbtk_sim* s, uint32_t g);
 }  // namespace dbtk
 
+// ---- what the association scan (dbtk_assoc.hip) needs of the matrix and dosage handles (dbtk_pred.hip): the float32 rows as they
+// lie in HBM, [nrows][ns], complete when the call returns, with the loci's cumulative row counts on the host.  pred_rows refuses a
+// windowed handle; dosage_rows makes the values of dbtk_dosage_values in the handle's buffer and refuses an unfinished handle.
+struct dbtk_pred;
+struct dbtk_dosage;
+namespace dbtk {
+struct RowsView { int device = 0; uint64_t ns = 0, nrows = 0, ntr = 0; const float* d_rows = nullptr; std::vector<uint32_t> nk_cum; };
+dbtk_status_t pred_rows(dbtk_pred* p, RowsView* out);
+dbtk_status_t dosage_rows(dbtk_dosage* d, RowsView* out);
+}  // namespace dbtk
+
 #endif

@@ -1045,3 +1045,31 @@ dbtk_status_t dbtk_dosage_load_samples(dbtk_dosage_t* d, uint64_t first_sample, 
 }
 
 }  // extern "C"
+
+// ---- the rows of the two handles for the association scan (dbtk_internal.h)
+namespace dbtk {
+static dbtk_status_t rows_meta(RowsView* out, const IkmerDev& meta, uint64_t ntr, hipStream_t s) {
+    out->nk_cum.resize(ntr);
+    PCHK(hipMemcpyAsync(out->nk_cum.data(), meta.nk, ntr * 4, hipMemcpyDeviceToHost, s));
+    PCHK(hipStreamSynchronize(s));
+    return DBTK_OK;
+}
+dbtk_status_t pred_rows(dbtk_pred* p, RowsView* out) {
+    if (!p || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
+    if (p->windowed) { set_error("a windowed handle holds a part of the rows at a time: the association scan needs the whole matrix (dbtk_pred_create)"); return DBTK_ERR_ARG; }
+    PCHK(hipSetDevice(p->device));
+    out->device = p->device; out->ns = p->ns; out->nrows = p->nk; out->ntr = p->ntr; out->d_rows = p->d_G;
+    return rows_meta(out, p->meta, p->ntr, p->stream);
+}
+dbtk_status_t dosage_rows(dbtk_dosage* d, RowsView* out) {
+    if (!d || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
+    if (!d->finished) { set_error("the dosage handle is unfinished: samples were loaded since the last dbtk_dosage_finish (or it was never called)"); return DBTK_ERR_ARG; }
+    PCHK(hipSetDevice(d->device));
+    hipLaunchKernelGGL(k_dosage_values, dim3((uint32_t)d->ntr, (uint32_t)((d->ns + 255) / 256)), dim3(256), 0, d->stream, d->d_kms, d->d_bias, d->d_depth, d->meta.nk, d->meta.nik, d->d_values, d->ns);
+    PCHK(hipGetLastError());
+    out->device = d->device; out->ns = d->ns; out->nrows = d->ntr; out->ntr = d->ntr; out->d_rows = d->d_values;
+    { const dbtk_status_t st = rows_meta(out, d->meta, d->ntr, d->stream); if (st) return st; }
+    for (uint64_t t = 0; t < d->ntr; ++t) out->nk_cum[t] = (uint32_t)(t + 1);  // a row per locus
+    return DBTK_OK;
+}
+}  // namespace dbtk

@@ -5,6 +5,8 @@
 // The second form makes the per-locus tables alone (dbtk_dosage_*): the matrix is never allocated, in HBM or on the host.
 //   danbing-tk-pred --window-rows R | --window-bytes N <INPUT1> <INPUT2> <OUTPUT1> <OUTPUT2> <OUTPUT3>
 // The first form for a cohort whose matrix fits neither: whole loci of at most R k-mers at a time (windowed()), the same three files.
+//   danbing-tk-pred --assoc PHENO.tsv OUTPREF [--assoc-pairs PAIRS.tsv] [--assoc-p X] [--assoc-raw] ... <either of the first two forms>
+// The association scan of the resident matrix or dosage table (dbtk_assoc_cli.h); the other outputs are unchanged by it.
 #include <fcntl.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -17,6 +19,7 @@
 #include <vector>
 
 #include "../../include/dbtk_pred.h"
+#include "dbtk_assoc_cli.h"
 #include "dbtk_pred_io.h"
 
 static void die(const std::string& m, int code = 1) { fprintf(stderr, "%s\n", m.c_str()); exit(code); }
@@ -62,7 +65,7 @@ static void load_batches(const std::vector<std::string>& fns, const std::vector<
 
 // --dosage: the count files go to the GPU like below, but into the per-locus tables
 static int dosage_tables(int device, const std::string& finGtMeta, const std::string& finIkMeta, const std::string& foutBias, const std::string& foutDosage,
-                         const std::string& foutKms) {
+                         const std::string& foutKms, dbtk_assoc_cli::Options& assoc) {
     printf("metadata of *.trkmc.ar: %s\ninvariant kmers: %s\ndosage table will be written to: %s\nbias matrix will be written to: %s\n",
            finGtMeta.c_str(), finIkMeta.c_str(), foutDosage.c_str(), foutBias.c_str());
     std::vector<std::string> fns;
@@ -94,6 +97,7 @@ static int dosage_tables(int device, const std::string& finGtMeta, const std::st
         if (dbtk_dosage_kms(D, kms.data())) die(dbtk_last_error());
         if (!dbtk_pred_io::save_kms(foutKms, kms.data(), ns, ntr, stdout, &err)) die(err);
     }
+    if (!dbtk_assoc_cli::run(&assoc, false, device, ns, ntr, [&](dbtk_assoc_t* h, double p) { return dbtk_assoc_scan_dosage(h, D, p); }, stdout, &err)) die(err);
     dbtk_dosage_free(D);
     return 0;
 }
@@ -192,14 +196,21 @@ int main(int argc, char** argv) {
                         "                  no invariant k-mers) in the layout of OUTPUT3, and the plain sums as `ktools sum -f` writes them\n"
                         "  --window-rows <INT>   the two matrices one window of whole loci at a time, at most INT k-mers each: the same\n"
                         "                  three files from O(window) of device and host memory (no locus may have more k-mers)\n"
-                        "  --window-bytes <INT>  the same, as the size of a window's device matrix: INT / (4 * samples) k-mers\n\n");
+                        "  --window-bytes <INT>  the same, as the size of a window's device matrix: INT / (4 * samples) k-mers\n%s\n", dbtk_assoc_cli::usage());
         return 0;
     }
     int argi = 1, device = 0;
     std::string foutDosage, foutKms;
     uint64_t winRows = 0, winBytes = 0;
+    dbtk_assoc_cli::Options assoc;
     while (argi < argc && argv[argi][0] == '-') {
         const std::string a = argv[argi];
+        {
+            std::string err;
+            const int used = dbtk_assoc_cli::take_flag(&assoc, argc, argv, argi, &err);
+            if (used < 0) die(err);
+            if (used) { argi += used; continue; }
+        }
         if (a == "--device" && argi + 1 < argc) { device = atoi(argv[argi + 1]); argi += 2; }
         else if (a == "--dosage" && argi + 1 < argc) { foutDosage = argv[argi + 1]; argi += 2; }
         else if (a == "--kms" && argi + 1 < argc) { foutKms = argv[argi + 1]; argi += 2; }
@@ -209,9 +220,14 @@ int main(int argc, char** argv) {
         else die("invalid option: " + a);
     }
     if (!foutKms.empty() && foutDosage.empty()) die("--kms needs --dosage");
+    if (assoc.any()) {  // everything of --assoc that can be refused before a device is touched
+        if (winRows || winBytes) die("--assoc: not with --window-rows / --window-bytes: a window holds a part of the rows, and the best row of a phenotype across windows is not made yet");
+        std::string err;
+        if (!dbtk_assoc_cli::load(&assoc, !foutDosage.empty(), &err)) die(err);
+    }
     if (!foutDosage.empty()) {
         if (argc - argi != 3) die("--dosage: expected 3 file arguments (INPUT1 INPUT2 OUTPUT3)");
-        return dosage_tables(device, argv[argi], argv[argi + 1], argv[argi + 2], foutDosage, foutKms);
+        return dosage_tables(device, argv[argi], argv[argi + 1], argv[argi + 2], foutDosage, foutKms, assoc);
     }
     if (argc - argi < 5) die("expected 5 file arguments");
     const std::string finGtMeta = argv[argi], finIkMeta = argv[argi + 1], foutRaw = argv[argi + 2], fout = argv[argi + 3], foutBias = argv[argi + 4];
@@ -239,6 +255,11 @@ int main(int argc, char** argv) {
     printf("normalizaing read depth\n");
     if (dbtk_pred_matrix(P, mat.data())) die(dbtk_last_error());
     save_matrix(foutRaw, mat.data(), ns, nk);
+    auto scan = [&](dbtk_assoc_t* h, double p) { return dbtk_assoc_scan_pred(h, P, p); };
+    {
+        std::string err;
+        if (!dbtk_assoc_cli::run(&assoc, true, device, ns, ntr, scan, stdout, &err)) die(err);
+    }
     printf("computing/correcting bias\n");
     if (dbtk_pred_correct(P)) die(dbtk_last_error());
     float ms[3];
@@ -251,6 +272,7 @@ int main(int argc, char** argv) {
     {
         std::string err;
         if (!dbtk_pred_io::save_bias_tsv(foutBias, bias.data(), ns, ntr, stdout, &err)) die(err);
+        if (!dbtk_assoc_cli::run(&assoc, false, device, ns, ntr, scan, stdout, &err)) die(err);
     }
     dbtk_pred_free(P);
     return 0;
