@@ -1097,6 +1097,38 @@ def assoc_r2_threshold(lib, p_threshold, n):
     return r2.value
 
 
+EXPORTS_ASSOC_COVAR = ["dbtk_assoc_covar_api_version", "dbtk_assoc_covar_basis", "dbtk_assoc_covar_set", "dbtk_assoc_covar_get"]
+
+
+def _bind_assoc_covar(L):
+    dp = C.POINTER(C.c_double)
+    L.dbtk_assoc_covar_api_version.restype = C.c_uint32
+    L.dbtk_assoc_covar_api_version.argtypes = []
+    L.dbtk_assoc_covar_basis.argtypes = [C.c_uint64, C.c_uint64, dp, dp, u64p]
+    L.dbtk_assoc_covar_set.argtypes = [C.c_void_p, C.c_uint64, dp, C.POINTER(C.c_char_p)]
+    L.dbtk_assoc_covar_get.argtypes = [C.c_void_p, u64p, u64p]
+    if L.dbtk_assoc_covar_api_version() != abi.ASSOC_COVAR_API_VERSION:
+        raise RuntimeError("libdbtk_hip.so: dbtk_assoc_covar.h version mismatch")
+
+
+def assoc_covar_basis(lib, covar):
+    """dbtk_assoc_covar_basis: covar[q][n] -> the orthonormal basis Q[q][n] of its centred columns; no device.  A DbtkError carries the
+    offending column in .bad_column."""
+    _bind_assoc_covar(lib.L)
+    covar = np.ascontiguousarray(covar, np.float64)
+    if covar.ndim == 1:
+        covar = covar.reshape(1, -1)
+    q, n = covar.shape
+    Q = np.zeros((q, n), np.float64)
+    bad = C.c_uint64(0)
+    try:
+        lib._chk(lib.L.dbtk_assoc_covar_basis(n, q, covar.ctypes.data_as(C.POINTER(C.c_double)), Q.ctypes.data_as(C.POINTER(C.c_double)), C.byref(bad)))
+    except DbtkError as e:
+        e.bad_column = int(bad.value)
+        raise
+    return Q
+
+
 ASSOC_BEST_FIELDS = ("n_tests", "skipped", "row", "locus", "r", "se", "t", "p", "p_bonf", "q")  # dbtk_assoc_best_t
 
 
@@ -1127,6 +1159,27 @@ class Assoc:
         idx = np.ascontiguousarray(pheno_idx, np.uint32)
         ntr = max(len(off) - 1, 0)
         self._lib._chk(self._lib.L.dbtk_assoc_set_pairs(self.h, ntr, _ptr(off, u64p) if ntr else None, _ptr(idx, u32p) if len(idx) else None))
+
+    def set_covariates(self, covar, names=None):
+        """dbtk_assoc_covar_set: covar[q][n], sample j = sample_of[j]; None or an empty array removes the covariates."""
+        _bind_assoc_covar(self._lib.L)
+        covar = np.zeros((0, self.n)) if covar is None else np.ascontiguousarray(covar, np.float64)
+        if covar.ndim == 1:
+            covar = covar.reshape(1, -1) if covar.size else covar.reshape(0, self.n)
+        q = covar.shape[0]
+        assert q == 0 or covar.shape[1] == self.n
+        cnames = None
+        if names is not None and q:
+            assert len(names) == q
+            cnames = (C.c_char_p * q)(*[os.fsencode(s) for s in names])
+        self._lib._chk(self._lib.L.dbtk_assoc_covar_set(self.h, q, covar.ctypes.data_as(C.POINTER(C.c_double)) if q else None, cnames))
+
+    def covariates(self):
+        """(q, dof): the covariates of the handle and the degrees of freedom n - 2 - q of its tests"""
+        _bind_assoc_covar(self._lib.L)
+        q, dof = C.c_uint64(), C.c_uint64()
+        self._lib._chk(self._lib.L.dbtk_assoc_covar_get(self.h, C.byref(q), C.byref(dof)))
+        return int(q.value), int(dof.value)
 
     def scan_device(self, d_rows, nrows, nk_cum=None, p_threshold=-1.0):
         """d_rows: address of float32 [nrows][ns] in device memory (an int, a ctypes c_void_p, or anything with data_ptr())."""

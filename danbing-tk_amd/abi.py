@@ -13,6 +13,9 @@ EVAL_API_VERSION = 1  # include/dbtk_eval.h: DBTK_EVAL_API_VERSION
 ASSOC_API_VERSION = 1  # include/dbtk_assoc.h: DBTK_ASSOC_API_VERSION
 ASSOC_ALL_PAIRS_MAX = 64  # phenotypes up to which a table may be scanned without a pair list
 ASSOC_NONE = 0xFFFFFFFF  # row / locus of a phenotype without tests
+ASSOC_COVAR_API_VERSION = 1  # include/dbtk_assoc_covar.h: DBTK_ASSOC_COVAR_API_VERSION
+ASSOC_COVAR_MAX = 128  # covariates of a table at most
+ASSOC_COVAR_COLLINEAR = 1e-6  # the residual share at or below which a covariate, a row or a phenotype counts as explained
 BUBBLES_LOG, BUBBLES_TABLE = 1, 2  # params.bubbles: event log replayed on the host (reference order) | counts in a device table
 ALN_TEXT = 4  # params.aln | ALN_TEXT: alignment records in text form (dbtk_ctx_aln_text)
 THREAD_CAP = 384

@@ -1,4 +1,5 @@
-// dbtk_assoc.hip — the association scan (include/dbtk_assoc.h): the phenotype centring, the scan kernel, the handle and the host fold.
+// dbtk_assoc.hip — the association scan (include/dbtk_assoc.h) and its covariates (include/dbtk_assoc_covar.h): the phenotype centring,
+// the phenotypes' projections on the covariate basis, the scan kernel, the handle and the host fold.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -13,6 +14,8 @@
 #include <vector>
 
 #include "../../include/dbtk_assoc.h"
+#include "../../include/dbtk_assoc_covar.h"
+#include "dbtk_assoc_covar_host.h"
 #include "dbtk_assoc_host.h"
 #include "dbtk_internal.h"
 
@@ -40,6 +43,9 @@ constexpr uint64_t AS_HITS_DEFAULT = 1ull << 20;    // entries of the hit buffer
 constexpr uint32_t AS_ROWS = AS_TILE * AS_WAVES;    // rows of a workgroup's pass
 constexpr uint32_t AS_ACC = AS_TILE * AS_CHUNK;     // accumulators of a wave
 constexpr uint32_t AS_GRID = 2048;                  // workgroups at most; the items are taken round robin
+constexpr uint32_t AS_COVAR_MAX = 128;              // covariates at most: the a_j of a pass' rows take AS_ROWS * AS_COVAR_MAX * 8 bytes of LDS
+constexpr double AS_COLLINEAR = DBTK_ASSOC_COVAR_COLLINEAR;
+static_assert(AS_COVAR_MAX == DBTK_ASSOC_COVAR_MAX && AS_COVAR_MAX == dbtk_assoc_host::COVAR_MAX && AS_COLLINEAR == dbtk_assoc_host::COVAR_COLLINEAR, "one cap and one threshold");
 static_assert(AS_ACC == 32, "as_reduce hands element e to lanes 2e and 2e + 1: 32 elements over 64 lanes");
 static_assert(AS_ITEM_ROWS % AS_ROWS == 0 && AS_WAVES * 64 == AS_SEG, "a workgroup stages one segment with one value per thread");
 
@@ -56,7 +62,7 @@ struct AsArgs {
     uint32_t n;              // samples of the mask
     const uint32_t* sidx;    // [n] ascending (not read when the mask is everything)
     const double* yc;        // [P][n] centred phenotypes
-    const double* syy;       // [P] their sums of squares
+    const double* syy;       // [P] their sums of squares (with covariates: Syy', what the covariates leave of them)
     const AsItem* items;
     uint32_t nitems;
     const uint32_t* ph_idx;  // null: the identity
@@ -65,6 +71,10 @@ struct AsArgs {
     unsigned long long* nhits;
     uint64_t hit_cap;
     double r2crit;           // above 1: no hits are collected
+    // the covariates, read by the COVAR instances alone (behind everything else: the other instances keep the argument layout they had)
+    const double* Q;         // [q][n] the orthonormal basis of the centred covariates
+    const double* bt;        // [P][q] b_j = sum dy Q_j of every phenotype
+    uint32_t q;              // covariates (0: none)
 };
 
 // The one summation tree of the scan: a lane adds its samples lane, lane + 64, ... in ascending order, the wave adds the lanes by
@@ -110,6 +120,24 @@ __global__ void __launch_bounds__(64) k_assoc_pheno(double* __restrict__ y, doub
     if (lane == 0) syy[blockIdx.x] = ss;
 }
 
+// One wave per phenotype, beside k_assoc_pheno: bt[p][j] = sum_i yc[p][i] Q[j][i] through the rows' summation tree (a lane's samples
+// ascending by fma, then as_wave_sum), and syyr[p] = syy[p] - sum_j b_j^2, j ascending by fma.
+__global__ void __launch_bounds__(64) k_assoc_covar_pheno(const double* __restrict__ yc, const double* __restrict__ syy, const double* __restrict__ Q,
+                                                          double* __restrict__ bt, double* __restrict__ syyr, uint32_t n, uint32_t q) {
+    const uint32_t lane = threadIdx.x;
+    const double* v = yc + (uint64_t)blockIdx.x * n;
+    double left = syy[blockIdx.x];
+    for (uint32_t j = 0; j < q; ++j) {
+        const double* c = Q + (uint64_t)j * n;
+        double s = 0.0;
+        for (uint32_t i = lane; i < n; i += 64) s = fma(v[i], c[i], s);
+        const double b = as_wave_sum(s);
+        left = fma(-b, b, left);
+        if (lane == 0) bt[(uint64_t)blockIdx.x * q + j] = b;
+    }
+    if (lane == 0) syyr[blockIdx.x] = left;
+}
+
 // the register slots of a lane that a segment fills: 64 samples each (the same for every thread; the slots behind them are not touched)
 __device__ __forceinline__ uint32_t as_slots(uint32_t n, uint32_t seg0) { return (min(n - seg0, AS_SEG) + 63u) / 64u; }
 
@@ -134,9 +162,13 @@ __device__ __forceinline__ void as_load(const AsArgs& a, const uint64_t (&base)[
 // accumulators: a staged value serves AS_TILE multiply-adds.  The accumulators are summed across the wave (as_reduce), a lane per
 // (row, phenotype) makes r and enters a hit under one atomic counter add per wave, and thread c folds the pass' rows into the
 // item's candidate of phenotype c in row order (strict >: a tie stays with the lower row).
-template <bool IDENT>
+// COVAR: in front of the phenotype chunks the q columns of Q go through the same chunk machinery, AS_CHUNK at a time, as phenotypes that
+// every row meets: their sums are the rows' a_j, kept in LDS.  Sxx' = Sxx - sum a_j^2 then replaces Sxx, a row that the covariates
+// explain leaves the tested ones (so tst is written only now), and the lane that makes r first takes sum_j a_j b_j off Sxy.
+template <bool IDENT, bool COVAR>
 __global__ void __launch_bounds__(AS_WAVES * 64) k_assoc_scan(const AsArgs a) {
     __shared__ double zl[AS_CHUNK][AS_SEG];
+    __shared__ double aj[COVAR ? AS_COVAR_MAX : 1][AS_ROWS];  // (the rows of a wave side by side: its lanes read AS_TILE neighbours; not referenced without COVAR)
     __shared__ double rbuf[AS_WAVES][AS_ACC];
     __shared__ uint32_t tst[AS_WAVES][AS_TILE];  // 0: no row, 1: tested, 2: skipped
     const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
@@ -203,10 +235,13 @@ __global__ void __launch_bounds__(AS_WAVES * 64) k_assoc_scan(const AsArgs a) {
 #pragma unroll
             for (uint32_t t = 0; t < AS_TILE; ++t) {
                 sxx[t] = as_wave_sum(sxx[t]);
-                if (lane == t) tst[w][t] = on[t] ? (tested[t] ? 1u : 2u) : 0u;
+                if (!COVAR && lane == t) tst[w][t] = on[t] ? (tested[t] ? 1u : 2u) : 0u;
             }
-            for (uint32_t c0 = 0; c0 < it.ph_n; c0 += AS_CHUNK) {
-                const uint32_t cn = min(AS_CHUNK, it.ph_n - c0);
+            const uint32_t qpad = COVAR ? (a.q + AS_CHUNK - 1) / AS_CHUNK * AS_CHUNK : 0u;  // the covariate chunks come first
+            for (uint32_t cc = 0; cc < qpad + it.ph_n; cc += AS_CHUNK) {
+                const bool cov = COVAR && cc < qpad;
+                const uint32_t c0 = cc - (cov ? 0u : qpad);
+                const uint32_t cn = min(AS_CHUNK, (cov ? a.q : it.ph_n) - c0);
                 double acc[AS_ACC];
 #pragma unroll
                 for (uint32_t e = 0; e < AS_ACC; ++e) acc[e] = 0.0;
@@ -214,6 +249,7 @@ __global__ void __launch_bounds__(AS_WAVES * 64) k_assoc_scan(const AsArgs a) {
                     if (!resident) as_load<IDENT>(a, base, seg0, lane, x);
                     __syncthreads();  // the segment before has been read (and, the first time, the fold before is done with rbuf)
                     for (uint32_t c = 0; c < cn; ++c) {
+                        if (cov) { zl[c][tid] = seg0 + tid < a.n ? a.Q[(uint64_t)(c0 + c) * a.n + seg0 + tid] : 0.0; continue; }
                         const uint64_t ph = a.ph_idx ? a.ph_idx[it.ph_off + c0 + c] : c0 + c;
                         zl[c][tid] = seg0 + tid < a.n ? a.yc[ph * a.n + seg0 + tid] : 0.0;  // (0 past the end: adds nothing)
                     }
@@ -235,8 +271,24 @@ __global__ void __launch_bounds__(AS_WAVES * 64) k_assoc_scan(const AsArgs a) {
                         }
                     }
                 }
-                const double sxy = as_reduce(acc, lane);
+                double sxy = as_reduce(acc, lane);
                 const uint32_t e = lane >> 1, t = e / AS_CHUNK, c = e % AS_CHUNK;
+                if constexpr (COVAR) {
+                    if (cov) {
+                        if (!(lane & 1u) && c < cn) aj[c0 + c][w * AS_TILE + t] = sxy;
+                        if (cc + AS_CHUNK < qpad) continue;
+                        __syncthreads();  // the a_j of every chunk are in LDS (each wave reads its own rows only)
+#pragma unroll
+                        for (uint32_t u = 0; u < AS_TILE; ++u) {
+                            double left = sxx[u];
+                            for (uint32_t j = 0; j < a.q; ++j) { const double v = aj[j][w * AS_TILE + u]; left = fma(-v, v, left); }
+                            tested[u] = tested[u] && left > AS_COLLINEAR * sxx[u];
+                            sxx[u] = left;
+                            if (lane == u) tst[w][u] = on[u] ? (tested[u] ? 1u : 2u) : 0u;
+                        }
+                        continue;
+                    }
+                }
                 const double sx = t == 0 ? sxx[0] : t == 1 ? sxx[1] : t == 2 ? sxx[2] : sxx[3];
                 const bool tt = t == 0 ? tested[0] : t == 1 ? tested[1] : t == 2 ? tested[2] : tested[3];
                 const bool mine = !(lane & 1u) && c < cn && tt;
@@ -244,6 +296,10 @@ __global__ void __launch_bounds__(AS_WAVES * 64) k_assoc_scan(const AsArgs a) {
                 double r = 0.0;
                 if (mine) {
                     ph = a.ph_idx ? a.ph_idx[it.ph_off + c0 + c] : c0 + c;
+                    if constexpr (COVAR) {
+                        const double* b = a.bt + (uint64_t)ph * a.q;
+                        for (uint32_t j = 0; j < a.q; ++j) sxy = fma(-aj[j][w * AS_TILE + t], b[j], sxy);
+                    }
                     r = sxy / sqrt(sx * a.syy[ph]);
                     r = r > 1.0 ? 1.0 : r < -1.0 ? -1.0 : r;
                 }
@@ -304,6 +360,10 @@ struct dbtk_assoc {
     std::vector<uint64_t> off;
     std::vector<uint32_t> idx;
     uint32_t* d_idx = nullptr;
+    // the covariates (dbtk_assoc_covar.h); q == 0: none
+    std::vector<uint64_t> ord;        // ord[j]: the position in sample_of of the j-th sample in ascending order
+    uint64_t q = 0;
+    double *d_Q = nullptr, *d_bt = nullptr, *d_syyr = nullptr;
     // per scan, regrown
     AsItem* d_items = nullptr; uint64_t items_cap = 0;
     AsCand* d_cand = nullptr; uint64_t cand_cap = 0;
@@ -386,6 +446,7 @@ dbtk_status_t assoc_create_impl(int device_id, uint64_t ns, uint64_t P, uint64_t
     ACHK(hipSetDevice(device_id));
     h->device = device_id; h->ns = ns; h->P = P; h->n = n; h->hit_cap = hit_cap;
     h->ident = n == ns;
+    h->ord = ord;
     ACHK(hipStreamCreate(&h->stream));
     for (auto& e : h->ev) ACHK(hipEventCreate(&e));
     const std::string what = "association tables (phenotypes 8 * P * n = " + std::to_string(8 * P * n) + " bytes, hit buffer 16 * DBTK_ASSOC_HITS = " + std::to_string(16 * hit_cap) + " bytes)";
@@ -469,7 +530,8 @@ dbtk_status_t assoc_scan_impl(dbtk_assoc_t* h, const float* d_rows, uint64_t nro
     else add(0, nrows, 0, h->P);
     if (items.size() > 0xFFFFFFFFull) { set_error("dbtk_assoc_scan: too many work items"); return DBTK_ERR_ARG; }
     const bool want_hits = p_threshold >= 0.0;
-    const double r2crit = want_hits ? dbtk_assoc_host::r2_threshold(p_threshold, h->n) : 2.0;
+    const uint64_t neff = h->n - h->q;  // with covariates every test has n - 2 - q degrees of freedom: the closed forms take n - q for n
+    const double r2crit = want_hits ? dbtk_assoc_host::r2_threshold(p_threshold, neff) : 2.0;
     ACHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     std::vector<AsCand> cand(ncand);
@@ -481,13 +543,17 @@ dbtk_status_t assoc_scan_impl(dbtk_assoc_t* h, const float* d_rows, uint64_t nro
         ACHK(hipMemcpyAsync(h->d_items, items.data(), items.size() * sizeof(AsItem), hipMemcpyHostToDevice, s));
         ACHK(hipMemsetAsync(h->d_nhits, 0, 8, s));
         AsArgs a;
-        a.G = d_rows; a.ns = h->ns; a.n = (uint32_t)h->n; a.sidx = h->d_sidx; a.yc = h->d_yc; a.syy = h->d_syy;
+        a.G = d_rows; a.ns = h->ns; a.n = (uint32_t)h->n; a.sidx = h->d_sidx; a.yc = h->d_yc; a.syy = h->q ? h->d_syyr : h->d_syy;
+        a.q = (uint32_t)h->q; a.Q = h->d_Q; a.bt = h->d_bt;
         a.items = h->d_items; a.nitems = (uint32_t)items.size(); a.ph_idx = h->pairs ? h->d_idx : nullptr; a.cand = h->d_cand;
         a.hits = h->d_hits; a.nhits = h->d_nhits; a.hit_cap = h->hit_cap; a.r2crit = r2crit;
         const uint32_t grid = (uint32_t)std::min<uint64_t>(items.size(), AS_GRID);
         ACHK(hipEventRecord(h->ev[0], s));
-        if (h->ident) hipLaunchKernelGGL(k_assoc_scan<true>, dim3(grid), dim3(AS_WAVES * 64), 0, s, a);
-        else hipLaunchKernelGGL(k_assoc_scan<false>, dim3(grid), dim3(AS_WAVES * 64), 0, s, a);
+        if (h->q) {
+            if (h->ident) hipLaunchKernelGGL((k_assoc_scan<true, true>), dim3(grid), dim3(AS_WAVES * 64), 0, s, a);
+            else hipLaunchKernelGGL((k_assoc_scan<false, true>), dim3(grid), dim3(AS_WAVES * 64), 0, s, a);
+        } else if (h->ident) hipLaunchKernelGGL((k_assoc_scan<true, false>), dim3(grid), dim3(AS_WAVES * 64), 0, s, a);
+        else hipLaunchKernelGGL((k_assoc_scan<false, false>), dim3(grid), dim3(AS_WAVES * 64), 0, s, a);
         ACHK(hipGetLastError());
         ACHK(hipEventRecord(h->ev[1], s));
         ACHK(hipMemcpyAsync(cand.data(), h->d_cand, ncand * sizeof(AsCand), hipMemcpyDeviceToHost, s));
@@ -511,7 +577,7 @@ dbtk_status_t assoc_scan_impl(dbtk_assoc_t* h, const float* d_rows, uint64_t nro
     h->best.assign(h->P, dbtk_assoc_best_t{});
     std::vector<double> pb;
     std::vector<uint64_t> who;
-    const double df = (double)(h->n - 2);
+    const double df = (double)(neff - 2);
     for (uint64_t p = 0; p < h->P; ++p) {
         dbtk_assoc_best_t& o = h->best[p];
         o.n_tests = acc[p].tested; o.skipped = acc[p].skipped; o.row = DBTK_ASSOC_NONE; o.locus = DBTK_ASSOC_NONE;
@@ -519,7 +585,7 @@ dbtk_status_t assoc_scan_impl(dbtk_assoc_t* h, const float* d_rows, uint64_t nro
         o.row = acc[p].row; o.locus = locus_of(nkc, o.row); o.r = acc[p].r;
         o.se = sqrt((1.0 - o.r * o.r) / df);
         o.t = o.r / o.se;
-        o.p = dbtk_assoc_host::pvalue(o.r, h->n);
+        o.p = dbtk_assoc_host::pvalue(o.r, neff);
         o.p_bonf = o.p * (double)o.n_tests;
         pb.push_back(o.p_bonf); who.push_back(p);
     }
@@ -542,12 +608,68 @@ dbtk_status_t assoc_scan_impl(dbtk_assoc_t* h, const float* d_rows, uint64_t nro
             dbtk_assoc_hit_t& o = h->hits[i];
             o.pheno = raw[i].ph; o.row = raw[i].row; o.locus = locus_of(nkc, o.row); o.pad = 0; o.r = raw[i].r;
             o.t = o.r / sqrt((1.0 - o.r * o.r) / df);
-            o.p = dbtk_assoc_host::pvalue(o.r, h->n);
+            o.p = dbtk_assoc_host::pvalue(o.r, neff);
         }
     }
     h->ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     h->scanned = true;
     return st;
+}
+
+dbtk_status_t assoc_covar_set_impl(dbtk_assoc_t* h, uint64_t q, const double* covar, const char* const* names) {
+    if (!h) { set_error("null argument"); return DBTK_ERR_ARG; }
+    h->scanned = false;
+    auto drop = [](double** p) { if (*p) { (void)hipFree(*p); *p = nullptr; } };
+    if (!q) {
+        ACHK(hipSetDevice(h->device));
+        ACHK(hipStreamSynchronize(h->stream));
+        drop(&h->d_Q); drop(&h->d_bt); drop(&h->d_syyr);
+        h->q = 0;
+        return DBTK_OK;
+    }
+    if (!covar) { set_error("null argument"); return DBTK_ERR_ARG; }
+    const uint64_t n = h->n, P = h->P;
+    if (q > DBTK_ASSOC_COVAR_MAX) { set_error("dbtk_assoc_covar_set: " + std::to_string(q) + " covariates: at most DBTK_ASSOC_COVAR_MAX = " + std::to_string(DBTK_ASSOC_COVAR_MAX)); return DBTK_ERR_ARG; }
+    if (n < q + 3) {
+        set_error("dbtk_assoc_covar_set: " + std::to_string(n) + " samples and " + std::to_string(q) + " covariates: a test needs at least q + 3 samples (n - 2 - q degrees of freedom)");
+        return DBTK_ERR_ARG;
+    }
+    auto name = [&](uint64_t j) { return names && names[j] ? std::string(names[j]) : "c" + std::to_string(j); };
+    std::vector<double> c(q * n), Q(q * n);  // the samples in ascending order, as the phenotypes lie on the device
+    for (uint64_t j = 0; j < q; ++j)
+        for (uint64_t i = 0; i < n; ++i) c[j * n + i] = covar[j * n + h->ord[i]];
+    uint64_t bad = 0;
+    bool finite = true;
+    if (!dbtk_assoc_host::covar_basis(n, q, c.data(), Q.data(), &bad, &finite)) {
+        set_error("dbtk_assoc_covar_set: covariate " + name(bad) + (finite ? " is constant or collinear with the intercept and the covariates in front of it" : " has a value that is not finite"));
+        return DBTK_ERR_ARG;
+    }
+    ACHK(hipSetDevice(h->device));
+    struct Hold { double* p = nullptr; ~Hold() { if (p) (void)hipFree(p); } } dQ, dbt, dsy;
+    const std::string what = "covariate tables (basis 8 * q * n = " + std::to_string(8 * q * n) + " bytes, projections 8 * P * q = " + std::to_string(8 * P * q) + " bytes)";
+    uint64_t cap = 0;
+    { const dbtk_status_t st = regrow(&dQ.p, &cap, q * n, what.c_str()); if (st) return st; } cap = 0;
+    { const dbtk_status_t st = regrow(&dbt.p, &cap, P * q, what.c_str()); if (st) return st; } cap = 0;
+    { const dbtk_status_t st = regrow(&dsy.p, &cap, P, what.c_str()); if (st) return st; }
+    std::vector<double> syy(P), left(P);
+    ACHK(hipMemcpyAsync(dQ.p, Q.data(), q * n * 8, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_assoc_covar_pheno, dim3((uint32_t)P), dim3(64), 0, h->stream, h->d_yc, h->d_syy, dQ.p, dbt.p, dsy.p, (uint32_t)n, (uint32_t)q);
+    ACHK(hipGetLastError());
+    ACHK(hipMemcpyAsync(syy.data(), h->d_syy, P * 8, hipMemcpyDeviceToHost, h->stream));
+    ACHK(hipMemcpyAsync(left.data(), dsy.p, P * 8, hipMemcpyDeviceToHost, h->stream));
+    ACHK(hipStreamSynchronize(h->stream));
+    for (uint64_t p = 0; p < P; ++p)
+        if (!(left[p] > DBTK_ASSOC_COVAR_COLLINEAR * syy[p])) {
+            char share[32];
+            snprintf(share, sizeof share, "%.3g", left[p] / syy[p]);
+            set_error("dbtk_assoc_covar_set: phenotype " + h->names[p] + " is explained by the covariates: they leave " + share + " of its sum of squares, a test needs more than DBTK_ASSOC_COVAR_COLLINEAR = 1e-6");
+            return DBTK_ERR_ARG;
+        }
+    drop(&h->d_Q); drop(&h->d_bt); drop(&h->d_syyr);
+    h->d_Q = dQ.p; h->d_bt = dbt.p; h->d_syyr = dsy.p;
+    dQ.p = dbt.p = dsy.p = nullptr;
+    h->q = q;
+    return DBTK_OK;
 }
 
 dbtk_status_t assoc_write_impl(dbtk_assoc_t* h, const char* out_prefix) {
@@ -588,7 +710,7 @@ void dbtk_assoc_free(dbtk_assoc_t* h) {
     if (!h) return;
     if (h->stream || h->d_yc) (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* q : {(void*)h->d_sidx, (void*)h->d_yc, (void*)h->d_syy, (void*)h->d_hits, (void*)h->d_nhits, (void*)h->d_idx, (void*)h->d_items, (void*)h->d_cand})
+    for (void* q : {(void*)h->d_sidx, (void*)h->d_yc, (void*)h->d_syy, (void*)h->d_hits, (void*)h->d_nhits, (void*)h->d_idx, (void*)h->d_items, (void*)h->d_cand, (void*)h->d_Q, (void*)h->d_bt, (void*)h->d_syyr})
         if (q) (void)hipFree(q);
     for (auto& e : h->ev) if (e) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -651,6 +773,24 @@ dbtk_status_t dbtk_assoc_pvalue(double r, uint64_t n, double* p) {
     if (!p) { set_error("null argument"); return DBTK_ERR_ARG; }
     if (n < 3 || !(fabs(r) <= 1.0)) { set_error("dbtk_assoc_pvalue: n >= 3 and |r| <= 1"); return DBTK_ERR_ARG; }
     *p = dbtk_assoc_host::pvalue(r, n);
+    return DBTK_OK;
+}
+uint32_t dbtk_assoc_covar_api_version(void) { return DBTK_ASSOC_COVAR_API_VERSION; }
+dbtk_status_t dbtk_assoc_covar_basis(uint64_t n, uint64_t q, const double* covar, double* Q, uint64_t* bad_column) {
+    if (!bad_column || (q && n && (!covar || !Q))) { set_error("null argument"); return DBTK_ERR_ARG; }
+    return guarded([&]() -> dbtk_status_t {
+        bool finite = true;
+        if (dbtk_assoc_host::covar_basis(n, q, covar, Q, bad_column, &finite)) return DBTK_OK;
+        set_error("dbtk_assoc_covar_basis: column " + std::to_string(*bad_column) + (finite ? " is constant or collinear with the intercept and the columns in front of it" : " has a value that is not finite"));
+        return DBTK_ERR_ARG;
+    });
+}
+dbtk_status_t dbtk_assoc_covar_set(dbtk_assoc_t* h, uint64_t q, const double* covar, const char* const* names) {
+    return guarded([&] { return assoc_covar_set_impl(h, q, covar, names); });
+}
+dbtk_status_t dbtk_assoc_covar_get(const dbtk_assoc_t* h, uint64_t* q, uint64_t* dof) {
+    if (!h || !q || !dof) { set_error("null argument"); return DBTK_ERR_ARG; }
+    *q = h->q; *dof = h->n - 2 - h->q;
     return DBTK_OK;
 }
 dbtk_status_t dbtk_assoc_bh(const double* p, uint64_t m, double* q) {

@@ -1,6 +1,6 @@
 // dbtk_assoc_cli.h — the --assoc flags as both command lines take them (danbing-tk-pred and danbing-tk --cohort): the flag group, what
 // is checked at parse time before a device is touched, and the scans of one resident matrix table after table.
-//   --assoc PHENO.tsv OUTPREF [--assoc-pairs PAIRS.tsv] [--assoc-p X] [--assoc-raw]      (the group may be repeated)
+//   --assoc PHENO.tsv OUTPREF [--assoc-covar COVAR.tsv] [--assoc-pairs PAIRS.tsv] [--assoc-p X] [--assoc-raw]      (the group may be repeated)
 #ifndef DBTK_ASSOC_CLI_H_
 #define DBTK_ASSOC_CLI_H_
 
@@ -10,15 +10,18 @@
 #include <vector>
 
 #include "../../include/dbtk_assoc.h"
+#include "../../include/dbtk_assoc_covar.h"
+#include "dbtk_assoc_covar_host.h"
 #include "dbtk_assoc_host.h"
 
 namespace dbtk_assoc_cli {
 
 struct Group {
-    std::string pheno, prefix, pairs, pairs_text;
+    std::string pheno, prefix, pairs, pairs_text, covar;
     double p = -1.0;   // --assoc-p; negative: no hit list
     bool raw = false;  // --assoc-raw: the matrix before the bias correction
     dbtk_assoc_host::PhenoTable table;
+    dbtk_assoc_host::Covariates covariates;  // --assoc-covar: the columns of COVAR.tsv in the table's sample order
 };
 struct Options {
     std::vector<Group> groups;
@@ -46,6 +49,15 @@ inline int take_flag(Options* o, int argc, char** argv, int argi, std::string* e
         if (!g) return -1;
         if (argi + 1 >= argc) { *err = "--assoc-pairs: expected PAIRS.tsv"; return -1; }
         g->pairs = argv[argi + 1];
+        return 2;
+    }
+    if (a == "--assoc-covar") {
+        Group* g = last();
+        if (!g) return -1;
+        if (argi + 1 >= argc) { *err = "--assoc-covar: expected COVAR.tsv"; return -1; }
+        if (!g->covar.empty()) { *err = std::string("--assoc-covar: given twice for ") + g->pheno + " (" + g->covar + " and " + argv[argi + 1] + "): one covariate file per --assoc"; return -1; }
+        if (!*argv[argi + 1]) { *err = "--assoc-covar: empty file name"; return -1; }
+        g->covar = argv[argi + 1];
         return 2;
     }
     if (a == "--assoc-p") {
@@ -84,6 +96,12 @@ inline bool load(Options* o, bool dosage, std::string* err) {
             if (!dbtk_assoc_host::read_text(g.pairs, &g.pairs_text, err)) { *err = "--assoc-pairs: " + *err; return false; }
             if (!dbtk_assoc_host::parse_pairs(g.pairs_text, g.pairs, g.table.names, 0xFFFFFFFFull, nullptr, nullptr, err)) { *err = "--assoc-pairs: " + *err; return false; }
         }
+        if (!g.covar.empty()) {  // the same layout and parser as PHENO.tsv; the basis needs no device, so a collinear covariate is refused here
+            dbtk_assoc_host::PhenoTable C;
+            if (!dbtk_assoc_host::read_text(g.covar, &text, err)) { *err = "--assoc-covar: " + *err; return false; }
+            if (!dbtk_assoc_host::parse_pheno(text, g.covar, &C, err)) { *err = "--assoc-covar: " + *err; return false; }
+            if (!dbtk_assoc_host::match_covar(g.table, C, g.covar, &g.covariates, err)) { *err = "--assoc-covar: " + *err; return false; }
+        }
         for (const char* ext : {".assoc.best.tsv", ".assoc.hits.tsv"}) {
             const std::string fn = g.prefix + ext;
             FILE* f = fopen(fn.c_str(), "w");
@@ -115,6 +133,13 @@ inline bool run(Options* o, bool raw_stage, int device, uint64_t ns, uint64_t nt
             if (!dbtk_assoc_host::parse_pairs(g.pairs_text, g.pairs, T.names, ntr, &off, &idx, err)) { *err = "--assoc-pairs: " + *err; ok = false; }
             else if (dbtk_assoc_set_pairs(h, ntr, off.data(), idx.data())) { *err = "--assoc-pairs: " + std::string(dbtk_last_error()); ok = false; }
         }
+        if (ok && !g.covar.empty()) {
+            std::vector<const char*> cn;
+            for (const std::string& s : g.covariates.names) cn.push_back(s.c_str());
+            uint64_t q = 0, dof = 0;
+            if (dbtk_assoc_covar_set(h, cn.size(), g.covariates.values.data(), cn.data()) || dbtk_assoc_covar_get(h, &q, &dof)) { *err = "--assoc-covar: " + g.covar + ": " + dbtk_last_error(); ok = false; }
+            else fprintf(stderr, "# assoc %s: n %zu, %llu covariates, dof %llu\n", g.prefix.c_str(), T.sample_of.size(), (unsigned long long)q, (unsigned long long)dof);
+        }
         if (ok && scan(h, g.p)) { *err = "--assoc: " + g.pheno + ": " + dbtk_last_error(); ok = false; }
         if (ok && dbtk_assoc_write(h, g.prefix.c_str())) { *err = "--assoc: " + std::string(dbtk_last_error()); ok = false; }
         if (ok && log) {
@@ -130,13 +155,16 @@ inline bool run(Options* o, bool raw_stage, int device, uint64_t ns, uint64_t nt
 }
 
 inline const char* usage() {
-    return "  --assoc <PHENO.tsv> <OUTPREF> [--assoc-pairs <PAIRS.tsv>] [--assoc-p <X>] [--assoc-raw]\n"
+    return "  --assoc <PHENO.tsv> <OUTPREF> [--assoc-covar <COVAR.tsv>] [--assoc-pairs <PAIRS.tsv>] [--assoc-p <X>] [--assoc-raw]\n"
            "                  association scan of the matrix (or the dosage values) while it lies in HBM: every row against the\n"
            "                  phenotypes of PHENO.tsv (id <TAB> NAME_1 ... / sample position <TAB> values; samples not listed are\n"
            "                  masked out), or against the phenotypes PAIRS.tsv (LOCUS <TAB> NAME) gives its locus; writes\n"
            "                  OUTPREF.assoc.best.tsv (best row per phenotype, Bonferroni and Benjamini-Hochberg) and, with\n"
            "                  --assoc-p, OUTPREF.assoc.hits.tsv (every pair with p <= X); --assoc-raw scans before the bias\n"
-           "                  correction; the group may be repeated, one scan per table\n";
+           "                  correction; --assoc-covar regresses the covariates of COVAR.tsv (the layout of PHENO.tsv, the same\n"
+           "                  samples, at most 128 columns) out of the rows and the phenotypes on the device: r is then the partial\n"
+           "                  correlation, t and p those of y ~ 1 + C + x with n - 2 - q degrees of freedom; the group may be\n"
+           "                  repeated, one scan per table, each with its own covariates\n";
 }
 
 }  // namespace dbtk_assoc_cli

@@ -198,10 +198,11 @@ void usage() {
             "                         locus has no invariant k-mers), and the bias table of --pred; neither needs the genotype matrix,\n"
             "                         so the cohort's size is not bounded by it\n"
             "  --no-trkmc             with --pred, --kms or --dosage: write no per-sample files at all\n"
-            "  --assoc <PHENO.tsv> <OUTPREF> [--assoc-pairs <PAIRS.tsv>] [--assoc-p <X>] [--assoc-raw]\n"
+            "  --assoc <PHENO.tsv> <OUTPREF> [--assoc-covar <COVAR.tsv>] [--assoc-pairs <PAIRS.tsv>] [--assoc-p <X>] [--assoc-raw]\n"
             "                         with --cohort and --pred or --dosage: after the last sample, what danbing-tk-pred --assoc makes of the\n"
             "                         matrix (with --pred) or of the dosage values: OUTPREF.assoc.best.tsv, with --assoc-p OUTPREF.assoc.hits.tsv;\n"
-            "                         the group may be repeated\n"
+            "                         --assoc-covar regresses COVAR.tsv's covariates out of rows and phenotypes on the device (partial\n"
+            "                         correlation, n - 2 - q degrees of freedom); the group may be repeated, each with its own covariates\n"
             "Developer:\n"
             "  -s <1|2>  -e <1|2>  -v <INT>  -g|-gc|-gcc <INT> [INT]  -a  -ae  -tb  -ik  -t <INT>  -m <FILE>  -au\n\n");
 }

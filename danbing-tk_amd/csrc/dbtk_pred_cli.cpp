@@ -5,7 +5,7 @@
 // The second form makes the per-locus tables alone (dbtk_dosage_*): the matrix is never allocated, in HBM or on the host.
 //   danbing-tk-pred --window-rows R | --window-bytes N <INPUT1> <INPUT2> <OUTPUT1> <OUTPUT2> <OUTPUT3>
 // The first form for a cohort whose matrix fits neither: whole loci of at most R k-mers at a time (windowed()), the same three files.
-//   danbing-tk-pred --assoc PHENO.tsv OUTPREF [--assoc-pairs PAIRS.tsv] [--assoc-p X] [--assoc-raw] ... <either of the first two forms>
+//   danbing-tk-pred --assoc PHENO.tsv OUTPREF [--assoc-covar COVAR.tsv] [--assoc-pairs PAIRS.tsv] [--assoc-p X] [--assoc-raw] ... <either of the first two forms>
 // The association scan of the resident matrix or dosage table (dbtk_assoc_cli.h); the other outputs are unchanged by it.
 #include <fcntl.h>
 #include <stdint.h>

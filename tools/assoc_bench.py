@@ -5,7 +5,9 @@ Prints, per (ns, ppl): k_assoc_scan's HIP-event time (median of 5 after 2 warm-u
 against the 8 TB/s roofline, the FP64 multiply-add rate reached ((ppl + 2) * nk * n multiply-adds, the algorithm's count), and beside
 them k_pred_correct's time on the same matrix from the same run (dbtk_pred_times), the yardstick of a one-pass stream (it reads AND
 writes G: 8 bytes per entry).
-    python tools/assoc_bench.py [--ns 256,879] [--ppl 5,20] [--ntr 20000] [--kpl 184]
+    python tools/assoc_bench.py [--ns 256,879] [--ppl 5,20] [--ntr 20000] [--kpl 184] [--covar 0,10,60]
+--covar Q: the same scans with Q covariates regressed out on the device (include/dbtk_assoc_covar.h; 0: none); the multiply-add count
+then has Q more dot products per row, (ppl + 2 + Q) * nk * n, and Q more per (row, phenotype) pair.
     python tools/assoc_bench.py --workflow [--ns 256] [--ntr 2000]
 --workflow: what the scan replaces.  The corrected matrix is copied to the host and written to /dev/shm in danbing-tk-pred's layout, read
 back, and a 16-thread numpy loop (one locus per task, the formulas of tests/assoc_model.py without the p-values) makes the same r; beside
@@ -56,7 +58,7 @@ def tables(ns, ntr, ppl, seed=2):
     return pheno, off, idx
 
 
-def rates(lib, nss, ppls, ntr, kpl):
+def rates(lib, nss, ppls, ntr, kpl, covars=(0,)):
     for ns in nss:
         P, nk_cum, nk = cohort(lib, ns, ntr, kpl)
         cor_ms = P.times()[2]
@@ -67,16 +69,18 @@ def rates(lib, nss, ppls, ntr, kpl):
             pheno, off, idx = tables(ns, ntr, ppl)
             A = pkg.Assoc(lib, ns, np.arange(ns), pheno)
             A.set_pairs(off, idx)
-            ms, fold = [], []
-            for _ in range(7):
-                A.scan_pred(P, p_threshold=1e-6)
-                t = A.times()
-                ms.append(t[0]); fold.append(t[1])
-            k = float(np.median(ms[2:]))
-            fma = (ppl + 2.0) * nk * ns
-            print(f"  {ppl:3d} phenotypes per locus: k_assoc_scan {k:.3f} ms (min {min(ms[2:]):.3f}, max {max(ms[2:]):.3f}) = {gbytes / k / 1e9:.2f} TB/s of G "
-                  f"({gbytes / k / 1e9 / 8:.1%} of 8 TB/s), {fma / k / 1e9:.2f} T FP64 multiply-adds/s; {k / cor_ms:.2f} x k_pred_correct; host fold {np.median(fold[2:]):.1f} ms; "
-                  f"{len(A.hits())} hits", flush=True)
+            for q in covars:
+                A.set_covariates(np.random.default_rng(3).normal(0, 1, (q, ns)) if q else None)
+                ms, fold = [], []
+                for _ in range(7):
+                    A.scan_pred(P, p_threshold=1e-6)
+                    t = A.times()
+                    ms.append(t[0]); fold.append(t[1])
+                k = float(np.median(ms[2:]))
+                fma = (ppl + 2.0 + q) * nk * ns + float(q) * ppl * nk
+                print(f"  {ppl:3d} phenotypes per locus, {q:3d} covariates: k_assoc_scan {k:.3f} ms (min {min(ms[2:]):.3f}, max {max(ms[2:]):.3f}) = {gbytes / k / 1e9:.2f} TB/s of G "
+                      f"({gbytes / k / 1e9 / 8:.1%} of 8 TB/s), {fma / k / 1e9:.2f} T FP64 multiply-adds/s; {k / cor_ms:.2f} x k_pred_correct; host fold {np.median(fold[2:]):.1f} ms; "
+                      f"{len(A.hits())} hits", flush=True)
             A.close()
         P.close()
 
@@ -134,6 +138,7 @@ def main():
     ap.add_argument("--ppl", default="5,20")
     ap.add_argument("--ntr", type=int, default=None)
     ap.add_argument("--kpl", type=int, default=184)
+    ap.add_argument("--covar", default="0")
     ap.add_argument("--workflow", action="store_true")
     a = ap.parse_args()
     import torch  # noqa: F401  (before libdbtk_hip.so is loaded, so that both bind to the one HIP runtime: INTEGRATION.md 5)
@@ -141,7 +146,7 @@ def main():
     if a.workflow:
         workflow(lib, int((a.ns or "256").split(",")[0]), a.ntr or 2000, a.kpl)
     else:
-        rates(lib, [int(v) for v in (a.ns or "256,879").split(",")], [int(v) for v in a.ppl.split(",")], a.ntr or 20000, a.kpl)
+        rates(lib, [int(v) for v in (a.ns or "256,879").split(",")], [int(v) for v in a.ppl.split(",")], a.ntr or 20000, a.kpl, [int(v) for v in a.covar.split(",")])
 
 
 if __name__ == "__main__":
