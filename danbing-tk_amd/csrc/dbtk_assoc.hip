@@ -17,18 +17,10 @@
 #include "../../include/dbtk_assoc_covar.h"
 #include "dbtk_assoc_covar_host.h"
 #include "dbtk_assoc_host.h"
+#include "dbtk_dev.h"
 #include "dbtk_internal.h"
 
 using namespace dbtk;
-
-#define ACHK(call)                                                                                    \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) {                                                                       \
-            set_error(std::string(#call) + ": " + hipGetErrorString(e_));                             \
-            return DBTK_ERR_HIP;                                                                      \
-        }                                                                                             \
-    } while (0)
 
 namespace {
 
@@ -349,26 +341,26 @@ struct dbtk_assoc {
     uint64_t ns = 0, P = 0, n = 0;
     bool ident = false;               // the mask is every sample: no index list
     std::vector<std::string> names;
-    uint32_t* d_sidx = nullptr;
-    double *d_yc = nullptr, *d_syy = nullptr;
-    AsHit* d_hits = nullptr;
-    unsigned long long* d_nhits = nullptr;
     uint64_t hit_cap = 0;
-    // the pair list
+    // the pair list (d_idx)
     bool pairs = false;
     uint64_t ntr = 0;
     std::vector<uint64_t> off;
     std::vector<uint32_t> idx;
-    uint32_t* d_idx = nullptr;
-    // the covariates (dbtk_assoc_covar.h); q == 0: none
+    // the covariates (dbtk_assoc_covar.h; d_Q, d_bt, d_syyr); q == 0: none
     std::vector<uint64_t> ord;        // ord[j]: the position in sample_of of the j-th sample in ascending order
     uint64_t q = 0;
-    double *d_Q = nullptr, *d_bt = nullptr, *d_syyr = nullptr;
-    // per scan, regrown
-    AsItem* d_items = nullptr; uint64_t items_cap = 0;
-    AsCand* d_cand = nullptr; uint64_t cand_cap = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    // the device side (destroyed last to first: the tables from d_sidx on, then the events, the stream behind them all)
+    DevStream stream;
+    DevEvent ev[2];
+    DevArr<double> d_syyr, d_bt, d_Q;
+    DevArr<AsCand> d_cand;            // per scan, regrown (and d_items)
+    DevArr<AsItem> d_items;
+    DevArr<uint32_t> d_idx;
+    DevArr<unsigned long long> d_nhits;
+    DevArr<AsHit> d_hits;
+    DevArr<double> d_syy, d_yc;
+    DevArr<uint32_t> d_sidx;
     // the scan made last
     bool scanned = false, with_hits = false;
     std::vector<dbtk_assoc_best_t> best;
@@ -382,10 +374,8 @@ uint32_t locus_of(const std::vector<uint32_t>& nkc, uint64_t row) {
     const auto it = std::upper_bound(nkc.begin(), nkc.end(), (uint32_t)row);  // the first locus whose cumulative count passes the row
     return it == nkc.end() ? DBTK_ASSOC_NONE : (uint32_t)(it - nkc.begin());
 }
-template <class T> dbtk_status_t regrow(T** p, uint64_t* cap, uint64_t need, const char* what) {
-    if (need <= *cap) return DBTK_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    const hipError_t e = hipMalloc(p, need * sizeof(T));
+template <class T> dbtk_status_t regrow(DevArr<T>& a, uint64_t need, const char* what) {
+    const hipError_t e = a.reserve(need, need);
     if (e == hipErrorOutOfMemory) {
         (void)hipGetLastError();
         size_t fr = 0, tot = 0;
@@ -394,7 +384,6 @@ template <class T> dbtk_status_t regrow(T** p, uint64_t* cap, uint64_t need, con
         return DBTK_ERR_NOMEM;
     }
     if (e != hipSuccess) { set_error(std::string("hipMalloc (") + what + "): " + hipGetErrorString(e)); return DBTK_ERR_HIP; }
-    *cap = need;
     return DBTK_OK;
 }
 
@@ -441,26 +430,25 @@ dbtk_status_t assoc_create_impl(int device_id, uint64_t ns, uint64_t P, uint64_t
         if (!(ss > 0.0) || !std::isfinite(ss)) { set_error("dbtk_assoc_create: phenotype " + h->names[p] + " has a sum of squares that is 0 or overflows in float64"); return DBTK_ERR_ARG; }
     }
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device (the library has no CPU path)"); return DBTK_ERR_NO_DEVICE; }
+    if (const dbtk_status_t nd = device_count(&ndev)) return nd;
     if (device_id < 0 || device_id >= ndev) { set_error("device_id out of range"); return DBTK_ERR_ARG; }
-    ACHK(hipSetDevice(device_id));
+    DEVCHK(hipSetDevice(device_id));
     h->device = device_id; h->ns = ns; h->P = P; h->n = n; h->hit_cap = hit_cap;
     h->ident = n == ns;
     h->ord = ord;
-    ACHK(hipStreamCreate(&h->stream));
-    for (auto& e : h->ev) ACHK(hipEventCreate(&e));
+    DEVCHK(h->stream.create(hipStreamDefault));
+    for (DevEvent& e : h->ev) DEVCHK(e.create(hipEventDefault));
     const std::string what = "association tables (phenotypes 8 * P * n = " + std::to_string(8 * P * n) + " bytes, hit buffer 16 * DBTK_ASSOC_HITS = " + std::to_string(16 * hit_cap) + " bytes)";
-    uint64_t cap = 0;
-    { const dbtk_status_t st = regrow(&h->d_yc, &cap, P * n, what.c_str()); if (st) return st; } cap = 0;
-    { const dbtk_status_t st = regrow(&h->d_syy, &cap, P, what.c_str()); if (st) return st; } cap = 0;
-    { const dbtk_status_t st = regrow(&h->d_sidx, &cap, n, what.c_str()); if (st) return st; } cap = 0;
-    { const dbtk_status_t st = regrow(&h->d_hits, &cap, hit_cap, what.c_str()); if (st) return st; } cap = 0;
-    { const dbtk_status_t st = regrow(&h->d_nhits, &cap, 1, what.c_str()); if (st) return st; }
-    ACHK(hipMemcpyAsync(h->d_yc, y.data(), P * n * 8, hipMemcpyHostToDevice, h->stream));
-    ACHK(hipMemcpyAsync(h->d_sidx, sidx.data(), n * 4, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_assoc_pheno, dim3((uint32_t)P), dim3(64), 0, h->stream, h->d_yc, h->d_syy, (uint32_t)n);
-    ACHK(hipGetLastError());
-    ACHK(hipStreamSynchronize(h->stream));
+    { const dbtk_status_t st = regrow(h->d_yc, P * n, what.c_str()); if (st) return st; }
+    { const dbtk_status_t st = regrow(h->d_syy, P, what.c_str()); if (st) return st; }
+    { const dbtk_status_t st = regrow(h->d_sidx, n, what.c_str()); if (st) return st; }
+    { const dbtk_status_t st = regrow(h->d_hits, hit_cap, what.c_str()); if (st) return st; }
+    { const dbtk_status_t st = regrow(h->d_nhits, 1, what.c_str()); if (st) return st; }
+    DEVCHK(hipMemcpyAsync(h->d_yc, y.data(), P * n * 8, hipMemcpyHostToDevice, h->stream));
+    DEVCHK(hipMemcpyAsync(h->d_sidx, sidx.data(), n * 4, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_assoc_pheno, dim3((uint32_t)P), dim3(64), 0, h->stream, h->d_yc.get(), h->d_syy.get(), (uint32_t)n);
+    DEVCHK(hipGetLastError());
+    DEVCHK(hipStreamSynchronize(h->stream));
     *out = hold.release();
     return DBTK_OK;
 }
@@ -484,11 +472,11 @@ dbtk_status_t assoc_set_pairs_impl(dbtk_assoc_t* h, uint64_t ntr, const uint64_t
         x.insert(x.end(), v.begin(), v.end());
         o[t + 1] = x.size();
     }
-    ACHK(hipSetDevice(h->device));
-    if (h->d_idx) { (void)hipFree(h->d_idx); h->d_idx = nullptr; }
-    ACHK(hipMalloc(&h->d_idx, (x.size() + 1) * 4));
-    if (!x.empty()) ACHK(hipMemcpy(h->d_idx, x.data(), x.size() * 4, hipMemcpyHostToDevice));
-    h->pairs = true; h->ntr = ntr; h->off.swap(o); h->idx.swap(x);
+    DEVCHK(hipSetDevice(h->device));
+    DevArr<uint32_t> d_idx;  // (made whole before the handle sees it: a failure leaves the old pair list as it was)
+    DEVCHK(d_idx.alloc(x.size() + 1));
+    if (!x.empty()) DEVCHK(hipMemcpy(d_idx, x.data(), x.size() * 4, hipMemcpyHostToDevice));
+    h->d_idx = std::move(d_idx); h->pairs = true; h->ntr = ntr; h->off.swap(o); h->idx.swap(x);
     return DBTK_OK;
 }
 
@@ -509,14 +497,7 @@ dbtk_status_t assoc_scan_impl(dbtk_assoc_t* h, const float* d_rows, uint64_t nro
         for (uint64_t t = 0; t < ntr; ++t)
             if (nkc[t] > nrows || (t && nkc[t] < nkc[t - 1])) { set_error("dbtk_assoc_scan: the cumulative row counts decrease or pass the " + std::to_string(nrows) + " rows at locus " + std::to_string(t)); return DBTK_ERR_ARG; }
     }
-    {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, d_rows) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != h->device) {
-            (void)hipGetLastError();
-            set_error("dbtk_assoc_scan: the rows are not device memory of the handle's device");
-            return DBTK_ERR_ARG;
-        }
-    }
+    if (!is_device_memory_of(d_rows, h->device)) { set_error("dbtk_assoc_scan: the rows are not device memory of the handle's device"); return DBTK_ERR_ARG; }
     // the work items
     std::vector<AsItem> items;
     uint64_t ncand = 0;
@@ -532,35 +513,35 @@ dbtk_status_t assoc_scan_impl(dbtk_assoc_t* h, const float* d_rows, uint64_t nro
     const bool want_hits = p_threshold >= 0.0;
     const uint64_t neff = h->n - h->q;  // with covariates every test has n - 2 - q degrees of freedom: the closed forms take n - q for n
     const double r2crit = want_hits ? dbtk_assoc_host::r2_threshold(p_threshold, neff) : 2.0;
-    ACHK(hipSetDevice(h->device));
+    DEVCHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     std::vector<AsCand> cand(ncand);
     unsigned long long nhits = 0;
     h->ms[0] = 0;
     if (!items.empty()) {
-        { const dbtk_status_t st = regrow(&h->d_items, &h->items_cap, items.size(), "association work items"); if (st) return st; }
-        { const dbtk_status_t st = regrow(&h->d_cand, &h->cand_cap, ncand, "association candidates"); if (st) return st; }
-        ACHK(hipMemcpyAsync(h->d_items, items.data(), items.size() * sizeof(AsItem), hipMemcpyHostToDevice, s));
-        ACHK(hipMemsetAsync(h->d_nhits, 0, 8, s));
+        { const dbtk_status_t st = regrow(h->d_items, items.size(), "association work items"); if (st) return st; }
+        { const dbtk_status_t st = regrow(h->d_cand, ncand, "association candidates"); if (st) return st; }
+        DEVCHK(hipMemcpyAsync(h->d_items, items.data(), items.size() * sizeof(AsItem), hipMemcpyHostToDevice, s));
+        DEVCHK(hipMemsetAsync(h->d_nhits, 0, 8, s));
         AsArgs a;
-        a.G = d_rows; a.ns = h->ns; a.n = (uint32_t)h->n; a.sidx = h->d_sidx; a.yc = h->d_yc; a.syy = h->q ? h->d_syyr : h->d_syy;
+        a.G = d_rows; a.ns = h->ns; a.n = (uint32_t)h->n; a.sidx = h->d_sidx; a.yc = h->d_yc; a.syy = h->q ? h->d_syyr.get() : h->d_syy.get();
         a.q = (uint32_t)h->q; a.Q = h->d_Q; a.bt = h->d_bt;
-        a.items = h->d_items; a.nitems = (uint32_t)items.size(); a.ph_idx = h->pairs ? h->d_idx : nullptr; a.cand = h->d_cand;
+        a.items = h->d_items; a.nitems = (uint32_t)items.size(); a.ph_idx = h->pairs ? h->d_idx.get() : nullptr; a.cand = h->d_cand;
         a.hits = h->d_hits; a.nhits = h->d_nhits; a.hit_cap = h->hit_cap; a.r2crit = r2crit;
         const uint32_t grid = (uint32_t)std::min<uint64_t>(items.size(), AS_GRID);
-        ACHK(hipEventRecord(h->ev[0], s));
+        DEVCHK(hipEventRecord(h->ev[0], s));
         if (h->q) {
             if (h->ident) hipLaunchKernelGGL((k_assoc_scan<true, true>), dim3(grid), dim3(AS_WAVES * 64), 0, s, a);
             else hipLaunchKernelGGL((k_assoc_scan<false, true>), dim3(grid), dim3(AS_WAVES * 64), 0, s, a);
         } else if (h->ident) hipLaunchKernelGGL((k_assoc_scan<true, false>), dim3(grid), dim3(AS_WAVES * 64), 0, s, a);
         else hipLaunchKernelGGL((k_assoc_scan<false, false>), dim3(grid), dim3(AS_WAVES * 64), 0, s, a);
-        ACHK(hipGetLastError());
-        ACHK(hipEventRecord(h->ev[1], s));
-        ACHK(hipMemcpyAsync(cand.data(), h->d_cand, ncand * sizeof(AsCand), hipMemcpyDeviceToHost, s));
-        ACHK(hipMemcpyAsync(&nhits, h->d_nhits, 8, hipMemcpyDeviceToHost, s));
-        ACHK(hipStreamSynchronize(s));
+        DEVCHK(hipGetLastError());
+        DEVCHK(hipEventRecord(h->ev[1], s));
+        DEVCHK(hipMemcpyAsync(cand.data(), h->d_cand, ncand * sizeof(AsCand), hipMemcpyDeviceToHost, s));
+        DEVCHK(hipMemcpyAsync(&nhits, h->d_nhits, 8, hipMemcpyDeviceToHost, s));
+        DEVCHK(hipStreamSynchronize(s));
         float ms = 0;
-        ACHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+        DEVCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
         h->ms[0] = ms;
     }
     const auto t0 = std::chrono::steady_clock::now();
@@ -601,7 +582,7 @@ dbtk_status_t assoc_scan_impl(dbtk_assoc_t* h, const float* d_rows, uint64_t nro
         st = DBTK_ERR_OVERFLOW;
     } else if (want_hits && nhits) {
         std::vector<AsHit> raw(nhits);
-        ACHK(hipMemcpy(raw.data(), h->d_hits, nhits * sizeof(AsHit), hipMemcpyDeviceToHost));
+        DEVCHK(hipMemcpy(raw.data(), h->d_hits, nhits * sizeof(AsHit), hipMemcpyDeviceToHost));
         std::sort(raw.begin(), raw.end(), [](const AsHit& a, const AsHit& b) { return a.ph != b.ph ? a.ph < b.ph : a.row < b.row; });
         h->hits.resize(nhits);
         for (uint64_t i = 0; i < nhits; ++i) {
@@ -619,11 +600,10 @@ dbtk_status_t assoc_scan_impl(dbtk_assoc_t* h, const float* d_rows, uint64_t nro
 dbtk_status_t assoc_covar_set_impl(dbtk_assoc_t* h, uint64_t q, const double* covar, const char* const* names) {
     if (!h) { set_error("null argument"); return DBTK_ERR_ARG; }
     h->scanned = false;
-    auto drop = [](double** p) { if (*p) { (void)hipFree(*p); *p = nullptr; } };
     if (!q) {
-        ACHK(hipSetDevice(h->device));
-        ACHK(hipStreamSynchronize(h->stream));
-        drop(&h->d_Q); drop(&h->d_bt); drop(&h->d_syyr);
+        DEVCHK(hipSetDevice(h->device));
+        DEVCHK(hipStreamSynchronize(h->stream));
+        h->d_Q.drop(); h->d_bt.drop(); h->d_syyr.drop();
         h->q = 0;
         return DBTK_OK;
     }
@@ -644,20 +624,19 @@ dbtk_status_t assoc_covar_set_impl(dbtk_assoc_t* h, uint64_t q, const double* co
         set_error("dbtk_assoc_covar_set: covariate " + name(bad) + (finite ? " is constant or collinear with the intercept and the covariates in front of it" : " has a value that is not finite"));
         return DBTK_ERR_ARG;
     }
-    ACHK(hipSetDevice(h->device));
-    struct Hold { double* p = nullptr; ~Hold() { if (p) (void)hipFree(p); } } dQ, dbt, dsy;
+    DEVCHK(hipSetDevice(h->device));
+    DevArr<double> dQ, dbt, dsy;
     const std::string what = "covariate tables (basis 8 * q * n = " + std::to_string(8 * q * n) + " bytes, projections 8 * P * q = " + std::to_string(8 * P * q) + " bytes)";
-    uint64_t cap = 0;
-    { const dbtk_status_t st = regrow(&dQ.p, &cap, q * n, what.c_str()); if (st) return st; } cap = 0;
-    { const dbtk_status_t st = regrow(&dbt.p, &cap, P * q, what.c_str()); if (st) return st; } cap = 0;
-    { const dbtk_status_t st = regrow(&dsy.p, &cap, P, what.c_str()); if (st) return st; }
+    { const dbtk_status_t st = regrow(dQ, q * n, what.c_str()); if (st) return st; }
+    { const dbtk_status_t st = regrow(dbt, P * q, what.c_str()); if (st) return st; }
+    { const dbtk_status_t st = regrow(dsy, P, what.c_str()); if (st) return st; }
     std::vector<double> syy(P), left(P);
-    ACHK(hipMemcpyAsync(dQ.p, Q.data(), q * n * 8, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_assoc_covar_pheno, dim3((uint32_t)P), dim3(64), 0, h->stream, h->d_yc, h->d_syy, dQ.p, dbt.p, dsy.p, (uint32_t)n, (uint32_t)q);
-    ACHK(hipGetLastError());
-    ACHK(hipMemcpyAsync(syy.data(), h->d_syy, P * 8, hipMemcpyDeviceToHost, h->stream));
-    ACHK(hipMemcpyAsync(left.data(), dsy.p, P * 8, hipMemcpyDeviceToHost, h->stream));
-    ACHK(hipStreamSynchronize(h->stream));
+    DEVCHK(hipMemcpyAsync(dQ, Q.data(), q * n * 8, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_assoc_covar_pheno, dim3((uint32_t)P), dim3(64), 0, h->stream, h->d_yc.get(), h->d_syy.get(), dQ.get(), dbt.get(), dsy.get(), (uint32_t)n, (uint32_t)q);
+    DEVCHK(hipGetLastError());
+    DEVCHK(hipMemcpyAsync(syy.data(), h->d_syy, P * 8, hipMemcpyDeviceToHost, h->stream));
+    DEVCHK(hipMemcpyAsync(left.data(), dsy, P * 8, hipMemcpyDeviceToHost, h->stream));
+    DEVCHK(hipStreamSynchronize(h->stream));
     for (uint64_t p = 0; p < P; ++p)
         if (!(left[p] > DBTK_ASSOC_COVAR_COLLINEAR * syy[p])) {
             char share[32];
@@ -665,9 +644,7 @@ dbtk_status_t assoc_covar_set_impl(dbtk_assoc_t* h, uint64_t q, const double* co
             set_error("dbtk_assoc_covar_set: phenotype " + h->names[p] + " is explained by the covariates: they leave " + share + " of its sum of squares, a test needs more than DBTK_ASSOC_COVAR_COLLINEAR = 1e-6");
             return DBTK_ERR_ARG;
         }
-    drop(&h->d_Q); drop(&h->d_bt); drop(&h->d_syyr);
-    h->d_Q = dQ.p; h->d_bt = dbt.p; h->d_syyr = dsy.p;
-    dQ.p = dbt.p = dsy.p = nullptr;
+    h->d_Q = std::move(dQ); h->d_bt = std::move(dbt); h->d_syyr = std::move(dsy);
     h->q = q;
     return DBTK_OK;
 }
@@ -710,10 +687,6 @@ void dbtk_assoc_free(dbtk_assoc_t* h) {
     if (!h) return;
     if (h->stream || h->d_yc) (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* q : {(void*)h->d_sidx, (void*)h->d_yc, (void*)h->d_syy, (void*)h->d_hits, (void*)h->d_nhits, (void*)h->d_idx, (void*)h->d_items, (void*)h->d_cand, (void*)h->d_Q, (void*)h->d_bt, (void*)h->d_syyr})
-        if (q) (void)hipFree(q);
-    for (auto& e : h->ev) if (e) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
 

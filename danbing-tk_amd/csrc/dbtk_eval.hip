@@ -11,18 +11,10 @@
 
 #include "../../include/dbtk_eval.h"
 #include "dbtk_eval.h"
+#include "dbtk_dev.h"
 #include "dbtk_internal.h"
 
 using namespace dbtk;
-
-#define ECHK(call)                                                                                    \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) {                                                                       \
-            set_error(std::string(#call) + ": " + hipGetErrorString(e_));                             \
-            return DBTK_ERR_HIP;                                                                      \
-        }                                                                                             \
-    } while (0)
 
 namespace {
 
@@ -147,18 +139,19 @@ struct dbtk_eval {
     uint32_t ksize = 0;
     void* tables = nullptr;  // tables_release
     EvalTables T{nullptr, 0, 0, nullptr, 0, 0};  // the shared class table, and the handle's own table of the k-mers in both sets
-    ClsSlot* d_both = nullptr;
     uint64_t nboth = 0;
-    hipStream_t stream = nullptr;
-    uint64_t* d_truth = nullptr;    // [nk], then the look-up counter
-    uint64_t* d_windows = nullptr;  // [nloci]
-    uint64_t* d_beg = nullptr;      // [nloci + 1]
-    uint32_t* d_list = nullptr;     // the loci of up to EV_SMALL k-mers, then the others
     uint32_t nsmall = 0, nlarge = 0;
-    EvalSums* d_sums = nullptr;     // [nloci]
-    uint32_t* d_ovf = nullptr;
-    uint64_t* d_scratch = nullptr;  // [nk]: dbtk_eval_score_host
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    // (members are destroyed last to first: the buffers from d_both on, then the events, the stream behind them all)
+    DevStream stream;
+    DevEvent ev[2];
+    DevArr<uint64_t> d_scratch;  // [nk]: dbtk_eval_score_host
+    DevArr<uint32_t> d_ovf;
+    DevArr<EvalSums> d_sums;     // [nloci]
+    DevArr<uint32_t> d_list;     // the loci of up to EV_SMALL k-mers, then the others
+    DevArr<uint64_t> d_beg;      // [nloci + 1]
+    DevArr<uint64_t> d_windows;  // [nloci]
+    DevArr<uint64_t> d_truth;    // [nk], then the look-up counter
+    DevArr<ClsSlot> d_both;
     bool windows_given = true;      // false after dbtk_eval_truth_set without windows: windows = Sx
     bool scored = false;
     std::vector<dbtk_eval_sums_t> sums;
@@ -170,27 +163,20 @@ namespace {
 void eval_release(dbtk_eval* e) {
     if (e->device >= 0) (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    void* ptrs[] = {e->d_both, e->d_truth, e->d_windows, e->d_beg, e->d_list, e->d_sums, e->d_ovf, e->d_scratch};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (hipEvent_t v : e->ev) if (v) (void)hipEventDestroy(v);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
-    tables_release(e->tables);
+    void* const tables = e->tables;
     delete e;
+    tables_release(tables);
 }
 
-template <class T> dbtk_status_t eval_alloc(T** p, uint64_t n, const char* what) {
-    *p = nullptr;
-    if (hipMalloc((void**)p, std::max<uint64_t>(n, 1) * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        set_error(std::string("genotype score: no device memory for ") + what + " (" + std::to_string(n * sizeof(T)) + " bytes)");
-        return DBTK_ERR_NOMEM;
-    }
-    return DBTK_OK;
+template <class T> dbtk_status_t eval_alloc(DevArr<T>& a, uint64_t n, const char* what) {
+    if (a.alloc(std::max<uint64_t>(n, 1)) == hipSuccess) return DBTK_OK;  // (never empty)
+    (void)hipGetLastError();
+    set_error(std::string("genotype score: no device memory for ") + what + " (" + std::to_string(n * sizeof(T)) + " bytes)");
+    return DBTK_ERR_NOMEM;
 }
 
 // EvalTables::both of a handle whose class table stands: the both-set k-mers found on the device (k_eval_both), hashed on the host
-// (they are few) and uploaded.  Its temporaries are freed on every way out.
+// (they are few) and uploaded.
 dbtk_status_t eval_build_both(dbtk_eval* e) {
     const dbtk_rpgg* g = e->g;
     const uint64_t n = g->tr_ks.size();
@@ -199,38 +185,33 @@ dbtk_status_t eval_build_both(dbtk_eval* e) {
         if (g->out_slot.size() != n || g->tr_cnt.size() != e->nloci) { set_error("dbtk_eval_create: the RPGG handle's output order does not match its TR k-mers"); return DBTK_ERR_ARG; }
         std::vector<uint64_t> fbeg(e->nloci + 1, 0);
         for (uint64_t l = 0; l < e->nloci; ++l) fbeg[l + 1] = fbeg[l] + g->tr_cnt[l];
-        uint64_t *d_ks = nullptr, *d_slot = nullptr, *d_fbeg = nullptr;
-        unsigned long long* d_cnt = nullptr;
-        ClsSlot* d_list = nullptr;
-        const dbtk_status_t st = [&]() -> dbtk_status_t {
-            dbtk_status_t a;
-            if ((a = eval_alloc(&d_ks, n, "the TR k-mers"))) return a;
-            if ((a = eval_alloc(&d_slot, n, "the TR k-mers' counters"))) return a;
-            if ((a = eval_alloc(&d_fbeg, e->nloci + 1, "the loci's first TR k-mers"))) return a;
-            if ((a = eval_alloc(&d_cnt, 1, "a counter"))) return a;
-            ECHK(hipMemcpy(d_ks, g->tr_ks.data(), n * 8, hipMemcpyHostToDevice));
-            ECHK(hipMemcpy(d_slot, g->out_slot.data(), n * 8, hipMemcpyHostToDevice));
-            ECHK(hipMemcpy(d_fbeg, fbeg.data(), (e->nloci + 1) * 8, hipMemcpyHostToDevice));
-            const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)e->num_cu * 8);
-            unsigned long long cnt = 0;
-            for (int pass = 0; pass < 2; ++pass) {
-                const uint64_t cap = pass ? cnt : 0;
-                if (pass && !cnt) break;
-                if (pass && (a = eval_alloc(&d_list, cap, "the k-mers in both sets"))) return a;
-                ECHK(hipMemsetAsync(d_cnt, 0, 8, e->stream));
-                hipLaunchKernelGGL(k_eval_both, dim3(grid), dim3(256), 0, e->stream, d_ks, d_slot, d_fbeg, (uint32_t)e->nloci, n, e->T.cls, e->T.cls_mask, e->T.cls_shift, d_list, cap, d_cnt);
-                ECHK(hipGetLastError());
-                ECHK(hipMemcpyAsync(&cnt, d_cnt, 8, hipMemcpyDeviceToHost, e->stream));
-                ECHK(hipStreamSynchronize(e->stream));
-                if (pass && cnt != cap) { set_error("dbtk_eval_create: the class table changed between two passes"); return DBTK_ERR_HIP; }
-            }
-            found.resize(cnt);
-            if (cnt) ECHK(hipMemcpy(found.data(), d_list, cnt * sizeof(ClsSlot), hipMemcpyDeviceToHost));
-            return DBTK_OK;
-        }();
-        void* tmp[] = {d_ks, d_slot, d_fbeg, d_cnt, d_list};
-        for (void* p : tmp) if (p) (void)hipFree(p);
-        if (st) return st;
+        DevArr<uint64_t> d_ks, d_slot, d_fbeg;
+        DevArr<unsigned long long> d_cnt;
+        DevArr<ClsSlot> d_list;
+        dbtk_status_t a;
+        if ((a = eval_alloc(d_ks, n, "the TR k-mers"))) return a;
+        if ((a = eval_alloc(d_slot, n, "the TR k-mers' counters"))) return a;
+        if ((a = eval_alloc(d_fbeg, e->nloci + 1, "the loci's first TR k-mers"))) return a;
+        if ((a = eval_alloc(d_cnt, 1, "a counter"))) return a;
+        DEVCHK(hipMemcpy(d_ks, g->tr_ks.data(), n * 8, hipMemcpyHostToDevice));
+        DEVCHK(hipMemcpy(d_slot, g->out_slot.data(), n * 8, hipMemcpyHostToDevice));
+        DEVCHK(hipMemcpy(d_fbeg, fbeg.data(), (e->nloci + 1) * 8, hipMemcpyHostToDevice));
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)e->num_cu * 8);
+        unsigned long long cnt = 0;
+        for (int pass = 0; pass < 2; ++pass) {
+            const uint64_t cap = pass ? cnt : 0;
+            if (pass && !cnt) break;
+            if (pass && (a = eval_alloc(d_list, cap, "the k-mers in both sets"))) return a;
+            DEVCHK(hipMemsetAsync(d_cnt, 0, 8, e->stream));
+            hipLaunchKernelGGL(k_eval_both, dim3(grid), dim3(256), 0, e->stream, d_ks.get(), d_slot.get(), d_fbeg.get(), (uint32_t)e->nloci, n, e->T.cls, e->T.cls_mask, e->T.cls_shift,
+                               d_list.get(), cap, d_cnt.get());
+            DEVCHK(hipGetLastError());
+            DEVCHK(hipMemcpyAsync(&cnt, d_cnt, 8, hipMemcpyDeviceToHost, e->stream));
+            DEVCHK(hipStreamSynchronize(e->stream));
+            if (pass && cnt != cap) { set_error("dbtk_eval_create: the class table changed between two passes"); return DBTK_ERR_HIP; }
+        }
+        found.resize(cnt);
+        if (cnt) DEVCHK(hipMemcpy(found.data(), d_list, cnt * sizeof(ClsSlot), hipMemcpyDeviceToHost));
     }
     std::sort(found.begin(), found.end(), [](const ClsSlot& x, const ClsSlot& y) { return x.lc != y.lc ? x.lc < y.lc : x.kmer < y.kmer; });
     uint64_t cap = 2;
@@ -243,9 +224,9 @@ dbtk_status_t eval_build_both(dbtk_eval* e) {
         while (tab[at].kmer != NAN64) at = (at + 1) & (cap - 1);
         tab[at] = s;
     }
-    const dbtk_status_t a = eval_alloc(&e->d_both, cap, "the table of the k-mers in both sets");
+    const dbtk_status_t a = eval_alloc(e->d_both, cap, "the table of the k-mers in both sets");
     if (a) return a;
-    ECHK(hipMemcpy(e->d_both, tab.data(), cap * sizeof(ClsSlot), hipMemcpyHostToDevice));
+    DEVCHK(hipMemcpy(e->d_both, tab.data(), cap * sizeof(ClsSlot), hipMemcpyHostToDevice));
     e->T.both = e->d_both; e->T.both_mask = cap - 1; e->T.both_shift = shift;
     e->nboth = found.size();
     return DBTK_OK;
@@ -259,44 +240,39 @@ dbtk_status_t eval_create_impl(const dbtk_rpgg_t* g, int device_id, dbtk_eval_t*
     if (g->ksize < 2 || g->ksize > 31) { set_error("dbtk_eval_create: ksize outside 2..31"); return DBTK_ERR_ARG; }
     if (device_id < 0) { set_error("dbtk_eval_create: device " + std::to_string(device_id)); return DBTK_ERR_ARG; }
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); set_error("no HIP device (the library has no CPU path)"); return DBTK_ERR_NO_DEVICE; }
+    if (const dbtk_status_t nd = device_count(&ndev)) return nd;
     if (device_id >= ndev) { set_error("dbtk_eval_create: device " + std::to_string(device_id) + " of " + std::to_string(ndev)); return DBTK_ERR_ARG; }
-    ECHK(hipSetDevice(device_id));
-    dbtk_eval* e = new dbtk_eval;
+    DEVCHK(hipSetDevice(device_id));
+    std::unique_ptr<dbtk_eval, void (*)(dbtk_eval*)> hold(new dbtk_eval, eval_release);  // (released on every way out but the last)
+    dbtk_eval* e = hold.get();
     e->g = g; e->device = device_id; e->nk = g->out_kmer.size(); e->nloci = g->nloci; e->ksize = g->ksize;
-    const dbtk_status_t st = [&]() -> dbtk_status_t {
-        hipDeviceProp_t prop;
-        ECHK(hipGetDeviceProperties(&prop, device_id));
-        e->num_cu = std::max(1, prop.multiProcessorCount);
-        dbtk_status_t a;
-        ClsView cv;
-        if ((a = tables_acquire(g, device_id, &cv, &e->tables))) return a;
-        e->T.cls = (const ClsSlot*)cv.cls; e->T.cls_mask = cv.mask; e->T.cls_shift = cv.shift;
-        ECHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-        for (hipEvent_t& v : e->ev) ECHK(hipEventCreate(&v));
-        if ((a = eval_build_both(e))) return a;
-        if ((a = eval_alloc(&e->d_truth, e->nk + 1, "the truth counts"))) return a;
-        if ((a = eval_alloc(&e->d_windows, e->nloci, "the windows"))) return a;
-        if ((a = eval_alloc(&e->d_beg, e->nloci + 1, "the loci's first counters"))) return a;
-        if ((a = eval_alloc(&e->d_list, e->nloci, "the locus lists"))) return a;
-        if ((a = eval_alloc(&e->d_sums, e->nloci, "the sums"))) return a;
-        if ((a = eval_alloc(&e->d_ovf, 1, "the overflow word"))) return a;
-        std::vector<uint32_t> list(e->nloci);
-        uint32_t ns = 0;
-        for (uint64_t l = 0; l < e->nloci; ++l) if (g->out_beg[l + 1] - g->out_beg[l] <= EV_SMALL) list[ns++] = (uint32_t)l;
-        e->nsmall = ns;
-        for (uint64_t l = 0; l < e->nloci; ++l) if (g->out_beg[l + 1] - g->out_beg[l] > EV_SMALL) list[ns++] = (uint32_t)l;
-        e->nlarge = (uint32_t)e->nloci - e->nsmall;
-        ECHK(hipMemcpy(e->d_list, list.data(), e->nloci * 4, hipMemcpyHostToDevice));
-        ECHK(hipMemcpy(e->d_beg, g->out_beg.data(), (e->nloci + 1) * 8, hipMemcpyHostToDevice));
-        // (waited for: the truth pass runs on a sim handle's stream, which is ordered against no other)
-        ECHK(hipMemsetAsync(e->d_truth, 0, (e->nk + 1) * 8, e->stream));
-        ECHK(hipMemsetAsync(e->d_windows, 0, e->nloci * 8, e->stream));
-        ECHK(hipStreamSynchronize(e->stream));
-        return DBTK_OK;
-    }();
-    if (st) { eval_release(e); return st; }
-    *out = e;
+    DEVCHK(device_cus(device_id, &e->num_cu));
+    dbtk_status_t a;
+    ClsView cv;
+    if ((a = tables_acquire(g, device_id, &cv, &e->tables))) return a;
+    e->T.cls = (const ClsSlot*)cv.cls; e->T.cls_mask = cv.mask; e->T.cls_shift = cv.shift;
+    DEVCHK(e->stream.create(hipStreamNonBlocking));
+    for (DevEvent& v : e->ev) DEVCHK(v.create(hipEventDefault));
+    if ((a = eval_build_both(e))) return a;
+    if ((a = eval_alloc(e->d_truth, e->nk + 1, "the truth counts"))) return a;
+    if ((a = eval_alloc(e->d_windows, e->nloci, "the windows"))) return a;
+    if ((a = eval_alloc(e->d_beg, e->nloci + 1, "the loci's first counters"))) return a;
+    if ((a = eval_alloc(e->d_list, e->nloci, "the locus lists"))) return a;
+    if ((a = eval_alloc(e->d_sums, e->nloci, "the sums"))) return a;
+    if ((a = eval_alloc(e->d_ovf, 1, "the overflow word"))) return a;
+    std::vector<uint32_t> list(e->nloci);
+    uint32_t ns = 0;
+    for (uint64_t l = 0; l < e->nloci; ++l) if (g->out_beg[l + 1] - g->out_beg[l] <= EV_SMALL) list[ns++] = (uint32_t)l;
+    e->nsmall = ns;
+    for (uint64_t l = 0; l < e->nloci; ++l) if (g->out_beg[l + 1] - g->out_beg[l] > EV_SMALL) list[ns++] = (uint32_t)l;
+    e->nlarge = (uint32_t)e->nloci - e->nsmall;
+    DEVCHK(hipMemcpy(e->d_list, list.data(), e->nloci * 4, hipMemcpyHostToDevice));
+    DEVCHK(hipMemcpy(e->d_beg, g->out_beg.data(), (e->nloci + 1) * 8, hipMemcpyHostToDevice));
+    // (waited for: the truth pass runs on a sim handle's stream, which is ordered against no other)
+    DEVCHK(hipMemsetAsync(e->d_truth, 0, (e->nk + 1) * 8, e->stream));
+    DEVCHK(hipMemsetAsync(e->d_windows, 0, e->nloci * 8, e->stream));
+    DEVCHK(hipStreamSynchronize(e->stream));
+    *out = hold.release();
     return DBTK_OK;
 }
 
@@ -309,13 +285,12 @@ dbtk_status_t eval_truth_sim_impl(dbtk_eval_t* e, dbtk_sim_t* sim) {
     if (ss.device != e->device) { set_error("dbtk_eval_truth_sim: the sim handle is on device " + std::to_string(ss.device) + ", the evaluator on device " + std::to_string(e->device)); return DBTK_ERR_ARG; }
     if (ss.nloci != e->nloci) { set_error("dbtk_eval_truth_sim: the sim handle was opened for " + std::to_string(ss.nloci) + " loci, the RPGG has " + std::to_string(e->nloci)); return DBTK_ERR_ARG; }
     if (!e->windows_given) { set_error("dbtk_eval_truth_sim: the truth was set without windows (dbtk_eval_truth_set): dbtk_eval_truth_reset first"); return DBTK_ERR_ARG; }
-    ECHK(hipSetDevice(e->device));
+    DEVCHK(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)ss.stream;
     const uint32_t k = e->ksize;
     std::vector<SimSpan> spans;
     std::vector<EvalItem> items;
-    EvalItem* d_items = nullptr;
-    uint64_t cap = 0;
+    DevArr<EvalItem> d_items;
     float total = 0;
     st = [&]() -> dbtk_status_t {
         for (uint32_t g = 0; g < ss.ngroups; ++g) {
@@ -330,51 +305,50 @@ dbtk_status_t eval_truth_sim_impl(dbtk_eval_t* e, dbtk_sim_t* sim) {
             if (items.empty()) continue;
             if (items.size() > 0xFFFFFFFFull) { set_error("dbtk_eval_truth_sim: more than 2^32 - 1 work items in one contig group"); return DBTK_ERR_UNSUPPORTED; }
             if ((a = sim_group_load(sim, g))) return a;
-            if (items.size() > cap) {
-                if (d_items) { ECHK(hipStreamSynchronize(s)); (void)hipFree(d_items); d_items = nullptr; }
-                cap = items.size() + items.size() / 4;
-                if ((a = eval_alloc(&d_items, cap, "the truth pass's work items"))) return a;
+            if (items.size() > d_items.cap()) {
+                if (d_items) DEVCHK(hipStreamSynchronize(s));
+                if ((a = eval_alloc(d_items, items.size() + items.size() / 4, "the truth pass's work items"))) return a;
             } else {
-                ECHK(hipStreamSynchronize(s));  // (the launch before reads the items this copy overwrites)
+                DEVCHK(hipStreamSynchronize(s));  // (the launch before reads the items this copy overwrites)
             }
-            ECHK(hipMemcpy(d_items, items.data(), items.size() * sizeof(EvalItem), hipMemcpyHostToDevice));
-            EvalTruthArgs a2{ss.d_arena, d_items, (uint32_t)items.size(), k, e->T, e->nk, e->d_truth, e->d_windows, e->d_truth + e->nk};
+            DEVCHK(hipMemcpy(d_items, items.data(), items.size() * sizeof(EvalItem), hipMemcpyHostToDevice));
+            EvalTruthArgs a2{ss.d_arena, d_items.get(), (uint32_t)items.size(), k, e->T, e->nk, e->d_truth, e->d_windows, e->d_truth + e->nk};
             const uint32_t grid = (uint32_t)std::min<uint64_t>(items.size(), (uint64_t)e->num_cu * 32);
-            ECHK(hipEventRecord(e->ev[0], s));
+            DEVCHK(hipEventRecord(e->ev[0], s));
             hipLaunchKernelGGL(k_eval_truth, dim3(grid), dim3(64), 0, s, a2);
-            ECHK(hipGetLastError());
-            ECHK(hipEventRecord(e->ev[1], s));
-            ECHK(hipEventSynchronize(e->ev[1]));
+            DEVCHK(hipGetLastError());
+            DEVCHK(hipEventRecord(e->ev[1], s));
+            DEVCHK(hipEventSynchronize(e->ev[1]));
             float ms = 0;
-            ECHK(hipEventElapsedTime(&ms, e->ev[0], e->ev[1]));
+            DEVCHK(hipEventElapsedTime(&ms, e->ev[0], e->ev[1]));
             total += ms;
         }
         return DBTK_OK;
     }();
-    if (d_items) { (void)hipStreamSynchronize(s); (void)hipFree(d_items); }
+    if (d_items) (void)hipStreamSynchronize(s);  // (the last launch reads the items: d_items is freed behind it)
     e->ms[0] += total;
     e->scored = false;
     return st;
 }
 
 dbtk_status_t eval_score_impl(dbtk_eval_t* e, const uint64_t* d_y) {
-    ECHK(hipSetDevice(e->device));
+    DEVCHK(hipSetDevice(e->device));
     hipStream_t s = e->stream;
-    ECHK(hipMemsetAsync(e->d_ovf, 0xFF, 4, s));  // EV_NOVF
-    ECHK(hipEventRecord(e->ev[0], s));
-    if (e->nsmall) hipLaunchKernelGGL(k_eval_sums<false>, dim3((e->nsmall + 3) / 4), dim3(256), 0, s, e->d_truth, d_y, e->d_beg, e->d_list, e->nsmall, e->d_sums, e->d_ovf);
-    if (e->nlarge) hipLaunchKernelGGL(k_eval_sums<true>, dim3(e->nlarge), dim3(256), 0, s, e->d_truth, d_y, e->d_beg, e->d_list + e->nsmall, e->nlarge, e->d_sums, e->d_ovf);
-    ECHK(hipGetLastError());
-    ECHK(hipEventRecord(e->ev[1], s));
+    DEVCHK(hipMemsetAsync(e->d_ovf, 0xFF, 4, s));  // EV_NOVF
+    DEVCHK(hipEventRecord(e->ev[0], s));
+    if (e->nsmall) hipLaunchKernelGGL(k_eval_sums<false>, dim3((e->nsmall + 3) / 4), dim3(256), 0, s, e->d_truth.get(), d_y, e->d_beg.get(), e->d_list.get(), e->nsmall, e->d_sums.get(), e->d_ovf.get());
+    if (e->nlarge) hipLaunchKernelGGL(k_eval_sums<true>, dim3(e->nlarge), dim3(256), 0, s, e->d_truth.get(), d_y, e->d_beg.get(), e->d_list + e->nsmall, e->nlarge, e->d_sums.get(), e->d_ovf.get());
+    DEVCHK(hipGetLastError());
+    DEVCHK(hipEventRecord(e->ev[1], s));
     std::vector<EvalSums> raw(e->nloci);
     std::vector<uint64_t> win(e->nloci);
     uint32_t ovf = EV_NOVF;
-    ECHK(hipMemcpyAsync(raw.data(), e->d_sums, e->nloci * sizeof(EvalSums), hipMemcpyDeviceToHost, s));
-    ECHK(hipMemcpyAsync(win.data(), e->d_windows, e->nloci * 8, hipMemcpyDeviceToHost, s));
-    ECHK(hipMemcpyAsync(&ovf, e->d_ovf, 4, hipMemcpyDeviceToHost, s));
-    ECHK(hipStreamSynchronize(s));
+    DEVCHK(hipMemcpyAsync(raw.data(), e->d_sums, e->nloci * sizeof(EvalSums), hipMemcpyDeviceToHost, s));
+    DEVCHK(hipMemcpyAsync(win.data(), e->d_windows, e->nloci * 8, hipMemcpyDeviceToHost, s));
+    DEVCHK(hipMemcpyAsync(&ovf, e->d_ovf, 4, hipMemcpyDeviceToHost, s));
+    DEVCHK(hipStreamSynchronize(s));
     float ms = 0;
-    ECHK(hipEventElapsedTime(&ms, e->ev[0], e->ev[1]));
+    DEVCHK(hipEventElapsedTime(&ms, e->ev[0], e->ev[1]));
     e->ms[1] += ms;
     e->scored = false;
     if (ovf != EV_NOVF) {
@@ -409,21 +383,16 @@ dbtk_status_t eval_score_ctx_impl(dbtk_eval_t* e, dbtk_ctx_t* ctx) {
 dbtk_status_t eval_score_device_impl(dbtk_eval_t* e, const void* d_counts) {
     if (!e || !d_counts) { set_error("dbtk_eval_score_device: null argument"); return DBTK_ERR_ARG; }
     if (((uintptr_t)d_counts & 7) != 0) { set_error("dbtk_eval_score_device: d_counts must be 8-byte aligned"); return DBTK_ERR_ARG; }
-    ECHK(hipSetDevice(e->device));
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, d_counts) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->device) {
-        (void)hipGetLastError();
-        set_error("dbtk_eval_score_device: d_counts is not device memory of the handle's device");
-        return DBTK_ERR_ARG;
-    }
+    DEVCHK(hipSetDevice(e->device));
+    if (!is_device_memory_of(d_counts, e->device)) { set_error("dbtk_eval_score_device: d_counts is not device memory of the handle's device"); return DBTK_ERR_ARG; }
     return eval_score_impl(e, (const uint64_t*)d_counts);
 }
 
 dbtk_status_t eval_score_host_impl(dbtk_eval_t* e, const uint64_t* counts) {
     if (!e || !counts) { set_error("dbtk_eval_score_host: null argument"); return DBTK_ERR_ARG; }
-    ECHK(hipSetDevice(e->device));
-    if (!e->d_scratch) { const dbtk_status_t a = eval_alloc(&e->d_scratch, e->nk, "a count vector"); if (a) return a; }
-    if (e->nk) ECHK(hipMemcpy(e->d_scratch, counts, e->nk * 8, hipMemcpyHostToDevice));
+    DEVCHK(hipSetDevice(e->device));
+    if (!e->d_scratch) { const dbtk_status_t a = eval_alloc(e->d_scratch, e->nk, "a count vector"); if (a) return a; }
+    if (e->nk) DEVCHK(hipMemcpy(e->d_scratch, counts, e->nk * 8, hipMemcpyHostToDevice));
     return eval_score_impl(e, e->d_scratch);
 }
 
@@ -474,10 +443,10 @@ dbtk_status_t dbtk_eval_truth_sim(dbtk_eval_t* e, dbtk_sim_t* sim) {
 
 dbtk_status_t dbtk_eval_truth_set(dbtk_eval_t* e, const uint64_t* counts, const uint64_t* windows) {
     if (!e || !counts) { set_error("dbtk_eval_truth_set: null argument"); return DBTK_ERR_ARG; }
-    ECHK(hipSetDevice(e->device));
-    if (e->nk) ECHK(hipMemcpy(e->d_truth, counts, e->nk * 8, hipMemcpyHostToDevice));
-    if (windows) ECHK(hipMemcpy(e->d_windows, windows, e->nloci * 8, hipMemcpyHostToDevice));
-    else { ECHK(hipMemsetAsync(e->d_windows, 0, e->nloci * 8, e->stream)); ECHK(hipStreamSynchronize(e->stream)); }
+    DEVCHK(hipSetDevice(e->device));
+    if (e->nk) DEVCHK(hipMemcpy(e->d_truth, counts, e->nk * 8, hipMemcpyHostToDevice));
+    if (windows) DEVCHK(hipMemcpy(e->d_windows, windows, e->nloci * 8, hipMemcpyHostToDevice));
+    else { DEVCHK(hipMemsetAsync(e->d_windows, 0, e->nloci * 8, e->stream)); DEVCHK(hipStreamSynchronize(e->stream)); }
     e->windows_given = windows != nullptr;
     e->scored = false;
     return DBTK_OK;
@@ -486,12 +455,12 @@ dbtk_status_t dbtk_eval_truth_set(dbtk_eval_t* e, const uint64_t* counts, const 
 dbtk_status_t dbtk_eval_truth(dbtk_eval_t* e, uint64_t* counts, uint64_t* windows) {
     if (!e) { set_error("dbtk_eval_truth: null argument"); return DBTK_ERR_ARG; }
     return guarded([&]() -> dbtk_status_t {
-        ECHK(hipSetDevice(e->device));
-        if (counts && e->nk) ECHK(hipMemcpy(counts, e->d_truth, e->nk * 8, hipMemcpyDeviceToHost));
-        if (windows && e->windows_given) ECHK(hipMemcpy(windows, e->d_windows, e->nloci * 8, hipMemcpyDeviceToHost));
+        DEVCHK(hipSetDevice(e->device));
+        if (counts && e->nk) DEVCHK(hipMemcpy(counts, e->d_truth, e->nk * 8, hipMemcpyDeviceToHost));
+        if (windows && e->windows_given) DEVCHK(hipMemcpy(windows, e->d_windows, e->nloci * 8, hipMemcpyDeviceToHost));
         if (windows && !e->windows_given) {  // windows = Sx
             std::vector<uint64_t> x(e->nk);
-            if (e->nk) ECHK(hipMemcpy(x.data(), e->d_truth, e->nk * 8, hipMemcpyDeviceToHost));
+            if (e->nk) DEVCHK(hipMemcpy(x.data(), e->d_truth, e->nk * 8, hipMemcpyDeviceToHost));
             for (uint64_t l = 0; l < e->nloci; ++l) {
                 uint64_t sx = 0;
                 for (uint64_t i = e->g->out_beg[l]; i < e->g->out_beg[l + 1]; ++i) sx += x[i];
@@ -504,10 +473,10 @@ dbtk_status_t dbtk_eval_truth(dbtk_eval_t* e, uint64_t* counts, uint64_t* window
 
 dbtk_status_t dbtk_eval_truth_reset(dbtk_eval_t* e) {
     if (!e) { set_error("dbtk_eval_truth_reset: null argument"); return DBTK_ERR_ARG; }
-    ECHK(hipSetDevice(e->device));
-    if (e->nk) ECHK(hipMemsetAsync(e->d_truth, 0, e->nk * 8, e->stream));  // (the look-up counter behind it stays: dbtk_eval_times counts since creation)
-    ECHK(hipMemsetAsync(e->d_windows, 0, e->nloci * 8, e->stream));
-    ECHK(hipStreamSynchronize(e->stream));
+    DEVCHK(hipSetDevice(e->device));
+    if (e->nk) DEVCHK(hipMemsetAsync(e->d_truth, 0, e->nk * 8, e->stream));  // (the look-up counter behind it stays: dbtk_eval_times counts since creation)
+    DEVCHK(hipMemsetAsync(e->d_windows, 0, e->nloci * 8, e->stream));
+    DEVCHK(hipStreamSynchronize(e->stream));
     e->windows_given = true;
     e->scored = false;
     return DBTK_OK;
@@ -554,9 +523,9 @@ dbtk_status_t dbtk_eval_write(dbtk_eval_t* e, const char* out_prefix) {
 
 dbtk_status_t dbtk_eval_times(dbtk_eval_t* e, double ms[2], uint64_t* lookups) {
     if (!e) { set_error("dbtk_eval_times: null argument"); return DBTK_ERR_ARG; }
-    ECHK(hipSetDevice(e->device));
+    DEVCHK(hipSetDevice(e->device));
     if (ms) { ms[0] = e->ms[0]; ms[1] = e->ms[1]; }
-    if (lookups) ECHK(hipMemcpy(lookups, e->d_truth + e->nk, 8, hipMemcpyDeviceToHost));
+    if (lookups) DEVCHK(hipMemcpy(lookups, e->d_truth + e->nk, 8, hipMemcpyDeviceToHost));
     return DBTK_OK;
 }
 

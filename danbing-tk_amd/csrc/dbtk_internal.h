@@ -1,4 +1,5 @@
-// dbtk_internal.h — host-side structures shared by dbtk_rpgg.cpp and dbtk_hip.hip.
+// dbtk_internal.h — host-side structures and seams shared by every translation unit of the library: dbtk_rpgg.cpp, dbtk_hip.hip and
+// the side modules (dbtk_pred.hip, dbtk_kcp.hip, dbtk_sim.hip, dbtk_eval.hip, dbtk_assoc.hip) with their dbtk_dev.h.
 #ifndef DBTK_INTERNAL_H_
 #define DBTK_INTERNAL_H_
 

@@ -7,24 +7,17 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/dbtk_kcp.h"
+#include "dbtk_dev.h"
 #include "dbtk_internal.h"
 #include "dbtk_kcp.h"
 
 using namespace dbtk;
-
-#define KCHK(call)                                                                                    \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) {                                                                       \
-            set_error(std::string(#call) + ": " + hipGetErrorString(e_));                             \
-            return DBTK_ERR_HIP;                                                                      \
-        }                                                                                             \
-    } while (0)
 
 namespace {
 
@@ -160,16 +153,16 @@ struct dbtk_kcp {
     int device = 0, num_cu = 1;
     uint32_t k = 0, flags = 0;
     uint64_t nloci = 0;
-    hipStream_t stream = nullptr;
-    KcpSlot* d_tab = nullptr;
+    // (members are destroyed last to first: the events, the table, the words, the staging, and the stream behind them all)
+    DevStream stream;
+    DevArr<KcpSel> d_sel;  // a batch's list of counted pairs, its offsets and reads (grown, never shrunk)
+    DevArr<uint64_t> d_off;
+    DevArr<uint8_t> d_seq;
+    DevArr<unsigned long long> d_words;
+    DevArr<KcpSlot> d_tab;
+    std::vector<DevEvent> ev;  // a pair per piece of the batch in flight
     uint64_t slots = 0;
-    unsigned long long* d_words = nullptr;
     uint64_t occ_ub = 0;  // no fewer than the slots taken: the last reading plus the bounds of the pieces launched since
-    // a batch's reads, offsets and list of counted pairs (grown, never shrunk)
-    uint8_t* d_seq = nullptr; size_t seq_cap = 0;
-    uint64_t* d_off = nullptr; size_t off_cap = 0;
-    KcpSel* d_sel = nullptr; size_t sel_cap = 0;
-    std::vector<hipEvent_t> ev;  // a pair per piece of the batch in flight
     double add_ms = 0;
 };
 
@@ -178,11 +171,11 @@ struct dbtk_kcp_fps {
     int device = 0, num_cu = 1;
     uint32_t k = 0;
     uint64_t nloci = 0;
-    hipStream_t stream = nullptr;
-    KcpCand* d_cand = nullptr;
-    uint32_t* d_state = nullptr;
-    unsigned long long* d_words = nullptr;  // living candidates looked up | candidates that died, over all applies
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DevStream stream;  // (destroyed last: behind the buffers, which go behind the events)
+    DevArr<unsigned long long> d_words;  // living candidates looked up | candidates that died, over all applies
+    DevArr<uint32_t> d_state;
+    DevArr<KcpCand> d_cand;
+    DevEvent ev1, ev0;
     uint64_t n = 0, alive = 0, lookups = 0;
     double apply_ms = 0;
 };
@@ -192,23 +185,24 @@ namespace {
 uint32_t grid_cu(int num_cu, uint64_t n, uint32_t per_block) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1) / per_block, (uint64_t)num_cu * 8)); }
 uint32_t grid_for(const dbtk_kcp* c, uint64_t n, uint32_t per_block) { return grid_cu(c->num_cu, n, per_block); }
 
-dbtk_status_t kcp_new_table(dbtk_kcp* c, uint64_t slots, KcpSlot** out) {
-    *out = nullptr;
-    if (hipMalloc((void**)out, slots * sizeof(KcpSlot)) != hipSuccess) {
+// (a failure leaves nothing behind: the table is *out's only once it is being filled)
+dbtk_status_t kcp_new_table(dbtk_kcp* c, uint64_t slots, DevArr<KcpSlot>* out) {
+    DevArr<KcpSlot> t;
+    if (t.alloc(slots) != hipSuccess) {
         (void)hipGetLastError();
-        *out = nullptr;
         set_error("bait profile table: no device memory for " + std::to_string(slots) + " slots (" + std::to_string(slots * sizeof(KcpSlot)) + " bytes)");
         return DBTK_ERR_NOMEM;
     }
-    hipLaunchKernelGGL(k_kcp_fill, dim3(grid_for(c, slots, 256)), dim3(256), 0, c->stream, *out, slots);
-    KCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_kcp_fill, dim3(grid_for(c, slots, 256)), dim3(256), 0, c->stream, t.get(), slots);
+    DEVCHK(hipGetLastError());
+    *out = std::move(t);
     return DBTK_OK;
 }
 
 // waits for the handle's kernels and reads the words; the sticky word is an error
 dbtk_status_t kcp_words(dbtk_kcp* c, unsigned long long w[KCP_WORDS]) {
-    KCHK(hipStreamSynchronize(c->stream));
-    KCHK(hipMemcpy(w, c->d_words, sizeof(unsigned long long) * KCP_WORDS, hipMemcpyDeviceToHost));
+    DEVCHK(hipStreamSynchronize(c->stream));
+    DEVCHK(hipMemcpy(w, c->d_words, sizeof(unsigned long long) * KCP_WORDS, hipMemcpyDeviceToHost));
     c->occ_ub = w[KCP_W_OCC];
     if (w[KCP_W_FAIL]) {
         set_error("bait profile table overflow: an insert found none of " + std::to_string(c->slots) +
@@ -228,18 +222,17 @@ dbtk_status_t kcp_room(dbtk_kcp* c, uint64_t bound) {
     if (2 * (c->occ_ub + bound) > c->slots) {
         uint64_t cap = c->slots;
         while (2 * (c->occ_ub + bound) > cap) cap <<= 1;
-        KcpSlot* nt = nullptr;
+        DevArr<KcpSlot> nt;
         dbtk_status_t st = kcp_new_table(c, cap, &nt);
         if (st) return st;
-        KCHK(hipMemsetAsync(c->d_words + KCP_W_OCC, 0, sizeof(unsigned long long), c->stream));
-        hipLaunchKernelGGL(k_kcp_rehash, dim3(grid_for(c, c->slots, 256)), dim3(256), 0, c->stream, (const KcpSlot*)c->d_tab, c->slots, nt, cap - 1, 64 - log2u64(cap), c->d_words);
-        KCHK(hipGetLastError());
-        KcpSlot* old = c->d_tab;
+        DEVCHK(hipMemsetAsync(c->d_words + KCP_W_OCC, 0, sizeof(unsigned long long), c->stream));
+        hipLaunchKernelGGL(k_kcp_rehash, dim3(grid_for(c, c->slots, 256)), dim3(256), 0, c->stream, (const KcpSlot*)c->d_tab, c->slots, nt.get(), cap - 1, 64 - log2u64(cap), c->d_words.get());
+        DEVCHK(hipGetLastError());
         const uint64_t old_slots = c->slots;
-        c->d_tab = nt; c->slots = cap;
+        std::swap(c->d_tab, nt);  // (nt: the old table from here on, freed behind kcp_words' wait)
+        c->slots = cap;
         unsigned long long w[KCP_WORDS];
         st = kcp_words(c, w);
-        (void)hipFree(old);
         if (st) return st;
         if (getenv("DBTK_VERBOSE")) fprintf(stderr, "bait profile table: grown from %llu to %llu slots, %llu taken\n", (unsigned long long)old_slots, (unsigned long long)cap, w[KCP_W_OCC]);
     }
@@ -285,18 +278,12 @@ void kcp_sort(std::vector<KcpSlot>& v, uint64_t nloci) {
     });
 }
 
-template <class T> dbtk_status_t kcp_reserve(T** p, size_t* cap, size_t n) {
-    if (n <= *cap) return DBTK_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
+template <class T> dbtk_status_t kcp_reserve(DevArr<T>& a, size_t n) {
     const size_t want = n + n / 4;
-    if (hipMalloc((void**)p, want * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        set_error("bait profile: no device memory for a batch's staging (" + std::to_string(want * sizeof(T)) + " bytes)");
-        return DBTK_ERR_NOMEM;
-    }
-    *cap = want;
-    return DBTK_OK;
+    if (a.reserve(n, want) == hipSuccess) return DBTK_OK;
+    (void)hipGetLastError();
+    set_error("bait profile: no device memory for a batch's staging (" + std::to_string(want * sizeof(T)) + " bytes)");
+    return DBTK_ERR_NOMEM;
 }
 
 dbtk_status_t kcp_create_impl(uint32_t ksize, uint64_t nloci, int device_id, uint32_t flags, dbtk_kcp_t** out) {
@@ -312,18 +299,16 @@ dbtk_status_t kcp_create_impl(uint32_t ksize, uint64_t nloci, int device_id, uin
         slots0 = v;
     }
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); set_error("no HIP device (the library has no CPU path)"); return DBTK_ERR_NO_DEVICE; }
+    if (const dbtk_status_t nd = device_count(&ndev)) return nd;
     if (device_id < 0 || device_id >= ndev) { set_error("dbtk_kcp_create: device " + std::to_string(device_id) + " of " + std::to_string(ndev)); return DBTK_ERR_ARG; }
-    KCHK(hipSetDevice(device_id));
+    DEVCHK(hipSetDevice(device_id));
     dbtk_kcp* c = new dbtk_kcp;
     c->device = device_id; c->k = ksize; c->flags = flags; c->nloci = nloci;
     dbtk_status_t st = DBTK_OK;
     do {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device_id) != hipSuccess) { set_error("hipGetDeviceProperties failed"); st = DBTK_ERR_HIP; break; }
-        c->num_cu = std::max(1, prop.multiProcessorCount);
-        if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { c->stream = nullptr; set_error("hipStreamCreate failed"); st = DBTK_ERR_HIP; break; }
-        if (hipMalloc((void**)&c->d_words, sizeof(unsigned long long) * KCP_WORDS) != hipSuccess) { c->d_words = nullptr; set_error("hipMalloc of the table's words failed"); st = DBTK_ERR_HIP; break; }
+        if (device_cus(device_id, &c->num_cu) != hipSuccess) { set_error("hipGetDeviceProperties failed"); st = DBTK_ERR_HIP; break; }
+        if (c->stream.create(hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); st = DBTK_ERR_HIP; break; }
+        if (c->d_words.alloc(KCP_WORDS) != hipSuccess) { set_error("hipMalloc of the table's words failed"); st = DBTK_ERR_HIP; break; }
         if (hipMemsetAsync(c->d_words, 0, sizeof(unsigned long long) * KCP_WORDS, c->stream) != hipSuccess) { set_error("hipMemsetAsync failed"); st = DBTK_ERR_HIP; break; }
         if ((st = kcp_new_table(c, slots0, &c->d_tab))) break;
         c->slots = slots0;
@@ -340,7 +325,7 @@ dbtk_status_t kcp_add_impl(dbtk_kcp_t* c, const uint8_t* seq, const uint64_t* of
                            const uint64_t* d_off = nullptr) {
     if (!c || (npairs && ((!seq && !d_seq) || !off || !src || !dst))) { set_error("dbtk_kcp_add: null argument"); return DBTK_ERR_ARG; }
     if (npairs > 0x7FFFFFFFull) { set_error("dbtk_kcp_add: more than 2^31 - 1 pairs in one call"); return DBTK_ERR_ARG; }
-    KCHK(hipSetDevice(c->device));
+    DEVCHK(hipSetDevice(c->device));
     {  // a failed insert of an earlier call
         unsigned long long w[KCP_WORDS];
         const dbtk_status_t st = kcp_words(c, w);
@@ -372,16 +357,16 @@ dbtk_status_t kcp_add_impl(dbtk_kcp_t* c, const uint8_t* seq, const uint64_t* of
     if (sel.empty()) return DBTK_OK;
     const uint64_t base = seq ? off[0] : 0, nbytes = off[2 * npairs] - base;
     dbtk_status_t st;
-    if (seq && (st = kcp_reserve(&c->d_seq, &c->seq_cap, (size_t)nbytes + 1))) return st;
-    if (seq && (st = kcp_reserve(&c->d_off, &c->off_cap, (size_t)(2 * npairs + 1)))) return st;
-    if ((st = kcp_reserve(&c->d_sel, &c->sel_cap, sel.size()))) return st;
+    if (seq && (st = kcp_reserve(c->d_seq, (size_t)nbytes + 1))) return st;
+    if (seq && (st = kcp_reserve(c->d_off, (size_t)(2 * npairs + 1)))) return st;
+    if ((st = kcp_reserve(c->d_sel, sel.size()))) return st;
     // (the stream is idle — kcp_words above waited for it — and these copies return when they are done)
     if (seq) {
-        KCHK(hipMemcpy(c->d_seq, seq + base, nbytes, hipMemcpyHostToDevice));
-        KCHK(hipMemcpy(c->d_off, off, sizeof(uint64_t) * (2 * npairs + 1), hipMemcpyHostToDevice));
+        DEVCHK(hipMemcpy(c->d_seq, seq + base, nbytes, hipMemcpyHostToDevice));
+        DEVCHK(hipMemcpy(c->d_off, off, sizeof(uint64_t) * (2 * npairs + 1), hipMemcpyHostToDevice));
         d_seq = c->d_seq; d_off = c->d_off;
     }
-    KCHK(hipMemcpy(c->d_sel, sel.data(), sizeof(KcpSel) * sel.size(), hipMemcpyHostToDevice));
+    DEVCHK(hipMemcpy(c->d_sel, sel.data(), sizeof(KcpSel) * sel.size(), hipMemcpyHostToDevice));
     // piece by piece: room first, then the kernel
     size_t nev = 0;
     for (size_t i = 0; i < sel.size();) {
@@ -390,72 +375,65 @@ dbtk_status_t kcp_add_impl(dbtk_kcp_t* c, const uint8_t* seq, const uint64_t* of
         size_t j = i;
         while (j < sel.size() && (j == i || bound + npos[j] <= piece)) bound += npos[j++];
         if ((st = kcp_room(c, bound))) return st;
-        if (c->ev.size() < nev + 2) {
-            hipEvent_t a, b;
-            KCHK(hipEventCreate(&a));
-            c->ev.push_back(a);
-            KCHK(hipEventCreate(&b));
-            c->ev.push_back(b);
+        while (c->ev.size() < nev + 2) {
+            DevEvent e;
+            DEVCHK(e.create(hipEventDefault));
+            c->ev.push_back(std::move(e));
         }
         const uint64_t w0 = 2 * (uint64_t)i, w1 = 2 * (uint64_t)j;
         const uint32_t grid = (uint32_t)std::min<uint64_t>(w1 - w0, (uint64_t)c->num_cu * 32);
-        KCHK(hipEventRecord(c->ev[nev], c->stream));
-        hipLaunchKernelGGL(k_kcp_add, dim3(grid), dim3(64), 0, c->stream, d_seq, d_off, base, (const KcpSel*)c->d_sel, w0, w1, c->k, c->d_tab,
-                           c->slots - 1, 64 - log2u64(c->slots), c->d_words);
-        KCHK(hipGetLastError());
-        KCHK(hipEventRecord(c->ev[nev + 1], c->stream));
+        DEVCHK(hipEventRecord(c->ev[nev], c->stream));
+        hipLaunchKernelGGL(k_kcp_add, dim3(grid), dim3(64), 0, c->stream, d_seq, d_off, base, (const KcpSel*)c->d_sel, w0, w1, c->k, c->d_tab.get(),
+                           c->slots - 1, 64 - log2u64(c->slots), c->d_words.get());
+        DEVCHK(hipGetLastError());
+        DEVCHK(hipEventRecord(c->ev[nev + 1], c->stream));
         nev += 2;
         i = j;
     }
-    KCHK(hipStreamSynchronize(c->stream));
+    DEVCHK(hipStreamSynchronize(c->stream));
     for (size_t e = 0; e < nev; e += 2) {
         float ms = 0;
-        KCHK(hipEventElapsedTime(&ms, c->ev[e], c->ev[e + 1]));
+        DEVCHK(hipEventElapsedTime(&ms, c->ev[e], c->ev[e + 1]));
         c->add_ms += ms;
     }
     return DBTK_OK;
 }
 
-// the entries of class cls compacted into a device array that the caller frees (want_out false: counted only, *d_out stays null)
-dbtk_status_t kcp_compact(dbtk_kcp_t* c, uint32_t cls, bool want_out, KcpSlot** d_out, uint64_t* count) {
-    *d_out = nullptr;
+// the entries of class cls compacted into a device array (want_out false: counted only, *d_out stays empty)
+dbtk_status_t kcp_compact(dbtk_kcp_t* c, uint32_t cls, bool want_out, DevArr<KcpSlot>* d_out, uint64_t* count) {
+    d_out->drop();
     if (!c || cls > 1) { set_error("bait profile: null handle or a class other than 0 (TP) and 1 (FP)"); return DBTK_ERR_ARG; }
-    KCHK(hipSetDevice(c->device));
+    DEVCHK(hipSetDevice(c->device));
     unsigned long long w[KCP_WORDS];
     dbtk_status_t st = kcp_words(c, w);
     if (st) return st;
     const uint64_t cap = want_out ? w[KCP_W_OCC] : 0;  // (no class has more entries than the table has slots taken)
-    unsigned long long* d_n = nullptr;
-    KCHK(hipMalloc((void**)&d_n, sizeof(unsigned long long)));
+    DevArr<unsigned long long> d_n;
+    DevArr<KcpSlot> out;
+    DEVCHK(d_n.alloc(1));
     unsigned long long n = 0;
-    st = [&]() -> dbtk_status_t {
-        KCHK(hipMemsetAsync(d_n, 0, sizeof(unsigned long long), c->stream));
-        if (cap) KCHK(hipMalloc((void**)d_out, cap * sizeof(KcpSlot)));
-        hipLaunchKernelGGL(k_kcp_compact, dim3(grid_for(c, c->slots, 256)), dim3(256), 0, c->stream, (const KcpSlot*)c->d_tab, c->slots, cls, *d_out, cap, d_n);
-        KCHK(hipGetLastError());
-        KCHK(hipMemcpyAsync(&n, d_n, sizeof n, hipMemcpyDeviceToHost, c->stream));
-        KCHK(hipStreamSynchronize(c->stream));
-        if (want_out && n > cap) { set_error("bait profile: the table holds more entries than slots taken"); return DBTK_ERR_HIP; }
-        return DBTK_OK;
-    }();
-    (void)hipFree(d_n);
-    if (st && *d_out) { (void)hipFree(*d_out); *d_out = nullptr; }
-    if (!st) *count = n;
-    return st;
+    DEVCHK(hipMemsetAsync(d_n, 0, sizeof(unsigned long long), c->stream));
+    if (cap) DEVCHK(out.alloc(cap));
+    hipLaunchKernelGGL(k_kcp_compact, dim3(grid_for(c, c->slots, 256)), dim3(256), 0, c->stream, (const KcpSlot*)c->d_tab, c->slots, cls, out.get(), cap, d_n.get());
+    DEVCHK(hipGetLastError());
+    DEVCHK(hipMemcpyAsync(&n, d_n, sizeof n, hipMemcpyDeviceToHost, c->stream));
+    DEVCHK(hipStreamSynchronize(c->stream));
+    if (want_out && n > cap) { set_error("bait profile: the table holds more entries than slots taken"); return DBTK_ERR_HIP; }
+    *d_out = std::move(out);
+    *count = n;
+    return DBTK_OK;
 }
 
 // the entries of class cls, sorted by (locus, k-mer)
 dbtk_status_t kcp_entries(dbtk_kcp_t* c, uint32_t cls, std::vector<KcpSlot>* out, uint64_t* count) {
-    KcpSlot* d_out = nullptr;
+    DevArr<KcpSlot> d_out;
     uint64_t n = 0;
-    dbtk_status_t st = kcp_compact(c, cls, out != nullptr, &d_out, &n);
+    const dbtk_status_t st = kcp_compact(c, cls, out != nullptr, &d_out, &n);
     if (st) return st;
     if (out) {
         out->resize(n);
-        if (n && hipMemcpy(out->data(), d_out, n * sizeof(KcpSlot), hipMemcpyDeviceToHost) != hipSuccess) { set_error("bait profile: copying the entries to the host failed"); st = DBTK_ERR_HIP; }
+        if (n && hipMemcpy(out->data(), d_out, n * sizeof(KcpSlot), hipMemcpyDeviceToHost) != hipSuccess) { set_error("bait profile: copying the entries to the host failed"); return DBTK_ERR_HIP; }
     }
-    if (d_out) (void)hipFree(d_out);
-    if (st) return st;
     if (count) *count = n;
     if (out) kcp_sort(*out, c->nloci);
     return DBTK_OK;
@@ -498,12 +476,6 @@ void kcp_fps_free_impl(dbtk_kcp_fps* f) {
     if (!f) return;
     (void)hipSetDevice(f->device);
     if (f->stream) (void)hipStreamSynchronize(f->stream);
-    if (f->ev0) (void)hipEventDestroy(f->ev0);
-    if (f->ev1) (void)hipEventDestroy(f->ev1);
-    if (f->d_cand) (void)hipFree(f->d_cand);
-    if (f->d_state) (void)hipFree(f->d_state);
-    if (f->d_words) (void)hipFree(f->d_words);
-    if (f->stream) (void)hipStreamDestroy(f->stream);
     delete f;
 }
 
@@ -511,34 +483,30 @@ dbtk_status_t kcp_fps_begin_impl(dbtk_kcp_t* c, dbtk_kcp_fps_t** out) {
     if (!c || !out) { set_error("dbtk_kcp_fps_begin: null argument"); return DBTK_ERR_ARG; }
     *out = nullptr;
     if (c->flags & DBTK_KCP_TP_ONLY) { set_error("dbtk_kcp_fps_begin: the handle counts true positives only (DBTK_KCP_TP_ONLY): it has no FP class to take candidates from"); return DBTK_ERR_ARG; }
-    KcpSlot* d_ent = nullptr;
+    DevArr<KcpSlot> d_ent;
     uint64_t n = 0;
-    dbtk_status_t st = kcp_compact(c, 1, true, &d_ent, &n);
+    const dbtk_status_t st = kcp_compact(c, 1, true, &d_ent, &n);
     if (st) return st;
-    dbtk_kcp_fps* f = new dbtk_kcp_fps;
+    std::unique_ptr<dbtk_kcp_fps, void (*)(dbtk_kcp_fps*)> hold(new dbtk_kcp_fps, kcp_fps_free_impl);  // (waits for its stream and goes before d_ent does)
+    dbtk_kcp_fps* f = hold.get();
     f->device = c->device; f->num_cu = c->num_cu; f->k = c->k; f->nloci = c->nloci; f->n = f->alive = n;
-    st = [&]() -> dbtk_status_t {
-        KCHK(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
-        KCHK(hipEventCreate(&f->ev0));
-        KCHK(hipEventCreate(&f->ev1));
-        KCHK(hipMalloc((void**)&f->d_words, 2 * sizeof(unsigned long long)));
-        KCHK(hipMemsetAsync(f->d_words, 0, 2 * sizeof(unsigned long long), f->stream));
-        if (n) {
-            if (hipMalloc((void**)&f->d_cand, n * sizeof(KcpCand)) != hipSuccess || hipMalloc((void**)&f->d_state, n * sizeof(uint32_t)) != hipSuccess) {
-                (void)hipGetLastError();
-                set_error("bait fps: no device memory for " + std::to_string(n) + " candidates (" + std::to_string(n * (sizeof(KcpCand) + sizeof(uint32_t))) + " bytes)");
-                return DBTK_ERR_NOMEM;
-            }
-            // (d_ent is complete: kcp_compact waited for the handle's stream)
-            hipLaunchKernelGGL(k_kcp_fps_begin, dim3(grid_cu(f->num_cu, n, 256)), dim3(256), 0, f->stream, (const KcpSlot*)d_ent, n, f->d_cand, f->d_state);
-            KCHK(hipGetLastError());
+    DEVCHK(f->stream.create(hipStreamNonBlocking));
+    DEVCHK(f->ev0.create(hipEventDefault));
+    DEVCHK(f->ev1.create(hipEventDefault));
+    DEVCHK(f->d_words.alloc(2));
+    DEVCHK(hipMemsetAsync(f->d_words, 0, 2 * sizeof(unsigned long long), f->stream));
+    if (n) {
+        if (f->d_cand.alloc(n) != hipSuccess || f->d_state.alloc(n) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("bait fps: no device memory for " + std::to_string(n) + " candidates (" + std::to_string(n * (sizeof(KcpCand) + sizeof(uint32_t))) + " bytes)");
+            return DBTK_ERR_NOMEM;
         }
-        KCHK(hipStreamSynchronize(f->stream));
-        return DBTK_OK;
-    }();
-    if (d_ent) (void)hipFree(d_ent);
-    if (st) { kcp_fps_free_impl(f); return st; }
-    *out = f;
+        // (d_ent is complete: kcp_compact waited for the handle's stream)
+        hipLaunchKernelGGL(k_kcp_fps_begin, dim3(grid_cu(f->num_cu, n, 256)), dim3(256), 0, f->stream, (const KcpSlot*)d_ent, n, f->d_cand.get(), f->d_state.get());
+        DEVCHK(hipGetLastError());
+    }
+    DEVCHK(hipStreamSynchronize(f->stream));
+    *out = hold.release();
     return DBTK_OK;
 }
 
@@ -549,21 +517,21 @@ dbtk_status_t kcp_fps_apply_impl(dbtk_kcp_fps_t* f, dbtk_kcp_t* c) {
                   std::to_string(f->device) + ", k " + std::to_string(f->k) + ", " + std::to_string(f->nloci) + " loci)");
         return DBTK_ERR_ARG;
     }
-    KCHK(hipSetDevice(f->device));
+    DEVCHK(hipSetDevice(f->device));
     unsigned long long w[KCP_WORDS];
     const dbtk_status_t st = kcp_words(c, w);  // the table is quiescent from here on (and whole: no insert failed)
     if (st) return st;
     if (!f->n) return DBTK_OK;
-    KCHK(hipEventRecord(f->ev0, f->stream));
-    hipLaunchKernelGGL(k_kcp_fps_apply, dim3(grid_cu(f->num_cu, f->n, 256)), dim3(256), 0, f->stream, (const KcpCand*)f->d_cand, f->d_state, f->n, (const KcpSlot*)c->d_tab,
-                       c->slots - 1, 64 - log2u64(c->slots), f->d_words);
-    KCHK(hipGetLastError());
-    KCHK(hipEventRecord(f->ev1, f->stream));
+    DEVCHK(hipEventRecord(f->ev0, f->stream));
+    hipLaunchKernelGGL(k_kcp_fps_apply, dim3(grid_cu(f->num_cu, f->n, 256)), dim3(256), 0, f->stream, (const KcpCand*)f->d_cand, f->d_state.get(), f->n, (const KcpSlot*)c->d_tab,
+                       c->slots - 1, 64 - log2u64(c->slots), f->d_words.get());
+    DEVCHK(hipGetLastError());
+    DEVCHK(hipEventRecord(f->ev1, f->stream));
     unsigned long long fw[2];
-    KCHK(hipMemcpyAsync(fw, f->d_words, sizeof fw, hipMemcpyDeviceToHost, f->stream));
-    KCHK(hipStreamSynchronize(f->stream));
+    DEVCHK(hipMemcpyAsync(fw, f->d_words, sizeof fw, hipMemcpyDeviceToHost, f->stream));
+    DEVCHK(hipStreamSynchronize(f->stream));
     float ms = 0;
-    KCHK(hipEventElapsedTime(&ms, f->ev0, f->ev1));
+    DEVCHK(hipEventElapsedTime(&ms, f->ev0, f->ev1));
     f->apply_ms += ms;
     f->lookups = fw[0];
     f->alive = f->n - fw[1];
@@ -575,12 +543,12 @@ struct FpsLine { uint32_t locus; uint64_t kmer; uint8_t mi, ma; };
 // the living candidates sorted by (locus, k-mer); `seen` (where not null): the loci that had a candidate, ascending
 dbtk_status_t kcp_fps_lines(dbtk_kcp_fps_t* f, std::vector<FpsLine>* lines, std::vector<uint32_t>* seen) {
     if (!f) { set_error("bait fps: null handle"); return DBTK_ERR_ARG; }
-    KCHK(hipSetDevice(f->device));
+    DEVCHK(hipSetDevice(f->device));
     std::vector<KcpCand> cand(f->n);
     std::vector<uint32_t> state(f->n);
     if (f->n) {
-        KCHK(hipMemcpy(cand.data(), f->d_cand, f->n * sizeof(KcpCand), hipMemcpyDeviceToHost));
-        KCHK(hipMemcpy(state.data(), f->d_state, f->n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        DEVCHK(hipMemcpy(cand.data(), f->d_cand, f->n * sizeof(KcpCand), hipMemcpyDeviceToHost));
+        DEVCHK(hipMemcpy(state.data(), f->d_state, f->n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
     lines->clear();
     for (uint64_t i = 0; i < f->n; ++i) {
@@ -604,32 +572,27 @@ dbtk_status_t kcp_text_stats_impl(int device_id, const uint32_t* n, const uint64
             return DBTK_ERR_ARG;
         }
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); set_error("no HIP device (the library has no CPU path)"); return DBTK_ERR_NO_DEVICE; }
+    if (const dbtk_status_t nd = device_count(&ndev)) return nd;
     if (device_id < 0 || device_id >= ndev) { set_error("dbtk_kcp_text_stats: device " + std::to_string(device_id) + " of " + std::to_string(ndev)); return DBTK_ERR_ARG; }
     if (!count) return DBTK_OK;
-    KCHK(hipSetDevice(device_id));
-    hipDeviceProp_t prop;
-    KCHK(hipGetDeviceProperties(&prop, device_id));
+    DEVCHK(hipSetDevice(device_id));
+    int num_cu = 1;
+    DEVCHK(device_cus(device_id, &num_cu));
     // one allocation: sum | sumsq | n | mean | sd
-    uint8_t* d = nullptr;
-    KCHK(hipMalloc((void**)&d, count * 28));
-    uint64_t *d_sum = (uint64_t*)d, *d_sq = d_sum + count;
+    DevArr<uint8_t> d;
+    DEVCHK(d.alloc(count * 28));
+    uint64_t *d_sum = (uint64_t*)d.get(), *d_sq = d_sum + count;
     uint32_t* d_n = (uint32_t*)(d_sq + count);
     float *d_mean = (float*)(d_n + count), *d_sd = d_mean + count;
-    const dbtk_status_t st = [&]() -> dbtk_status_t {
-        KCHK(hipMemcpy(d_sum, sum, count * 8, hipMemcpyHostToDevice));
-        KCHK(hipMemcpy(d_sq, sumsq, count * 8, hipMemcpyHostToDevice));
-        KCHK(hipMemcpy(d_n, n, count * 4, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_kcp_text_stats, dim3(grid_cu(std::max(1, prop.multiProcessorCount), count, 256)), dim3(256), 0, nullptr, (const uint32_t*)d_n, (const uint64_t*)d_sum,
-                           (const uint64_t*)d_sq, count, d_mean, d_sd);
-        KCHK(hipGetLastError());
-        KCHK(hipDeviceSynchronize());
-        KCHK(hipMemcpy(mean_out, d_mean, count * 4, hipMemcpyDeviceToHost));
-        KCHK(hipMemcpy(sd_out, d_sd, count * 4, hipMemcpyDeviceToHost));
-        return DBTK_OK;
-    }();
-    (void)hipFree(d);
-    return st;
+    DEVCHK(hipMemcpy(d_sum, sum, count * 8, hipMemcpyHostToDevice));
+    DEVCHK(hipMemcpy(d_sq, sumsq, count * 8, hipMemcpyHostToDevice));
+    DEVCHK(hipMemcpy(d_n, n, count * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_kcp_text_stats, dim3(grid_cu(num_cu, count, 256)), dim3(256), 0, nullptr, (const uint32_t*)d_n, (const uint64_t*)d_sum, (const uint64_t*)d_sq, count, d_mean, d_sd);
+    DEVCHK(hipGetLastError());
+    DEVCHK(hipDeviceSynchronize());
+    DEVCHK(hipMemcpy(mean_out, d_mean, count * 4, hipMemcpyDeviceToHost));
+    DEVCHK(hipMemcpy(sd_out, d_sd, count * 4, hipMemcpyDeviceToHost));
+    return DBTK_OK;
 }
 
 }  // namespace
@@ -713,13 +676,6 @@ void dbtk_kcp_free(dbtk_kcp_t* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
-    if (c->d_tab) (void)hipFree(c->d_tab);
-    if (c->d_words) (void)hipFree(c->d_words);
-    if (c->d_seq) (void)hipFree(c->d_seq);
-    if (c->d_off) (void)hipFree(c->d_off);
-    if (c->d_sel) (void)hipFree(c->d_sel);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -732,12 +688,12 @@ dbtk_status_t dbtk_kcp_add_device(dbtk_kcp_t* c, const void* d_seq, const void* 
         if (!c || (npairs && (!d_seq || !d_offsets || !d_src || !dst))) { set_error("dbtk_kcp_add_device: null argument"); return DBTK_ERR_ARG; }
         if (npairs > 0x7FFFFFFFull) { set_error("dbtk_kcp_add_device: more than 2^31 - 1 pairs in one call"); return DBTK_ERR_ARG; }
         if (!npairs) return kcp_add_impl(c, nullptr, nullptr, 0, nullptr, nullptr);
-        KCHK(hipSetDevice(c->device));
+        DEVCHK(hipSetDevice(c->device));
         // what decides which pairs are counted, and the bound on their new keys, comes to the host: 20 bytes per pair; the reads stay
         std::vector<uint64_t> off(2 * npairs + 1);
         std::vector<uint32_t> src(npairs);
-        KCHK(hipMemcpy(off.data(), d_offsets, off.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        KCHK(hipMemcpy(src.data(), d_src, src.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        DEVCHK(hipMemcpy(off.data(), d_offsets, off.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        DEVCHK(hipMemcpy(src.data(), d_src, src.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         return kcp_add_impl(c, nullptr, off.data(), npairs, src.data(), dst, (const uint8_t*)d_seq, (const uint64_t*)d_offsets);
     });
 }
@@ -780,11 +736,11 @@ dbtk_status_t dbtk_kcp_write(dbtk_kcp_t* c, const char* out_prefix) {
 
 dbtk_status_t dbtk_kcp_reset(dbtk_kcp_t* c) {
     if (!c) { set_error("dbtk_kcp_reset: null argument"); return DBTK_ERR_ARG; }
-    KCHK(hipSetDevice(c->device));
-    hipLaunchKernelGGL(k_kcp_fill, dim3(grid_for(c, c->slots, 256)), dim3(256), 0, c->stream, c->d_tab, c->slots);
-    KCHK(hipGetLastError());
-    KCHK(hipMemsetAsync(c->d_words, 0, sizeof(unsigned long long) * KCP_WORDS, c->stream));
-    KCHK(hipStreamSynchronize(c->stream));
+    DEVCHK(hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_kcp_fill, dim3(grid_for(c, c->slots, 256)), dim3(256), 0, c->stream, c->d_tab.get(), c->slots);
+    DEVCHK(hipGetLastError());
+    DEVCHK(hipMemsetAsync(c->d_words, 0, sizeof(unsigned long long) * KCP_WORDS, c->stream));
+    DEVCHK(hipStreamSynchronize(c->stream));
     c->occ_ub = 0;
     c->add_ms = 0;
     return DBTK_OK;
@@ -792,7 +748,7 @@ dbtk_status_t dbtk_kcp_reset(dbtk_kcp_t* c) {
 
 dbtk_status_t dbtk_kcp_stats(dbtk_kcp_t* c, uint64_t* table_bytes, uint64_t* slots, uint64_t* occupied) {
     if (!c) { set_error("dbtk_kcp_stats: null argument"); return DBTK_ERR_ARG; }
-    KCHK(hipSetDevice(c->device));
+    DEVCHK(hipSetDevice(c->device));
     unsigned long long w[KCP_WORDS];
     const dbtk_status_t st = kcp_words(c, w);
     if (st) return st;
@@ -804,7 +760,7 @@ dbtk_status_t dbtk_kcp_stats(dbtk_kcp_t* c, uint64_t* table_bytes, uint64_t* slo
 
 dbtk_status_t dbtk_kcp_times(dbtk_kcp_t* c, double* add_ms, uint64_t* inserts) {
     if (!c) { set_error("dbtk_kcp_times: null argument"); return DBTK_ERR_ARG; }
-    KCHK(hipSetDevice(c->device));
+    DEVCHK(hipSetDevice(c->device));
     unsigned long long w[KCP_WORDS];
     const dbtk_status_t st = kcp_words(c, w);
     if (st) return st;

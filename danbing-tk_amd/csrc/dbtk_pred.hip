@@ -12,19 +12,11 @@
 #include <vector>
 
 #include "../../include/dbtk_pred.h"
+#include "dbtk_dev.h"
 #include "dbtk_internal.h"
 #include "dbtk_pred_plan.h"
 
 using namespace dbtk;
-
-#define PCHK(call)                                                                                    \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) {                                                                       \
-            set_error(std::string(#call) + ": " + hipGetErrorString(e_));                             \
-            return DBTK_ERR_HIP;                                                                      \
-        }                                                                                             \
-    } while (0)
 
 // ---- locus t of ikmer.meta: its k-mers [si, ei) and its invariant k-mers [isi, iei).  bias_correction leaves a locus that lacks
 // either alone (pred.h:219-220): its Bias row stays 0, its columns are not divided.
@@ -305,9 +297,9 @@ static dbtk_status_t check_ikmer_meta(int device_id, uint64_t ns, uint64_t nk, u
     }
     for (uint64_t j = 0; j < nik; ++j) if (iki[j] >= nk) { set_error("ikmer.meta: invariant k-mer index out of range"); return DBTK_ERR_FORMAT; }
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device (the library has no CPU path)"); return DBTK_ERR_NO_DEVICE; }
+    if (const dbtk_status_t nd = device_count(&ndev)) return nd;
     if (device_id < 0 || device_id >= ndev) { set_error("device_id out of range"); return DBTK_ERR_ARG; }
-    PCHK(hipSetDevice(device_id));
+    DEVCHK(hipSetDevice(device_id));
     return DBTK_OK;
 }
 // `ikmer.meta` (dbtk_pred.h: dbtk_pred_create_from_file) into host vectors
@@ -390,13 +382,9 @@ static dbtk_status_t check_sample_range(uint64_t first, uint64_t n, uint64_t ns)
     return DBTK_OK;
 }
 static dbtk_status_t check_device_counts(const void* d_counts, int device, const char* who) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, d_counts) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device) {
-        (void)hipGetLastError();
-        set_error(std::string(who) + ": d_counts is not device memory of the handle's device");
-        return DBTK_ERR_ARG;
-    }
-    return DBTK_OK;
+    if (is_device_memory_of(d_counts, device)) return DBTK_OK;
+    set_error(std::string(who) + ": d_counts is not device memory of the handle's device");
+    return DBTK_ERR_ARG;
 }
 // a context's accumulated counts as one sample's count vector in HBM (*base): the context is of the handle's RPGG build (nk k-mers)
 // and device, has nothing unflushed, every batch of it is done, its counter replicas are folded, and a pending sticky error word is
@@ -411,7 +399,7 @@ static dbtk_status_t ctx_counts_ready(dbtk_ctx_t* ctx, int device, uint64_t nk, 
     void* b = nullptr; uint64_t n64 = 0;
     { const dbtk_status_t st = dbtk_ctx_accum_buffer(ctx, &b, &n64); if (st) return st; }
     if (!b || n64 < nk) { set_error("the context has no accumulators"); return DBTK_ERR_ARG; }
-    PCHK(hipSetDevice(device));
+    DEVCHK(hipSetDevice(device));
     *base = (const uint64_t*)b;
     return DBTK_OK;
 }
@@ -422,7 +410,7 @@ static dbtk_status_t launch_tile(void (*kernel)(P...), hipStream_t s, uint64_t r
     if (kt > 0x7FFFFFFFull) { set_error("too many k-mers for one launch"); return DBTK_ERR_ARG; }
     const uint32_t gy = (uint32_t)std::min<uint64_t>((n + PT_S - 1) / PT_S, 64);
     hipLaunchKernelGGL(kernel, dim3((uint32_t)kt, gy), dim3(64), 0, s, args...);
-    PCHK(hipGetLastError());
+    DEVCHK(hipGetLastError());
     return DBTK_OK;
 }
 
@@ -433,11 +421,14 @@ struct dbtk_pred {
     float* d_bias = nullptr;
     IkmerDev meta;
     uint32_t* d_loc = nullptr;  // d_loc[k]: locus of k-mer k, NOLOC where bias_correction skips it
-    Setup mem;                  // the creation's allocations (the three below it are regrown by the loads)
-    uint64_t* d_counts = nullptr; float* d_depth = nullptr; uint64_t stage_cap = 0;  // staging of dbtk_pred_load_samples
-    float* d_depth2 = nullptr; uint64_t depth_cap = 0;                                 // the depths of dbtk_pred_load_device
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    Setup mem;                  // the creation's allocations (dbtk_pred_free releases them; the owners below go when the handle does,
+                                // last to first: the loads' buffers, the events, the streams)
+    DevStream stream2;          // ws[1] (ws[0] = stream): a window's copies and kernels run on its buffer's stream
+    DevStream stream;
+    DevEvent ev[4];
+    DevArr<float> d_depth2;     // the depths of dbtk_pred_load_device, regrown by it
+    DevArr<float> d_depth;      // staging of dbtk_pred_load_samples, regrown by it: n depths
+    DevArr<uint64_t> d_counts;  //   ... and n * nk counts
     float ms[3] = {0, 0, 0};
     // the rows of d_G, the current window: loci [w_first, w_end), k-mers [w_row0, w_row0 + w_rows); on its stream ws(cur).  A handle of
     // dbtk_pred_create has one window for good: everything, on `stream`
@@ -453,7 +444,6 @@ struct dbtk_pred {
     float *d_raw = nullptr, *d_cor = nullptr;        // what the fused pass writes, [w_rows][ns] each (one set: one window's outputs are in flight at a time)
     uint64_t* h_stage = nullptr;                     // pinned, PW_STAGE x max_rows counts: what dbtk_pred_load_samples sends from
     float *h_raw = nullptr, *h_cor = nullptr;        // pinned, max_rows x ns: where the fused pass' outputs land
-    hipStream_t stream2 = nullptr;                   // ws[1] (ws[0] = stream): a window's copies and kernels run on its buffer's stream
     std::vector<uint8_t> dirty;                      // [ns]: staged into the window since d_G was last made from the staged counts
     int pending = -1;                                // the buffer whose fused pass was submitted and not collected yet
     uint64_t pend_rows = 0;
@@ -467,16 +457,16 @@ static dbtk_status_t pred_open_window(dbtk_pred* p, uint64_t first) {
     uint64_t end = 0, row0 = 0, rows = 0;
     if (first >= p->ntr) { set_error("dbtk_pred_window: first_locus " + std::to_string(first) + " >= ntr " + std::to_string(p->ntr)); return DBTK_ERR_ARG; }
     if (!dbtk_pred_plan::window(p->nkc.data(), p->ntr, p->nk, p->max_rows, first, &end, &row0, &rows)) { set_error("dbtk_pred_window: locus does not fit"); return DBTK_ERR_ARG; }
-    PCHK(hipSetDevice(p->device));
+    DEVCHK(hipSetDevice(p->device));
     const int slot = p->pending == (p->cur ^ 1) ? p->cur : p->cur ^ 1;
     hipStream_t s = p->ws(slot);
     if (rows) {
-        PCHK(hipMemsetAsync(p->d_wc[slot], 0, p->ns * rows * 8, s));
-        PCHK(hipMemsetAsync(p->d_G, 0, p->ns * rows * sizeof(float), s));
+        DEVCHK(hipMemsetAsync(p->d_wc[slot], 0, p->ns * rows * 8, s));
+        DEVCHK(hipMemsetAsync(p->d_G, 0, p->ns * rows * sizeof(float), s));
     }
     for (uint64_t i = 0; i < p->ns; ++i) p->h_depth[slot][i] = 1.f;
     std::fill(p->dirty.begin(), p->dirty.end(), (uint8_t)0);
-    PCHK(hipStreamSynchronize(s));
+    DEVCHK(hipStreamSynchronize(s));
     p->cur = slot; p->w_first = first; p->w_end = end; p->w_row0 = row0; p->w_rows = rows;
     return DBTK_OK;
 }
@@ -491,13 +481,13 @@ static dbtk_status_t pred_window_materialize(dbtk_pred* p) {
         uint64_t b = a;
         while (b < ns && p->dirty[b]) p->dirty[b++] = 0;
         if (rows) {
-            if (!sent) { PCHK(hipMemcpyAsync(p->d_wdepth[p->cur], p->h_depth[p->cur], ns * 4, hipMemcpyHostToDevice, s)); sent = true; }
+            if (!sent) { DEVCHK(hipMemcpyAsync(p->d_wdepth[p->cur], p->h_depth[p->cur], ns * 4, hipMemcpyHostToDevice, s)); sent = true; }
             const dbtk_status_t st = launch_tile(k_pred_load, s, rows, b - a, p->d_wc[p->cur] + a * rows, p->d_wdepth[p->cur] + a, p->d_G, rows, ns, a, (uint32_t)(b - a));
             if (st) return st;
         }
         a = b;
     }
-    if (sent) PCHK(hipStreamSynchronize(s));  // (h_depth may change with the next load)
+    if (sent) DEVCHK(hipStreamSynchronize(s));  // (h_depth may change with the next load)
     return DBTK_OK;
 }
 // host counts into the current window: counts[i * rows + r].  Sent PW_STAGE samples at a time from the pinned staging buffer; a caller
@@ -509,8 +499,8 @@ static dbtk_status_t pred_window_load_host(dbtk_pred* p, uint64_t first, uint64_
         const uint64_t ni = std::min<uint64_t>(PW_STAGE, n - i0);
         const uint64_t* src = counts + i0 * rows;
         if (src != p->h_stage) memcpy(p->h_stage, src, ni * rows * 8);
-        PCHK(hipMemcpyAsync(p->d_wc[p->cur] + (first + i0) * rows, p->h_stage, ni * rows * 8, hipMemcpyHostToDevice, s));
-        PCHK(hipStreamSynchronize(s));  // (the staging buffer is free again)
+        DEVCHK(hipMemcpyAsync(p->d_wc[p->cur] + (first + i0) * rows, p->h_stage, ni * rows * 8, hipMemcpyHostToDevice, s));
+        DEVCHK(hipStreamSynchronize(s));  // (the staging buffer is free again)
     }
     for (uint64_t i = 0; i < n; ++i) { p->h_depth[p->cur][first + i] = read_depth[i]; p->dirty[first + i] = 1; }
     return DBTK_OK;
@@ -551,8 +541,8 @@ static dbtk_status_t dbtk_pred_create_impl(int device_id, uint64_t ns, uint64_t 
     p->windowed = windowed; p->w_end = ntr; p->w_rows = nk;  // (a windowed handle opens its first window below)
     if (windowed) { p->max_rows = max_rows; p->nkc.assign(nk_cum, nk_cum + ntr); p->dirty.assign(ns, 0); }
     Setup& m = p->mem;
-    STEP(m, hipStreamCreate(&p->stream), "hipStreamCreate");
-    for (auto& e : p->ev) STEP(m, hipEventCreate(&e), "hipEventCreate");
+    STEP(m, p->stream.create(hipStreamDefault), "hipStreamCreate");
+    for (DevEvent& e : p->ev) STEP(m, e.create(hipEventDefault), "hipEventCreate");
     // the one allocation of a whole-matrix handle that competes with an aligner's tables for the HBM
     const std::string gfit = std::string("genotype matrix: 4 * ") + (windowed ? "max_rows" : "nk") + " * ns = " + std::to_string(grows * ns * sizeof(float)) + " bytes";
     m.device(&p->d_G, grows * ns * sizeof(float), "hipMalloc (genotype matrix)", &gfit);
@@ -562,7 +552,7 @@ static dbtk_status_t dbtk_pred_create_impl(int device_id, uint64_t ns, uint64_t 
         auto pin = [&](auto** q, uint64_t bytes, const char* what) { const std::string fit = what + win; m.host(q, bytes, what, &fit); };
         const std::string sfit = "hipStreamCreate" + win;
         const uint64_t cells = max_rows * ns;
-        STEP(m, hipStreamCreate(&p->stream2), "hipStreamCreate", &sfit);
+        STEP(m, p->stream2.create(hipStreamDefault), "hipStreamCreate", &sfit);
         for (int i = 0; i < 2; ++i) {
             dev(&p->d_wc[i], cells * 8, "hipMalloc (staged counts)");
             dev(&p->d_wdepth[i], ns * 4, "hipMalloc (depths)");
@@ -594,10 +584,6 @@ void dbtk_pred_free(dbtk_pred_t* p) {
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     if (p->stream2) (void)hipStreamSynchronize(p->stream2);  // (a submitted window that nobody collected)
     p->mem.release();
-    for (void* q : {(void*)p->d_counts, (void*)p->d_depth, (void*)p->d_depth2}) if (q) (void)hipFree(q);
-    for (auto& e : p->ev) if (e) (void)hipEventDestroy(e);
-    if (p->stream) (void)hipStreamDestroy(p->stream);
-    if (p->stream2) (void)hipStreamDestroy(p->stream2);
     delete p;
 }
 
@@ -616,20 +602,14 @@ static dbtk_status_t dbtk_pred_load_samples_impl(dbtk_pred_t* p, uint64_t first_
     if (!p || !counts || !read_depth) { set_error("null argument"); return DBTK_ERR_ARG; }
     { const dbtk_status_t st = check_sample_range(first_sample, n, p->ns); if (st) return st; }
     if (!n) return DBTK_OK;
-    PCHK(hipSetDevice(p->device));
+    DEVCHK(hipSetDevice(p->device));
     if (p->windowed) return pred_window_load_host(p, first_sample, n, counts, read_depth);
-    if (n > p->stage_cap) {
-        if (p->d_counts) PCHK(hipFree(p->d_counts));
-        if (p->d_depth) PCHK(hipFree(p->d_depth));
-        p->d_counts = nullptr; p->d_depth = nullptr; p->stage_cap = 0;
-        PCHK(hipMalloc(&p->d_counts, n * p->nk * 8));
-        PCHK(hipMalloc(&p->d_depth, n * 4));
-        p->stage_cap = n;
-    }
-    PCHK(hipMemcpyAsync(p->d_counts, counts, n * p->nk * 8, hipMemcpyHostToDevice, p->stream));
-    PCHK(hipMemcpyAsync(p->d_depth, read_depth, n * 4, hipMemcpyHostToDevice, p->stream));
-    { const dbtk_status_t st = launch_tile(k_pred_load, p->stream, p->nk, n, p->d_counts, p->d_depth, p->d_G, p->nk, p->ns, first_sample, (uint32_t)n); if (st) return st; }
-    PCHK(hipStreamSynchronize(p->stream));  // (the caller's buffers are free again)
+    DEVCHK(p->d_counts.reserve(n * p->nk, n * p->nk));
+    DEVCHK(p->d_depth.reserve(n, n));
+    DEVCHK(hipMemcpyAsync(p->d_counts, counts, n * p->nk * 8, hipMemcpyHostToDevice, p->stream));
+    DEVCHK(hipMemcpyAsync(p->d_depth, read_depth, n * 4, hipMemcpyHostToDevice, p->stream));
+    { const dbtk_status_t st = launch_tile(k_pred_load, p->stream, p->nk, n, p->d_counts.get(), p->d_depth.get(), p->d_G, p->nk, p->ns, first_sample, (uint32_t)n); if (st) return st; }
+    DEVCHK(hipStreamSynchronize(p->stream));  // (the caller's buffers are free again)
     return DBTK_OK;
 }
 
@@ -640,35 +620,30 @@ static dbtk_status_t pred_load_device_async(dbtk_pred_t* p, uint64_t first_sampl
     if (n == 1) {
         const uint32_t nb = (uint32_t)std::min<uint64_t>((p->nk + 255) / 256, 1u << 16);
         hipLaunchKernelGGL(k_pred_load_col, dim3(nb), dim3(256), 0, p->stream, d_counts, read_depth[0], p->d_G, p->nk, p->ns, first_sample);
-        PCHK(hipGetLastError());
+        DEVCHK(hipGetLastError());
         return DBTK_OK;
     }
-    if (n > p->depth_cap) {
-        if (p->d_depth2) PCHK(hipFree(p->d_depth2));
-        p->d_depth2 = nullptr; p->depth_cap = 0;
-        PCHK(hipMalloc(&p->d_depth2, n * 4));
-        p->depth_cap = n;
-    }
-    PCHK(hipMemcpyAsync(p->d_depth2, read_depth, n * 4, hipMemcpyHostToDevice, p->stream));
-    return launch_tile(k_pred_load, p->stream, p->nk, n, d_counts, p->d_depth2, p->d_G, p->nk, p->ns, first_sample, (uint32_t)n);
+    DEVCHK(p->d_depth2.reserve(n, n));
+    DEVCHK(hipMemcpyAsync(p->d_depth2, read_depth, n * 4, hipMemcpyHostToDevice, p->stream));
+    return launch_tile(k_pred_load, p->stream, p->nk, n, d_counts, p->d_depth2.get(), p->d_G, p->nk, p->ns, first_sample, (uint32_t)n);
 }
 
 dbtk_status_t dbtk_pred_load_device(dbtk_pred_t* p, uint64_t first_sample, uint64_t n, const uint64_t* d_counts, const float* read_depth) {
     if (!p || !d_counts || !read_depth) { set_error("null argument"); return DBTK_ERR_ARG; }
     { const dbtk_status_t st = check_sample_range(first_sample, n, p->ns); if (st) return st; }
     if (!n) return DBTK_OK;
-    PCHK(hipSetDevice(p->device));
+    DEVCHK(hipSetDevice(p->device));
     { const dbtk_status_t st = check_device_counts(d_counts, p->device, "dbtk_pred_load_device"); if (st) return st; }
     if (p->windowed) {  // the window's counts are staged (the fused pass reads all samples at once): one copy inside HBM
         hipStream_t s = p->ws(p->cur);
-        if (p->w_rows) PCHK(hipMemcpyAsync(p->d_wc[p->cur] + first_sample * p->w_rows, d_counts, n * p->w_rows * 8, hipMemcpyDeviceToDevice, s));
-        PCHK(hipStreamSynchronize(s));  // (d_counts is no longer being read)
+        if (p->w_rows) DEVCHK(hipMemcpyAsync(p->d_wc[p->cur] + first_sample * p->w_rows, d_counts, n * p->w_rows * 8, hipMemcpyDeviceToDevice, s));
+        DEVCHK(hipStreamSynchronize(s));  // (d_counts is no longer being read)
         for (uint64_t i = 0; i < n; ++i) { p->h_depth[p->cur][first_sample + i] = read_depth[i]; p->dirty[first_sample + i] = 1; }
         return DBTK_OK;
     }
     const dbtk_status_t st = pred_load_device_async(p, first_sample, n, d_counts, read_depth);
     if (st) return st;
-    PCHK(hipStreamSynchronize(p->stream));  // (d_counts is no longer being read)
+    DEVCHK(hipStreamSynchronize(p->stream));  // (d_counts is no longer being read)
     return DBTK_OK;
 }
 
@@ -681,45 +656,45 @@ dbtk_status_t dbtk_pred_load_ctx(dbtk_pred_t* p, uint64_t sample, dbtk_ctx_t* ct
     { const dbtk_status_t st = ctx_counts_ready(ctx, p->device, p->nk, whose, &base); if (st) return st; }
     const dbtk_status_t st = pred_load_device_async(p, sample, 1, base, &read_depth);
     if (st) return st;
-    PCHK(hipStreamSynchronize(p->stream));  // (d_accum is no longer being read: dbtk_ctx_reset may follow)
+    DEVCHK(hipStreamSynchronize(p->stream));  // (d_accum is no longer being read: dbtk_ctx_reset may follow)
     return DBTK_OK;
 }
 
 dbtk_status_t dbtk_pred_correct(dbtk_pred_t* p) {
     if (!p) { set_error("null argument"); return DBTK_ERR_ARG; }
-    PCHK(hipSetDevice(p->device));
+    DEVCHK(hipSetDevice(p->device));
     // the loci and rows at work: the current window's (everything on a whole-matrix handle); its Bias rows alone are made again
     const uint64_t t0 = p->w_first, nl = p->w_end - p->w_first, row0 = p->w_row0, rows = p->w_rows;
     hipStream_t s = p->ws(p->cur);
     if (p->windowed) { const dbtk_status_t st = pred_window_materialize(p); if (st) return st; }
-    PCHK(hipMemsetAsync(p->d_bias + t0 * p->ns, 0, nl * p->ns * sizeof(float), s));
-    PCHK(hipEventRecord(p->ev[0], s));
+    DEVCHK(hipMemsetAsync(p->d_bias + t0 * p->ns, 0, nl * p->ns * sizeof(float), s));
+    DEVCHK(hipEventRecord(p->ev[0], s));
     hipLaunchKernelGGL(k_pred_bias, dim3((uint32_t)nl, (uint32_t)((p->ns + 63) / 64)), dim3(64), 0, s, p->d_G, p->meta.nk, p->meta.nik, p->meta.iki, p->meta.ikmc, p->d_bias, p->ns,
                        (uint32_t)t0, (uint32_t)row0);
-    PCHK(hipGetLastError());
-    PCHK(hipEventRecord(p->ev[1], s));
+    DEVCHK(hipGetLastError());
+    DEVCHK(hipEventRecord(p->ev[1], s));
     hipLaunchKernelGGL(k_pred_bias_norm, dim3((uint32_t)nl), dim3(256), 0, s, p->meta.nk, p->meta.nik, p->d_bias, p->ns, (uint32_t)t0);
-    PCHK(hipGetLastError());
-    PCHK(hipEventRecord(p->ev[2], s));
+    DEVCHK(hipGetLastError());
+    DEVCHK(hipEventRecord(p->ev[2], s));
     if (rows) {
         const uint64_t nb = (rows + 4 * PR_ROWS - 1) / (4 * PR_ROWS);
         hipLaunchKernelGGL(k_pred_correct, dim3((uint32_t)nb), dim3(256), 0, s, p->d_G, p->d_loc + row0, p->d_bias, rows, p->ns);
-        PCHK(hipGetLastError());
+        DEVCHK(hipGetLastError());
     }
-    PCHK(hipEventRecord(p->ev[3], s));
-    PCHK(hipStreamSynchronize(s));
-    for (int i = 0; i < 3; ++i) PCHK(hipEventElapsedTime(&p->ms[i], p->ev[i], p->ev[i + 1]));
+    DEVCHK(hipEventRecord(p->ev[3], s));
+    DEVCHK(hipStreamSynchronize(s));
+    for (int i = 0; i < 3; ++i) DEVCHK(hipEventElapsedTime(&p->ms[i], p->ev[i], p->ev[i + 1]));
     return DBTK_OK;
 }
 
 dbtk_status_t dbtk_pred_matrix(dbtk_pred_t* p, float* out) {
     if (!p || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
-    PCHK(hipSetDevice(p->device));
+    DEVCHK(hipSetDevice(p->device));
     if (p->windowed) {
         { const dbtk_status_t st = pred_window_materialize(p); if (st) return st; }
-        PCHK(hipStreamSynchronize(p->ws(p->cur)));
+        DEVCHK(hipStreamSynchronize(p->ws(p->cur)));
     }
-    if (p->w_rows) PCHK(hipMemcpy(out, p->d_G, p->w_rows * p->ns * sizeof(float), hipMemcpyDeviceToHost));
+    if (p->w_rows) DEVCHK(hipMemcpy(out, p->d_G, p->w_rows * p->ns * sizeof(float), hipMemcpyDeviceToHost));
     return DBTK_OK;
 }
 
@@ -747,22 +722,22 @@ dbtk_status_t dbtk_pred_window_stage(dbtk_pred_t* p, uint64_t** buf, uint64_t* c
 dbtk_status_t dbtk_pred_window_submit(dbtk_pred_t* p) {
     { const dbtk_status_t st = need_windowed(p, "dbtk_pred_window_submit"); if (st) return st; }
     if (p->pending >= 0) { set_error("dbtk_pred_window_submit: the outputs of the window submitted before have not been taken (dbtk_pred_window_outputs)"); return DBTK_ERR_ARG; }
-    PCHK(hipSetDevice(p->device));
+    DEVCHK(hipSetDevice(p->device));
     const int c = p->cur;
     hipStream_t s = p->ws(c);
     const uint64_t ns = p->ns, rows = p->w_rows, nl = p->w_end - p->w_first;
-    PCHK(hipMemcpyAsync(p->d_wdepth[c], p->h_depth[c], ns * 4, hipMemcpyHostToDevice, s));
-    PCHK(hipMemsetAsync(p->d_bias + p->w_first * ns, 0, nl * ns * sizeof(float), s));
+    DEVCHK(hipMemcpyAsync(p->d_wdepth[c], p->h_depth[c], ns * 4, hipMemcpyHostToDevice, s));
+    DEVCHK(hipMemsetAsync(p->d_bias + p->w_first * ns, 0, nl * ns * sizeof(float), s));
     if (rows) {
         if (nl > 0x7FFFFFFFull) { set_error("window too large for one launch"); return DBTK_ERR_ARG; }
         hipLaunchKernelGGL(k_pred_wbias, dim3((uint32_t)nl, (uint32_t)((ns + WB_S - 1) / WB_S)), dim3(64), 0, s, p->d_wc[c], p->d_wdepth[c], p->meta.nk, p->meta.nik, p->meta.iki, p->meta.ikmc,
                            p->d_bias, ns, rows, (uint32_t)p->w_first, (uint32_t)p->w_row0);
-        PCHK(hipGetLastError());
+        DEVCHK(hipGetLastError());
         hipLaunchKernelGGL(k_pred_bias_norm, dim3((uint32_t)nl), dim3(256), 0, s, p->meta.nk, p->meta.nik, p->d_bias, ns, (uint32_t)p->w_first);
-        PCHK(hipGetLastError());
+        DEVCHK(hipGetLastError());
         { const dbtk_status_t st = launch_tile(k_pred_wfused, s, rows, ns, p->d_wc[c], p->d_wdepth[c], p->d_loc + p->w_row0, p->d_bias, p->d_raw, p->d_cor, rows, ns); if (st) return st; }
-        PCHK(hipMemcpyAsync(p->h_raw, p->d_raw, rows * ns * sizeof(float), hipMemcpyDeviceToHost, s));
-        PCHK(hipMemcpyAsync(p->h_cor, p->d_cor, rows * ns * sizeof(float), hipMemcpyDeviceToHost, s));
+        DEVCHK(hipMemcpyAsync(p->h_raw, p->d_raw, rows * ns * sizeof(float), hipMemcpyDeviceToHost, s));
+        DEVCHK(hipMemcpyAsync(p->h_cor, p->d_cor, rows * ns * sizeof(float), hipMemcpyDeviceToHost, s));
     }
     p->pending = c; p->pend_rows = rows;
     return DBTK_OK;
@@ -770,10 +745,10 @@ dbtk_status_t dbtk_pred_window_submit(dbtk_pred_t* p) {
 dbtk_status_t dbtk_pred_window_outputs_pinned(dbtk_pred_t* p, const float** raw, const float** corrected, uint64_t* rows) {
     { const dbtk_status_t st = need_windowed(p, "dbtk_pred_window_outputs"); if (st) return st; }
     if (p->pending < 0) { const dbtk_status_t st = dbtk_pred_window_submit(p); if (st) return st; }
-    PCHK(hipSetDevice(p->device));
+    DEVCHK(hipSetDevice(p->device));
     const int c = p->pending;
     p->pending = -1;  // (whatever the wait says: a failed window is not waited for twice)
-    PCHK(hipStreamSynchronize(p->ws(c)));
+    DEVCHK(hipStreamSynchronize(p->ws(c)));
     if (raw) *raw = p->h_raw;
     if (corrected) *corrected = p->h_cor;
     if (rows) *rows = p->pend_rows;
@@ -789,8 +764,8 @@ dbtk_status_t dbtk_pred_window_outputs(dbtk_pred_t* p, float* raw_out, float* co
 }
 dbtk_status_t dbtk_pred_bias(dbtk_pred_t* p, float* out) {
     if (!p || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
-    PCHK(hipSetDevice(p->device));
-    PCHK(hipMemcpy(out, p->d_bias, p->ntr * p->ns * sizeof(float), hipMemcpyDeviceToHost));
+    DEVCHK(hipSetDevice(p->device));
+    DEVCHK(hipMemcpy(out, p->d_bias, p->ntr * p->ns * sizeof(float), hipMemcpyDeviceToHost));
     return DBTK_OK;
 }
 dbtk_status_t dbtk_pred_times(dbtk_pred_t* p, float ms[3]) {
@@ -833,14 +808,15 @@ struct dbtk_dosage {
     DosItem* d_items = nullptr;
     uint64_t* d_part = nullptr;
     Setup mem;                                   // the creation's allocations (all above)
-    uint64_t* d_stage = nullptr;                 // 16 samples' counts of dbtk_dosage_load_samples, allocated by its first call
     uint32_t nitems = 0, nfold = 0;
     uint64_t bytes = 0;
     std::vector<float> depth;                    // host copy: what the next load sends along
     bool finished = false;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     float ms[2] = {0, 0};
+    // (gone with the handle, last to first: the staging, the events, the stream)
+    DevStream stream;
+    DevEvent ev[4];
+    DevArr<uint64_t> d_stage;                    // 16 samples' counts of dbtk_dosage_load_samples, allocated by its first call
 };
 constexpr uint64_t DS_STAGE = 16;  // samples per transfer of dbtk_dosage_load_samples (what danbing-tk-pred stages for the matrix, too)
 
@@ -850,9 +826,6 @@ void dbtk_dosage_free(dbtk_dosage_t* d) {
     if (!d) return;
     (void)hipSetDevice(d->device);
     d->mem.release();
-    if (d->d_stage) (void)hipFree(d->d_stage);
-    for (auto& e : d->ev) if (e) (void)hipEventDestroy(e);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
     delete d;
 }
 
@@ -879,9 +852,9 @@ static dbtk_status_t dbtk_dosage_create_impl(int device_id, uint64_t ns, uint64_
     const char* const what = "hipMalloc (dosage tables)";
     const std::string fit = "dosage tables: " + std::to_string(d->bytes) + " bytes (20 * ntr * ns = " + std::to_string(cells * 20) + " of them)";
     Setup& m = d->mem;
-    hipStream_t& s = d->stream;
-    STEP(m, hipStreamCreate(&s), "hipStreamCreate");
-    for (auto& e : d->ev) STEP(m, hipEventCreate(&e), "hipEventCreate");
+    DevStream& s = d->stream;
+    STEP(m, s.create(hipStreamDefault), "hipStreamCreate");
+    for (DevEvent& e : d->ev) STEP(m, e.create(hipEventDefault), "hipEventCreate");
     for (auto& t : tabs) m.device(t.slot, t.bytes, what, &fit);
     ikmer_upload(m, &d->meta, ntr, nk_cum, nik_cum, nik, iki, ikmc, s, what, &fit);
     STEP(m, hipMemsetAsync(d->d_kms, 0, cells * 8, s), "hipMemset");
@@ -923,21 +896,21 @@ static dbtk_status_t dosage_load(dbtk_dosage_t* d, uint64_t first, uint64_t n, c
     hipStream_t s = d->stream;
     for (uint64_t i = 0; i < n; ++i) d->depth[first + i] = read_depth[i];
     d->finished = false;
-    PCHK(hipMemcpyAsync(d->d_depth + first, d->depth.data() + first, n * 4, hipMemcpyHostToDevice, s));
-    PCHK(hipEventRecord(d->ev[0], s));
+    DEVCHK(hipMemcpyAsync(d->d_depth + first, d->depth.data() + first, n * 4, hipMemcpyHostToDevice, s));
+    DEVCHK(hipEventRecord(d->ev[0], s));
     for (uint64_t i = 0; i < n && d->nitems; ++i) {
         hipLaunchKernelGGL(k_dosage_sample, dim3(d->nitems), dim3(DS_T), 0, s, d_counts + i * d->nk, read_depth[i], d->d_items, d->meta.nk, d->meta.nik, d->meta.iki, d->meta.ikmc,
                            d->d_kms, d->d_raw, d->d_part, d->ns, first + i);
-        PCHK(hipGetLastError());
+        DEVCHK(hipGetLastError());
         if (d->nfold) {
             hipLaunchKernelGGL(k_dosage_fold, dim3((d->nfold + 63) / 64), dim3(64), 0, s, d->d_floc, d->d_fbeg, d->d_part, d->d_kms, d->ns, first + i, d->nfold);
-            PCHK(hipGetLastError());
+            DEVCHK(hipGetLastError());
         }
     }
-    PCHK(hipEventRecord(d->ev[1], s));
-    PCHK(hipStreamSynchronize(s));  // (d_counts is no longer being read)
+    DEVCHK(hipEventRecord(d->ev[1], s));
+    DEVCHK(hipStreamSynchronize(s));  // (d_counts is no longer being read)
     float ms = 0;
-    PCHK(hipEventElapsedTime(&ms, d->ev[0], d->ev[1]));
+    DEVCHK(hipEventElapsedTime(&ms, d->ev[0], d->ev[1]));
     *ms_sum += ms;
     return DBTK_OK;
 }
@@ -946,7 +919,7 @@ dbtk_status_t dbtk_dosage_load_device(dbtk_dosage_t* d, uint64_t first_sample, u
     if (!d || !d_counts || !read_depth) { set_error("null argument"); return DBTK_ERR_ARG; }
     { const dbtk_status_t st = check_sample_range(first_sample, n, d->ns); if (st) return st; }
     if (!n) return DBTK_OK;
-    PCHK(hipSetDevice(d->device));
+    DEVCHK(hipSetDevice(d->device));
     { const dbtk_status_t st = check_device_counts(d_counts, d->device, "dbtk_dosage_load_device"); if (st) return st; }
     float ms = 0;
     { const dbtk_status_t st = dosage_load(d, first_sample, n, d_counts, read_depth, &ms); if (st) return st; }
@@ -970,15 +943,15 @@ static dbtk_status_t dbtk_dosage_load_samples_impl(dbtk_dosage_t* d, uint64_t fi
     if (!d || !counts || !read_depth) { set_error("null argument"); return DBTK_ERR_ARG; }
     { const dbtk_status_t st = check_sample_range(first_sample, n, d->ns); if (st) return st; }
     if (!n) return DBTK_OK;
-    PCHK(hipSetDevice(d->device));
+    DEVCHK(hipSetDevice(d->device));
     if (!d->d_stage) {
-        PCHK(hipMalloc(&d->d_stage, DS_STAGE * d->nk * 8));
+        DEVCHK(d->d_stage.alloc(DS_STAGE * d->nk));
         d->bytes += DS_STAGE * d->nk * 8;
     }
     float ms = 0;
     for (uint64_t i0 = 0; i0 < n; i0 += DS_STAGE) {
         const uint64_t ni = std::min<uint64_t>(DS_STAGE, n - i0);
-        PCHK(hipMemcpyAsync(d->d_stage, counts + i0 * d->nk, ni * d->nk * 8, hipMemcpyHostToDevice, d->stream));
+        DEVCHK(hipMemcpyAsync(d->d_stage, counts + i0 * d->nk, ni * d->nk * 8, hipMemcpyHostToDevice, d->stream));
         { const dbtk_status_t st = dosage_load(d, first_sample + i0, ni, d->d_stage, read_depth + i0, &ms); if (st) return st; }  // (the staging buffer is free again)
     }
     d->ms[0] = ms;
@@ -987,40 +960,40 @@ static dbtk_status_t dbtk_dosage_load_samples_impl(dbtk_dosage_t* d, uint64_t fi
 
 dbtk_status_t dbtk_dosage_finish(dbtk_dosage_t* d) {
     if (!d) { set_error("null argument"); return DBTK_ERR_ARG; }
-    PCHK(hipSetDevice(d->device));
+    DEVCHK(hipSetDevice(d->device));
     hipStream_t s = d->stream;
-    PCHK(hipEventRecord(d->ev[2], s));
-    PCHK(hipMemcpyAsync(d->d_bias, d->d_raw, d->ntr * d->ns * sizeof(float), hipMemcpyDeviceToDevice, s));
+    DEVCHK(hipEventRecord(d->ev[2], s));
+    DEVCHK(hipMemcpyAsync(d->d_bias, d->d_raw, d->ntr * d->ns * sizeof(float), hipMemcpyDeviceToDevice, s));
     hipLaunchKernelGGL(k_pred_bias_norm, dim3((uint32_t)d->ntr), dim3(256), 0, s, d->meta.nk, d->meta.nik, d->d_bias, d->ns, 0u);
-    PCHK(hipGetLastError());
-    PCHK(hipEventRecord(d->ev[3], s));
-    PCHK(hipStreamSynchronize(s));
-    PCHK(hipEventElapsedTime(&d->ms[1], d->ev[2], d->ev[3]));
+    DEVCHK(hipGetLastError());
+    DEVCHK(hipEventRecord(d->ev[3], s));
+    DEVCHK(hipStreamSynchronize(s));
+    DEVCHK(hipEventElapsedTime(&d->ms[1], d->ev[2], d->ev[3]));
     d->finished = true;
     return DBTK_OK;
 }
 
 dbtk_status_t dbtk_dosage_kms(dbtk_dosage_t* d, uint64_t* out) {
     if (!d || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
-    PCHK(hipSetDevice(d->device));
-    PCHK(hipMemcpy(out, d->d_kms, d->ntr * d->ns * 8, hipMemcpyDeviceToHost));
+    DEVCHK(hipSetDevice(d->device));
+    DEVCHK(hipMemcpy(out, d->d_kms, d->ntr * d->ns * 8, hipMemcpyDeviceToHost));
     return DBTK_OK;
 }
 dbtk_status_t dbtk_dosage_bias(dbtk_dosage_t* d, float* out) {
     if (!d || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
     if (!d->finished) { set_error("dbtk_dosage_bias: samples were loaded since the last dbtk_dosage_finish (or it was never called)"); return DBTK_ERR_ARG; }
-    PCHK(hipSetDevice(d->device));
-    PCHK(hipMemcpy(out, d->d_bias, d->ntr * d->ns * sizeof(float), hipMemcpyDeviceToHost));
+    DEVCHK(hipSetDevice(d->device));
+    DEVCHK(hipMemcpy(out, d->d_bias, d->ntr * d->ns * sizeof(float), hipMemcpyDeviceToHost));
     return DBTK_OK;
 }
 dbtk_status_t dbtk_dosage_values(dbtk_dosage_t* d, float* out) {
     if (!d || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
     if (!d->finished) { set_error("dbtk_dosage_values: samples were loaded since the last dbtk_dosage_finish (or it was never called)"); return DBTK_ERR_ARG; }
-    PCHK(hipSetDevice(d->device));
+    DEVCHK(hipSetDevice(d->device));
     hipLaunchKernelGGL(k_dosage_values, dim3((uint32_t)d->ntr, (uint32_t)((d->ns + 255) / 256)), dim3(256), 0, d->stream, d->d_kms, d->d_bias, d->d_depth, d->meta.nk, d->meta.nik, d->d_values, d->ns);
-    PCHK(hipGetLastError());
-    PCHK(hipMemcpyAsync(out, d->d_values, d->ntr * d->ns * sizeof(float), hipMemcpyDeviceToHost, d->stream));
-    PCHK(hipStreamSynchronize(d->stream));
+    DEVCHK(hipGetLastError());
+    DEVCHK(hipMemcpyAsync(out, d->d_values, d->ntr * d->ns * sizeof(float), hipMemcpyDeviceToHost, d->stream));
+    DEVCHK(hipStreamSynchronize(d->stream));
     return DBTK_OK;
 }
 dbtk_status_t dbtk_dosage_times(dbtk_dosage_t* d, float ms[2]) {
@@ -1050,23 +1023,23 @@ dbtk_status_t dbtk_dosage_load_samples(dbtk_dosage_t* d, uint64_t first_sample, 
 namespace dbtk {
 static dbtk_status_t rows_meta(RowsView* out, const IkmerDev& meta, uint64_t ntr, hipStream_t s) {
     out->nk_cum.resize(ntr);
-    PCHK(hipMemcpyAsync(out->nk_cum.data(), meta.nk, ntr * 4, hipMemcpyDeviceToHost, s));
-    PCHK(hipStreamSynchronize(s));
+    DEVCHK(hipMemcpyAsync(out->nk_cum.data(), meta.nk, ntr * 4, hipMemcpyDeviceToHost, s));
+    DEVCHK(hipStreamSynchronize(s));
     return DBTK_OK;
 }
 dbtk_status_t pred_rows(dbtk_pred* p, RowsView* out) {
     if (!p || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
     if (p->windowed) { set_error("a windowed handle holds a part of the rows at a time: the association scan needs the whole matrix (dbtk_pred_create)"); return DBTK_ERR_ARG; }
-    PCHK(hipSetDevice(p->device));
+    DEVCHK(hipSetDevice(p->device));
     out->device = p->device; out->ns = p->ns; out->nrows = p->nk; out->ntr = p->ntr; out->d_rows = p->d_G;
     return rows_meta(out, p->meta, p->ntr, p->stream);
 }
 dbtk_status_t dosage_rows(dbtk_dosage* d, RowsView* out) {
     if (!d || !out) { set_error("null argument"); return DBTK_ERR_ARG; }
     if (!d->finished) { set_error("the dosage handle is unfinished: samples were loaded since the last dbtk_dosage_finish (or it was never called)"); return DBTK_ERR_ARG; }
-    PCHK(hipSetDevice(d->device));
+    DEVCHK(hipSetDevice(d->device));
     hipLaunchKernelGGL(k_dosage_values, dim3((uint32_t)d->ntr, (uint32_t)((d->ns + 255) / 256)), dim3(256), 0, d->stream, d->d_kms, d->d_bias, d->d_depth, d->meta.nk, d->meta.nik, d->d_values, d->ns);
-    PCHK(hipGetLastError());
+    DEVCHK(hipGetLastError());
     out->device = d->device; out->ns = d->ns; out->nrows = d->ntr; out->ntr = d->ntr; out->d_rows = d->d_values;
     { const dbtk_status_t st = rows_meta(out, d->meta, d->ntr, d->stream); if (st) return st; }
     for (uint64_t t = 0; t < d->ntr; ++t) out->nk_cum[t] = (uint32_t)(t + 1);  // a row per locus

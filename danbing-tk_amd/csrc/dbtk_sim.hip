@@ -15,18 +15,10 @@
 #include <vector>
 
 #include "../../include/dbtk_sim.h"
+#include "dbtk_dev.h"
 #include "dbtk_internal.h"
 
 using namespace dbtk;
-
-#define SCHK(call)                                                                                    \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) {                                                                       \
-            set_error(std::string(#call) + ": " + hipGetErrorString(e_));                             \
-            return DBTK_ERR_HIP;                                                                      \
-        }                                                                                             \
-    } while (0)
 
 namespace {
 
@@ -153,11 +145,11 @@ struct HostContig {
     uint64_t iv0 = 0, iv1 = 0, iv_span = 0;  // its intervals (dbtk_sim::ivs, ascending by `from`) and the longest to - from among them
 };
 
-struct BufSet {
-    uint8_t* d_seq = nullptr; uint64_t seq_cap = 0;
-    uint64_t* d_off = nullptr; uint64_t off_cap = 0;
-    uint32_t* d_src = nullptr; uint64_t src_cap = 0;
-    hipEvent_t made = nullptr, consumed = nullptr;
+struct BufSet {  // (destroyed last to first: the buffers, then the events)
+    DevEvent consumed, made;
+    DevArr<uint32_t> d_src;
+    DevArr<uint64_t> d_off;
+    DevArr<uint8_t> d_seq;
     bool in_use = false;  // `consumed` has been recorded since the set was last filled
     uint64_t npairs = 0;
 };
@@ -174,17 +166,19 @@ struct dbtk_sim {
     std::vector<SimIv> ivs;      // every kept contig's intervals (dbtk_sim_labels)
     // device side
     int device = -1, num_cu = 1;
-    hipStream_t stream = nullptr;
     std::vector<uint32_t> group_c0;  // contigs [group_c0[g], group_c0[g + 1]) form group g
     int64_t resident = -1;
-    uint8_t* d_arena = nullptr; uint64_t arena_cap = 0;
-    SimContig* d_ctg = nullptr;
-    uint64_t* d_brk_pos = nullptr;
-    uint32_t* d_brk_src = nullptr;
-    BufSet set[2];
+    uint64_t arena_cap = 0;
     int cur = -1;  // the set of the batch made last
-    std::deque<std::pair<hipEvent_t, hipEvent_t>> timing;  // around launches whose time is not yet taken
-    std::vector<hipEvent_t> spare;
+    // (destroyed last to first, as sim_release_device lets go of them: the batch sets, the timing events, the tables, the stream)
+    DevStream stream;
+    DevArr<uint32_t> d_brk_src;
+    DevArr<uint64_t> d_brk_pos;
+    DevArr<SimContig> d_ctg;
+    DevArr<uint8_t> d_arena;
+    std::vector<DevEvent> spare;
+    std::deque<std::pair<DevEvent, DevEvent>> timing;  // around launches whose time is not yet taken
+    BufSet set[2];
     double tile_ms = 0;
     uint64_t bytes_written = 0, bytes_uploaded = 0;
 };
@@ -384,35 +378,23 @@ void sim_release_device(dbtk_sim* s) {
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     for (BufSet& b : s->set) {
         if (b.in_use && b.consumed) (void)hipEventSynchronize(b.consumed);
-        if (b.d_seq) (void)hipFree(b.d_seq);
-        if (b.d_off) (void)hipFree(b.d_off);
-        if (b.d_src) (void)hipFree(b.d_src);
-        if (b.made) (void)hipEventDestroy(b.made);
-        if (b.consumed) (void)hipEventDestroy(b.consumed);
         b = BufSet();
     }
-    for (auto& t : s->timing) { (void)hipEventDestroy(t.first); (void)hipEventDestroy(t.second); }
     s->timing.clear();
-    for (hipEvent_t e : s->spare) (void)hipEventDestroy(e);
     s->spare.clear();
-    if (s->d_arena) (void)hipFree(s->d_arena);
-    if (s->d_ctg) (void)hipFree(s->d_ctg);
-    if (s->d_brk_pos) (void)hipFree(s->d_brk_pos);
-    if (s->d_brk_src) (void)hipFree(s->d_brk_src);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    s->d_arena = nullptr; s->d_ctg = nullptr; s->d_brk_pos = nullptr; s->d_brk_src = nullptr; s->stream = nullptr;
+    s->d_arena.drop(); s->d_ctg.drop(); s->d_brk_pos.drop(); s->d_brk_src.drop();
+    s->stream = DevStream();
     s->device = -1; s->resident = -1; s->cur = -1; s->group_c0.clear();
 }
 
-template <class T> dbtk_status_t sim_alloc(T** p, uint64_t n, const char* what) {
-    *p = nullptr;
-    if (hipMalloc((void**)p, std::max<uint64_t>(n, 1) * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        set_error(std::string("simulated reads: no device memory for ") + what + " (" + std::to_string(n * sizeof(T)) + " bytes)");
-        return DBTK_ERR_NOMEM;
-    }
-    return DBTK_OK;
+dbtk_status_t sim_nomem(hipError_t e, const char* what, uint64_t bytes) {
+    if (e == hipSuccess) return DBTK_OK;
+    (void)hipGetLastError();
+    set_error(std::string("simulated reads: no device memory for ") + what + " (" + std::to_string(bytes) + " bytes)");
+    return DBTK_ERR_NOMEM;
+}
+template <class T> dbtk_status_t sim_alloc(DevArr<T>& a, uint64_t n, const char* what) {
+    return sim_nomem(a.alloc(std::max<uint64_t>(n, 1)), what, n * sizeof(T));  // (never empty)
 }
 
 dbtk_status_t sim_attach_impl(dbtk_sim_t* s, int device_id) {
@@ -424,7 +406,7 @@ dbtk_status_t sim_attach_impl(dbtk_sim_t* s, int device_id) {
         if (arena < s->flen) { set_error("DBTK_SIM_ARENA_BYTES: at least the fragment length (" + std::to_string(s->flen) + ")"); return DBTK_ERR_ARG; }
     }
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); set_error("no HIP device (the library has no CPU path)"); return DBTK_ERR_NO_DEVICE; }
+    if (const dbtk_status_t nd = device_count(&ndev)) return nd;
     if (device_id < 0 || device_id >= ndev) { set_error("dbtk_sim_attach: device " + std::to_string(device_id) + " of " + std::to_string(ndev)); return DBTK_ERR_ARG; }
     // groups of whole contigs, each within the arena; the device table holds every contig's offset inside its group
     std::vector<SimContig> tab(s->ctg.size());
@@ -442,28 +424,26 @@ dbtk_status_t sim_attach_impl(dbtk_sim_t* s, int device_id) {
         largest = std::max(largest, used);
     }
     g0.push_back((uint32_t)s->ctg.size());
-    SCHK(hipSetDevice(device_id));
+    DEVCHK(hipSetDevice(device_id));
     s->device = device_id;
     dbtk_status_t st = [&]() -> dbtk_status_t {
-        hipDeviceProp_t prop;
-        SCHK(hipGetDeviceProperties(&prop, device_id));
-        s->num_cu = std::max(1, prop.multiProcessorCount);
-        SCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+        DEVCHK(device_cus(device_id, &s->num_cu));
+        DEVCHK(s->stream.create(hipStreamNonBlocking));
         dbtk_status_t a;
         // (16 bytes of slack: the 16-byte read of a chunk never leaves its read, but the allocation is never empty either)
-        if ((a = sim_alloc(&s->d_arena, largest + 16, "the assembly's arena"))) return a;
+        if ((a = sim_alloc(s->d_arena, largest + 16, "the assembly's arena"))) return a;
         s->arena_cap = largest;
-        if ((a = sim_alloc(&s->d_ctg, tab.size(), "the contig table"))) return a;
-        if ((a = sim_alloc(&s->d_brk_pos, s->brk_pos.size(), "the source-locus breakpoints"))) return a;
-        if ((a = sim_alloc(&s->d_brk_src, s->brk_src.size(), "the source-locus breakpoints"))) return a;
-        if (!tab.empty()) SCHK(hipMemcpy(s->d_ctg, tab.data(), tab.size() * sizeof(SimContig), hipMemcpyHostToDevice));
+        if ((a = sim_alloc(s->d_ctg, tab.size(), "the contig table"))) return a;
+        if ((a = sim_alloc(s->d_brk_pos, s->brk_pos.size(), "the source-locus breakpoints"))) return a;
+        if ((a = sim_alloc(s->d_brk_src, s->brk_src.size(), "the source-locus breakpoints"))) return a;
+        if (!tab.empty()) DEVCHK(hipMemcpy(s->d_ctg, tab.data(), tab.size() * sizeof(SimContig), hipMemcpyHostToDevice));
         if (!s->brk_pos.empty()) {
-            SCHK(hipMemcpy(s->d_brk_pos, s->brk_pos.data(), s->brk_pos.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-            SCHK(hipMemcpy(s->d_brk_src, s->brk_src.data(), s->brk_src.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            DEVCHK(hipMemcpy(s->d_brk_pos, s->brk_pos.data(), s->brk_pos.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+            DEVCHK(hipMemcpy(s->d_brk_src, s->brk_src.data(), s->brk_src.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         }
         for (BufSet& b : s->set) {
-            SCHK(hipEventCreateWithFlags(&b.made, hipEventDisableTiming));
-            SCHK(hipEventCreateWithFlags(&b.consumed, hipEventDisableTiming));
+            DEVCHK(b.made.create(hipEventDisableTiming));
+            DEVCHK(b.consumed.create(hipEventDisableTiming));
         }
         return DBTK_OK;
     }();
@@ -472,26 +452,21 @@ dbtk_status_t sim_attach_impl(dbtk_sim_t* s, int device_id) {
     return DBTK_OK;
 }
 
-template <class T> dbtk_status_t sim_reserve(T** p, uint64_t* cap, uint64_t n, const char* what) {
-    if (n <= *cap) return DBTK_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
+template <class T> dbtk_status_t sim_reserve(DevArr<T>& a, uint64_t n, const char* what) {
     const uint64_t want = n + n / 8 + 16;
-    const dbtk_status_t st = sim_alloc(p, want, what);
-    if (st) return st;
-    *cap = want;
-    return DBTK_OK;
+    return sim_nomem(a.reserve(n, want), what, want * sizeof(T));
 }
 
 // the times of the launches that have finished (all of them with `all`)
 dbtk_status_t sim_take_times(dbtk_sim* s, bool all) {
     while (!s->timing.empty()) {
-        if (all) SCHK(hipEventSynchronize(s->timing.front().second));
+        if (all) DEVCHK(hipEventSynchronize(s->timing.front().second));
         else if (hipEventQuery(s->timing.front().second) != hipSuccess) { (void)hipGetLastError(); break; }
         float ms = 0;
-        SCHK(hipEventElapsedTime(&ms, s->timing.front().first, s->timing.front().second));
+        DEVCHK(hipEventElapsedTime(&ms, s->timing.front().first, s->timing.front().second));
         s->tile_ms += ms;
-        s->spare.push_back(s->timing.front().first);
-        s->spare.push_back(s->timing.front().second);
+        s->spare.push_back(std::move(s->timing.front().first));
+        s->spare.push_back(std::move(s->timing.front().second));
         s->timing.pop_front();
     }
     return DBTK_OK;
@@ -504,7 +479,7 @@ dbtk_status_t sim_make_resident(dbtk_sim* s, size_t g) {
     if (c0 == c1) return DBTK_OK;  // (an assembly without a kept contig)
     const uint64_t b0 = s->ctg[c0].off, b1 = s->ctg[c1 - 1].off + s->ctg[c1 - 1].len;
     if (b1 - b0 > s->arena_cap) { set_error("simulated reads: a contig group outgrew the arena"); return DBTK_ERR_HIP; }
-    if (b1 > b0) SCHK(hipMemcpyAsync(s->d_arena, s->bases.data() + b0, b1 - b0, hipMemcpyHostToDevice, s->stream));
+    if (b1 > b0) DEVCHK(hipMemcpyAsync(s->d_arena, s->bases.data() + b0, b1 - b0, hipMemcpyHostToDevice, s->stream));
     s->resident = (int64_t)g;
     s->bytes_uploaded += b1 - b0;
     return DBTK_OK;
@@ -515,22 +490,23 @@ dbtk_status_t sim_batch_impl(dbtk_sim_t* s, uint64_t first, uint64_t npairs, voi
     if (s->device < 0) { set_error("dbtk_sim_batch: dbtk_sim_attach first"); return DBTK_ERR_ARG; }
     if (npairs == 0 || npairs > 0x7FFFFFFFull) { set_error("dbtk_sim_batch: 1 .. 2^31 - 1 pairs in one batch"); return DBTK_ERR_ARG; }
     if (first > s->nfrags || npairs > s->nfrags - first) { set_error("dbtk_sim_batch: fragments " + std::to_string(first) + " + " + std::to_string(npairs) + " of " + std::to_string(s->nfrags)); return DBTK_ERR_ARG; }
-    SCHK(hipSetDevice(s->device));
+    DEVCHK(hipSetDevice(s->device));
     dbtk_status_t st;
     if ((st = sim_take_times(s, false))) return st;
     const int k = s->cur < 0 ? 0 : 1 - s->cur;
     BufSet& B = s->set[k];
     const uint64_t nbytes = npairs * 2 * s->rlen, padded = (nbytes + 15) & ~15ull;
+    const bool grows = padded > B.d_seq.cap() || 2 * npairs + 1 > B.d_off.cap() || npairs > B.d_src.cap();
     if (B.in_use) {
         // the batch aligned from this set two calls ago: its kernels first (in stream order; on the host only where the set must grow)
-        if (padded > B.seq_cap || 2 * npairs + 1 > B.off_cap || npairs > B.src_cap) SCHK(hipEventSynchronize(B.consumed));
-        else SCHK(hipStreamWaitEvent(s->stream, B.consumed, 0));
+        if (grows) DEVCHK(hipEventSynchronize(B.consumed));
+        else DEVCHK(hipStreamWaitEvent(s->stream, B.consumed, 0));
         B.in_use = false;
     }
-    if (padded > B.seq_cap || 2 * npairs + 1 > B.off_cap || npairs > B.src_cap) SCHK(hipStreamSynchronize(s->stream));  // (our own launches into the old buffers)
-    if ((st = sim_reserve(&B.d_seq, &B.seq_cap, padded, "a batch of reads"))) return st;
-    if ((st = sim_reserve(&B.d_off, &B.off_cap, 2 * npairs + 1, "a batch's offsets"))) return st;
-    if ((st = sim_reserve(&B.d_src, &B.src_cap, npairs, "a batch's source loci"))) return st;
+    if (grows) DEVCHK(hipStreamSynchronize(s->stream));  // (our own launches into the old buffers)
+    if ((st = sim_reserve(B.d_seq, padded, "a batch of reads"))) return st;
+    if ((st = sim_reserve(B.d_off, 2 * npairs + 1, "a batch's offsets"))) return st;
+    if ((st = sim_reserve(B.d_src, npairs, "a batch's source loci"))) return st;
     B.npairs = npairs;
     // group by group: the group's bases into the arena (in stream order behind the launches that read the group before), then its pairs
     const size_t ca = host_contig_of(s, first), cz = host_contig_of(s, first + npairs - 1);
@@ -549,21 +525,21 @@ dbtk_status_t sim_batch_impl(dbtk_sim_t* s, uint64_t first, uint64_t npairs, voi
             const uint64_t r0 = a.q0 * 2 * s->rlen, r1 = a.q1 * 2 * s->rlen;
             const uint64_t nchunks = (r1 + 15) / 16 - r0 / 16;
             const uint64_t grid = (nchunks + 255) / 256;  // (at most 2^31 - 1 pairs of 512 bytes: 2^28 workgroups)
-            hipEvent_t e0, e1;
-            for (hipEvent_t* e : {&e0, &e1}) {
-                if (!s->spare.empty()) { *e = s->spare.back(); s->spare.pop_back(); }
-                else SCHK(hipEventCreate(e));
+            DevEvent ev[2];
+            for (DevEvent& e : ev) {
+                if (!s->spare.empty()) { e = std::move(s->spare.back()); s->spare.pop_back(); }
+                else DEVCHK(e.create(hipEventDefault));
             }
-            s->timing.emplace_back(e0, e1);
-            SCHK(hipEventRecord(e0, s->stream));
+            s->timing.emplace_back(std::move(ev[0]), std::move(ev[1]));
+            DEVCHK(hipEventRecord(s->timing.back().first, s->stream));
             hipLaunchKernelGGL(k_sim_tile, dim3((uint32_t)grid), dim3(256), 0, s->stream, a);
-            SCHK(hipGetLastError());
-            SCHK(hipEventRecord(e1, s->stream));
+            DEVCHK(hipGetLastError());
+            DEVCHK(hipEventRecord(s->timing.back().second, s->stream));
             s->bytes_written += r1 - r0;
         }
         if (c1 > cz) break;
     }
-    SCHK(hipEventRecord(B.made, s->stream));
+    DEVCHK(hipEventRecord(B.made, s->stream));
     s->cur = k;
     if (d_seq) *d_seq = B.d_seq;
     if (d_offsets) *d_offsets = B.d_off;
@@ -607,7 +583,7 @@ dbtk_status_t dbtk::sim_group_spans(const dbtk_sim* s, uint32_t g, std::vector<d
 }
 dbtk_status_t dbtk::sim_group_load(dbtk_sim* s, uint32_t g) {
     if (!s || s->device < 0 || (size_t)g + 1 >= s->group_c0.size()) { set_error("sim_group_load: an unattached handle or no such contig group"); return DBTK_ERR_ARG; }
-    SCHK(hipSetDevice(s->device));
+    DEVCHK(hipSetDevice(s->device));
     return sim_make_resident(s, g);
 }
 
@@ -661,8 +637,8 @@ dbtk_status_t dbtk_sim_batch(dbtk_sim_t* s, uint64_t first_frag, uint64_t npairs
 
 dbtk_status_t dbtk_sim_batch_wait(dbtk_sim_t* s) {
     if (!s || s->device < 0) { set_error("dbtk_sim_batch_wait: null or unattached handle"); return DBTK_ERR_ARG; }
-    SCHK(hipSetDevice(s->device));
-    SCHK(hipStreamSynchronize(s->stream));
+    DEVCHK(hipSetDevice(s->device));
+    DEVCHK(hipStreamSynchronize(s->stream));
     return DBTK_OK;
 }
 
@@ -672,7 +648,7 @@ dbtk_status_t dbtk_sim_align(dbtk_sim_t* s, dbtk_ctx_t* ctx, int sync, dbtk_pair
 
 dbtk_status_t dbtk_sim_times(dbtk_sim_t* s, double* tile_ms, uint64_t* bytes_written, uint64_t* bytes_uploaded) {
     if (!s || s->device < 0) { set_error("dbtk_sim_times: null or unattached handle"); return DBTK_ERR_ARG; }
-    SCHK(hipSetDevice(s->device));
+    DEVCHK(hipSetDevice(s->device));
     const dbtk_status_t st = sim_take_times(s, true);
     if (st) return st;
     if (tile_ms) *tile_ms = s->tile_ms;
