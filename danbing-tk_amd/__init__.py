@@ -1129,6 +1129,41 @@ def assoc_covar_basis(lib, covar):
     return Q
 
 
+EXPORTS_ASSOC_PERM = [
+    "dbtk_assoc_perm_api_version", "dbtk_assoc_perm_generate", "dbtk_assoc_perm_set", "dbtk_assoc_perm_seed", "dbtk_assoc_perm_get",
+    "dbtk_assoc_perm_scan_device", "dbtk_assoc_perm_scan_pred", "dbtk_assoc_perm_scan_dosage", "dbtk_assoc_perm_results", "dbtk_assoc_perm_stats",
+    "dbtk_assoc_perm_write", "dbtk_assoc_perm_times",
+]
+
+
+def _bind_assoc_perm(L):
+    dp = C.POINTER(C.c_double)
+    L.dbtk_assoc_perm_api_version.restype = C.c_uint32
+    L.dbtk_assoc_perm_api_version.argtypes = []
+    L.dbtk_assoc_perm_generate.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, u32p]
+    L.dbtk_assoc_perm_set.argtypes = [C.c_void_p, C.c_uint64, u32p]
+    L.dbtk_assoc_perm_seed.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
+    L.dbtk_assoc_perm_get.argtypes = [C.c_void_p, u64p, u32p, C.c_uint64]
+    L.dbtk_assoc_perm_scan_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, u32p, C.c_double]
+    L.dbtk_assoc_perm_scan_pred.argtypes = [C.c_void_p, C.c_void_p, C.c_double]
+    L.dbtk_assoc_perm_scan_dosage.argtypes = [C.c_void_p, C.c_void_p, C.c_double]
+    L.dbtk_assoc_perm_results.argtypes = [C.c_void_p, C.POINTER(abi.AssocPermResult)]
+    L.dbtk_assoc_perm_stats.argtypes = [C.c_void_p, C.c_uint64, dp]
+    L.dbtk_assoc_perm_write.argtypes = [C.c_void_p, C.c_char_p]
+    L.dbtk_assoc_perm_times.argtypes = [C.c_void_p, dp]
+    if L.dbtk_assoc_perm_api_version() != abi.ASSOC_PERM_API_VERSION:
+        raise RuntimeError("libdbtk_hip.so: dbtk_assoc_perm.h version mismatch")
+
+
+def assoc_perm_generate(lib, n, B, seed):
+    """dbtk_assoc_perm_generate: perm[B][n] uint32, permutations 1 .. B of the splitmix64 stream of `seed`; no device."""
+    _bind_assoc_perm(lib.L)
+    perm = np.zeros((int(B), int(n)), np.uint32)
+    lib._chk(lib.L.dbtk_assoc_perm_generate(int(n), int(B), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(perm, u32p) if perm.size else None))
+    return perm
+
+
+ASSOC_PERM_FIELDS = ("n_perm", "n_ge", "row", "r2", "p_perm", "q_perm")  # dbtk_assoc_perm_result_t
 ASSOC_BEST_FIELDS = ("n_tests", "skipped", "row", "locus", "r", "se", "t", "p", "p_bonf", "q")  # dbtk_assoc_best_t
 
 
@@ -1192,6 +1227,71 @@ class Assoc:
 
     def scan_dosage(self, dosage, p_threshold=-1.0):
         self._lib._chk(self._lib.L.dbtk_assoc_scan_dosage(self.h, dosage.h, float(p_threshold)))
+
+    def set_permutations(self, B, seed=None, perms=None):
+        """dbtk_assoc_perm_seed (B permutations from `seed`, 1 when neither is given) or dbtk_assoc_perm_set (perms[B][n] over the positions
+        0 .. n - 1 of the mask in ascending sample order); B == 0 removes the permutations."""
+        _bind_assoc_perm(self._lib.L)
+        if perms is not None:
+            assert seed is None
+            perms = np.ascontiguousarray(perms, np.uint32).reshape(int(B), self.n) if int(B) else np.zeros((0, self.n), np.uint32)
+            self._lib._chk(self._lib.L.dbtk_assoc_perm_set(self.h, int(B), _ptr(perms, u32p) if perms.size else None))
+        elif not int(B):
+            self._lib._chk(self._lib.L.dbtk_assoc_perm_set(self.h, 0, None))
+        else:
+            self._lib._chk(self._lib.L.dbtk_assoc_perm_seed(self.h, int(B), (1 if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF))
+
+    def permutations(self):
+        """perm[B][n] as the handle holds them"""
+        _bind_assoc_perm(self._lib.L)
+        B = C.c_uint64()
+        self._lib._chk(self._lib.L.dbtk_assoc_perm_get(self.h, C.byref(B), None, 0))
+        perm = np.zeros((B.value, self.n), np.uint32)
+        if perm.size:
+            self._lib._chk(self._lib.L.dbtk_assoc_perm_get(self.h, C.byref(B), _ptr(perm, u32p), B.value))
+        return perm
+
+    def perm_scan_device(self, d_rows, nrows, nk_cum=None, p_threshold=-1.0):
+        """scan_device, then the permutation pass over the same rows"""
+        _bind_assoc_perm(self._lib.L)
+        ptr = d_rows.data_ptr() if hasattr(d_rows, "data_ptr") else d_rows.value if isinstance(d_rows, C.c_void_p) else int(d_rows)
+        nkc = np.ascontiguousarray(nk_cum, np.uint32) if nk_cum is not None else None
+        self._lib._chk(self._lib.L.dbtk_assoc_perm_scan_device(self.h, C.c_void_p(ptr), int(nrows), len(nkc) if nkc is not None else 0, _ptr(nkc, u32p), float(p_threshold)))
+
+    def perm_scan_pred(self, pred, p_threshold=-1.0):
+        _bind_assoc_perm(self._lib.L)
+        self._lib._chk(self._lib.L.dbtk_assoc_perm_scan_pred(self.h, pred.h, float(p_threshold)))
+
+    def perm_scan_dosage(self, dosage, p_threshold=-1.0):
+        _bind_assoc_perm(self._lib.L)
+        self._lib._chk(self._lib.L.dbtk_assoc_perm_scan_dosage(self.h, dosage.h, float(p_threshold)))
+
+    def perm_results(self):
+        """per phenotype a dict of dbtk_assoc_perm_result_t"""
+        _bind_assoc_perm(self._lib.L)
+        arr = (abi.AssocPermResult * self.P)()
+        self._lib._chk(self._lib.L.dbtk_assoc_perm_results(self.h, arr))
+        return [{f: getattr(arr[p], f) for f in ASSOC_PERM_FIELDS} for p in range(self.P)]
+
+    def perm_stats(self, p):
+        """T[B + 1] of phenotype p: the observed maximum of r^2 and those of the B permutations"""
+        _bind_assoc_perm(self._lib.L)
+        B = C.c_uint64()
+        self._lib._chk(self._lib.L.dbtk_assoc_perm_get(self.h, C.byref(B), None, 0))
+        T = np.zeros(B.value + 1, np.float64)
+        self._lib._chk(self._lib.L.dbtk_assoc_perm_stats(self.h, int(p), T.ctypes.data_as(C.POINTER(C.c_double))))
+        return T
+
+    def perm_write(self, prefix):
+        _bind_assoc_perm(self._lib.L)
+        self._lib._chk(self._lib.L.dbtk_assoc_perm_write(self.h, os.fsencode(prefix)))
+
+    def perm_times(self):
+        """(milliseconds in k_assoc_perm, milliseconds in the host fold) of the last permutation scan"""
+        _bind_assoc_perm(self._lib.L)
+        ms = (C.c_double * 2)()
+        self._lib._chk(self._lib.L.dbtk_assoc_perm_times(self.h, ms))
+        return float(ms[0]), float(ms[1])
 
     def best(self):
         """per phenotype a dict of dbtk_assoc_best_t"""

@@ -16,6 +16,8 @@ ASSOC_NONE = 0xFFFFFFFF  # row / locus of a phenotype without tests
 ASSOC_COVAR_API_VERSION = 1  # include/dbtk_assoc_covar.h: DBTK_ASSOC_COVAR_API_VERSION
 ASSOC_COVAR_MAX = 128  # covariates of a table at most
 ASSOC_COVAR_COLLINEAR = 1e-6  # the residual share at or below which a covariate, a row or a phenotype counts as explained
+ASSOC_PERM_API_VERSION = 1  # include/dbtk_assoc_perm.h: DBTK_ASSOC_PERM_API_VERSION
+ASSOC_PERM_MAX = 1000000  # permutations of a handle at most
 BUBBLES_LOG, BUBBLES_TABLE = 1, 2  # params.bubbles: event log replayed on the host (reference order) | counts in a device table
 ALN_TEXT = 4  # params.aln | ALN_TEXT: alignment records in text form (dbtk_ctx_aln_text)
 THREAD_CAP = 384
@@ -133,6 +135,12 @@ class AssocBest(C.Structure):
     """include/dbtk_assoc.h: dbtk_assoc_best_t"""
     _fields_ = [("n_tests", C.c_uint64), ("skipped", C.c_uint64), ("row", C.c_uint32), ("locus", C.c_uint32)] + \
                [(n, C.c_double) for n in ("r", "se", "t", "p", "p_bonf", "q")]
+
+
+class AssocPermResult(C.Structure):
+    """include/dbtk_assoc_perm.h: dbtk_assoc_perm_result_t"""
+    _fields_ = [("n_perm", C.c_uint64), ("n_ge", C.c_uint64), ("row", C.c_uint32), ("pad", C.c_uint32)] + \
+               [(n, C.c_double) for n in ("r2", "p_perm", "q_perm")]
 
 
 class AssocHit(C.Structure):

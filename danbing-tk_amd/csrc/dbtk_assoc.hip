@@ -1,5 +1,6 @@
 // dbtk_assoc.hip — the association scan (include/dbtk_assoc.h) and its covariates (include/dbtk_assoc_covar.h): the phenotype centring,
-// the phenotypes' projections on the covariate basis, the scan kernel, the handle and the host fold.
+// the phenotypes' projections on the covariate basis, the scan kernel, the handle and the host fold.  The permutation pass
+// (include/dbtk_assoc_perm.h) is dbtk_assoc_perm_dev.h, included at the end of this file.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -15,6 +16,7 @@
 
 #include "../../include/dbtk_assoc.h"
 #include "../../include/dbtk_assoc_covar.h"
+#include "../../include/dbtk_assoc_perm.h"
 #include "dbtk_assoc_covar_host.h"
 #include "dbtk_assoc_host.h"
 #include "dbtk_dev.h"
@@ -353,6 +355,10 @@ struct dbtk_assoc {
     // the device side (destroyed last to first: the tables from d_sidx on, then the events, the stream behind them all)
     DevStream stream;
     DevEvent ev[2];
+    DevEvent pev[2];                  // around the permutation kernel (made with the first permutations)
+    DevArr<double> d_yres;            // the permutations (dbtk_assoc_perm.h, dbtk_assoc_perm_dev.h): with covariates the phenotypes' residuals,
+    DevArr<unsigned long long> d_T;   // the P (B + 1) maxima,
+    DevArr<uint32_t> d_perm;          // the table, the identity in front
     DevArr<double> d_syyr, d_bt, d_Q;
     DevArr<AsCand> d_cand;            // per scan, regrown (and d_items)
     DevArr<AsItem> d_items;
@@ -366,6 +372,14 @@ struct dbtk_assoc {
     std::vector<dbtk_assoc_best_t> best;
     std::vector<dbtk_assoc_hit_t> hits;
     double ms[2] = {0, 0};
+    std::vector<AsItem> items;        // its work items, which the permutation pass takes again
+    // the permutations and the permutation scan made last
+    uint64_t B = 0;
+    std::vector<uint32_t> perm;
+    bool perm_done = false;
+    std::vector<double> T;
+    std::vector<dbtk_assoc_perm_result_t> pres;
+    double pms[2] = {0, 0};
 };
 
 namespace {
@@ -482,7 +496,7 @@ dbtk_status_t assoc_set_pairs_impl(dbtk_assoc_t* h, uint64_t ntr, const uint64_t
 
 dbtk_status_t assoc_scan_impl(dbtk_assoc_t* h, const float* d_rows, uint64_t nrows, uint64_t ntr, const uint32_t* nk_cum, double p_threshold) {
     if (!h || !d_rows) { set_error("null argument"); return DBTK_ERR_ARG; }
-    h->scanned = false;
+    h->scanned = false; h->perm_done = false;
     if (std::isnan(p_threshold)) { set_error("dbtk_assoc_scan: p_threshold is not a number"); return DBTK_ERR_ARG; }
     if (!nrows || nrows > 0xFFFFFFFEull) { set_error("dbtk_assoc_scan: " + std::to_string(nrows) + " rows (1 .. 2^32 - 2)"); return DBTK_ERR_ARG; }
     if (h->pairs && ntr != h->ntr) { set_error("dbtk_assoc_scan: the pair list is over " + std::to_string(h->ntr) + " loci, the matrix has " + std::to_string(ntr)); return DBTK_ERR_ARG; }
@@ -593,13 +607,14 @@ dbtk_status_t assoc_scan_impl(dbtk_assoc_t* h, const float* d_rows, uint64_t nro
         }
     }
     h->ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    h->items.swap(items);
     h->scanned = true;
     return st;
 }
 
 dbtk_status_t assoc_covar_set_impl(dbtk_assoc_t* h, uint64_t q, const double* covar, const char* const* names) {
     if (!h) { set_error("null argument"); return DBTK_ERR_ARG; }
-    h->scanned = false;
+    h->scanned = false; h->perm_done = false;
     if (!q) {
         DEVCHK(hipSetDevice(h->device));
         DEVCHK(hipStreamSynchronize(h->stream));
@@ -778,3 +793,5 @@ dbtk_status_t dbtk_assoc_r2_threshold(double p_threshold, uint64_t n, double* r2
 }
 
 }  // extern "C"
+
+#include "dbtk_assoc_perm_dev.h"  // the permutation pass: dbtk_assoc_perm_*

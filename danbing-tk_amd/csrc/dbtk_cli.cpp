@@ -202,7 +202,9 @@ void usage() {
             "                         with --cohort and --pred or --dosage: after the last sample, what danbing-tk-pred --assoc makes of the\n"
             "                         matrix (with --pred) or of the dosage values: OUTPREF.assoc.best.tsv, with --assoc-p OUTPREF.assoc.hits.tsv;\n"
             "                         --assoc-covar regresses COVAR.tsv's covariates out of rows and phenotypes on the device (partial\n"
-            "                         correlation, n - 2 - q degrees of freedom); the group may be repeated, each with its own covariates\n"
+            "                         correlation, n - 2 - q degrees of freedom); the group may be repeated, each with its own covariates;\n"
+            "                         [--assoc-perm <B> [--assoc-seed <S>]] adds OUTPREF.assoc.perm.tsv: permutation p-values of the best\n"
+            "                         r^2 per phenotype from B permutations on the device (seed S, default 1)\n"
             "Developer:\n"
             "  -s <1|2>  -e <1|2>  -v <INT>  -g|-gc|-gcc <INT> [INT]  -a  -ae  -tb  -ik  -t <INT>  -m <FILE>  -au\n\n");
 }
@@ -2234,7 +2236,7 @@ int main(int argc, char* argv[]) {
             std::string err;
             if (dbtk_pred_matrix(pred, mat.data())) die_assert(dbtk_last_error());
             if (!dbtk_pred_io::save_matrix(o.pred[1], mat.data(), ns, ntrk, stderr, &err)) die_assert(err);
-            auto scan = [&](dbtk_assoc_t* h, double p) { return dbtk_assoc_scan_pred(h, pred, p); };
+            auto scan = [&](dbtk_assoc_t* h, double p, bool perm) { return perm ? dbtk_assoc_perm_scan_pred(h, pred, p) : dbtk_assoc_scan_pred(h, pred, p); };
             if (!dbtk_assoc_cli::run(&o.assoc, true, dev_of(0), ns, ntr, scan, stderr, &err)) die_assert(err);
             if (dbtk_pred_correct(pred)) die_assert(dbtk_last_error());
             if (dbtk_pred_matrix(pred, mat.data())) die_assert(dbtk_last_error());
@@ -2252,7 +2254,7 @@ int main(int argc, char* argv[]) {
             if (!dbtk_pred_io::save_bias_tsv(o.dosage[1], tab.data(), ns, ntr, stderr, &err)) die_assert(err);
             if (dbtk_dosage_bias(dosage, tab.data())) die_assert(dbtk_last_error());
             if (!dbtk_pred_io::save_bias_tsv(o.dosage[2], tab.data(), ns, ntr, stderr, &err)) die_assert(err);
-            if (!pred && !dbtk_assoc_cli::run(&o.assoc, false, dev_of(0), ns, ntr, [&](dbtk_assoc_t* h, double p) { return dbtk_assoc_scan_dosage(h, dosage, p); }, stderr, &err)) die_assert(err);
+            if (!pred && !dbtk_assoc_cli::run(&o.assoc, false, dev_of(0), ns, ntr, [&](dbtk_assoc_t* h, double p, bool perm) { return perm ? dbtk_assoc_perm_scan_dosage(h, dosage, p) : dbtk_assoc_scan_dosage(h, dosage, p); }, stderr, &err)) die_assert(err);
         }
         if (kms) {
             const uint64_t ns = samples.size(), ntr = dbtk_dosage_ntr(kms);

@@ -5,7 +5,7 @@
 // The second form makes the per-locus tables alone (dbtk_dosage_*): the matrix is never allocated, in HBM or on the host.
 //   danbing-tk-pred --window-rows R | --window-bytes N <INPUT1> <INPUT2> <OUTPUT1> <OUTPUT2> <OUTPUT3>
 // The first form for a cohort whose matrix fits neither: whole loci of at most R k-mers at a time (windowed()), the same three files.
-//   danbing-tk-pred --assoc PHENO.tsv OUTPREF [--assoc-covar COVAR.tsv] [--assoc-pairs PAIRS.tsv] [--assoc-p X] [--assoc-raw] ... <either of the first two forms>
+//   danbing-tk-pred --assoc PHENO.tsv OUTPREF [--assoc-covar COVAR.tsv] [--assoc-pairs PAIRS.tsv] [--assoc-p X] [--assoc-raw] [--assoc-perm B [--assoc-seed S]] ... <either of the first two forms>
 // The association scan of the resident matrix or dosage table (dbtk_assoc_cli.h); the other outputs are unchanged by it.
 #include <fcntl.h>
 #include <stdint.h>
@@ -97,7 +97,7 @@ static int dosage_tables(int device, const std::string& finGtMeta, const std::st
         if (dbtk_dosage_kms(D, kms.data())) die(dbtk_last_error());
         if (!dbtk_pred_io::save_kms(foutKms, kms.data(), ns, ntr, stdout, &err)) die(err);
     }
-    if (!dbtk_assoc_cli::run(&assoc, false, device, ns, ntr, [&](dbtk_assoc_t* h, double p) { return dbtk_assoc_scan_dosage(h, D, p); }, stdout, &err)) die(err);
+    if (!dbtk_assoc_cli::run(&assoc, false, device, ns, ntr, [&](dbtk_assoc_t* h, double p, bool perm) { return perm ? dbtk_assoc_perm_scan_dosage(h, D, p) : dbtk_assoc_scan_dosage(h, D, p); }, stdout, &err)) die(err);
     dbtk_dosage_free(D);
     return 0;
 }
@@ -255,7 +255,7 @@ int main(int argc, char** argv) {
     printf("normalizaing read depth\n");
     if (dbtk_pred_matrix(P, mat.data())) die(dbtk_last_error());
     save_matrix(foutRaw, mat.data(), ns, nk);
-    auto scan = [&](dbtk_assoc_t* h, double p) { return dbtk_assoc_scan_pred(h, P, p); };
+    auto scan = [&](dbtk_assoc_t* h, double p, bool perm) { return perm ? dbtk_assoc_perm_scan_pred(h, P, p) : dbtk_assoc_scan_pred(h, P, p); };
     {
         std::string err;
         if (!dbtk_assoc_cli::run(&assoc, true, device, ns, ntr, scan, stdout, &err)) die(err);

@@ -8,6 +8,14 @@ writes G: 8 bytes per entry).
     python tools/assoc_bench.py [--ns 256,879] [--ppl 5,20] [--ntr 20000] [--kpl 184] [--covar 0,10,60]
 --covar Q: the same scans with Q covariates regressed out on the device (include/dbtk_assoc_covar.h; 0: none); the multiply-add count
 then has Q more dot products per row, (ppl + 2 + Q) * nk * n, and Q more per (row, phenotype) pair.
+    python tools/assoc_bench.py --perm 1000 [--ns 256,879] [--ppl 5] [--covar 0,60] [--reps 7]
+--perm B: behind each scan, the permutation pass (include/dbtk_assoc_perm.h) with B seeded permutations: k_assoc_perm's HIP-event time
+(median of the runs after 2 warm-ups) and its FP64 multiply-add rate, ppl * (B + 1) * nk * n multiply-adds.
+    python tools/assoc_bench.py --perm-yardstick [--yardstick-lib PATH] [--perm 100] [--ns 256,879] [--ntr 1000] [--ppl 5]
+--perm-yardstick: k_assoc_perm against k_assoc_scan fed the SAME permuted vectors as explicit phenotypes through a pair list, on one
+random matrix in device memory, at equal (row, column) work; PATH is the library whose scan is the yardstick (a build of the commit
+before the permutation pass; default: this library's own scan).  Also k_assoc_perm with B identity permutations: the same multiply-adds
+with a gather that is a plain read, which tells what the scattered gather costs.
     python tools/assoc_bench.py --workflow [--ns 256] [--ntr 2000]
 --workflow: what the scan replaces.  The corrected matrix is copied to the host and written to /dev/shm in danbing-tk-pred's layout, read
 back, and a 16-thread numpy loop (one locus per task, the formulas of tests/assoc_model.py without the p-values) makes the same r; beside
@@ -58,7 +66,7 @@ def tables(ns, ntr, ppl, seed=2):
     return pheno, off, idx
 
 
-def rates(lib, nss, ppls, ntr, kpl, covars=(0,)):
+def rates(lib, nss, ppls, ntr, kpl, covars=(0,), perm=0, reps=7):
     for ns in nss:
         P, nk_cum, nk = cohort(lib, ns, ntr, kpl)
         cor_ms = P.times()[2]
@@ -81,8 +89,69 @@ def rates(lib, nss, ppls, ntr, kpl, covars=(0,)):
                 print(f"  {ppl:3d} phenotypes per locus, {q:3d} covariates: k_assoc_scan {k:.3f} ms (min {min(ms[2:]):.3f}, max {max(ms[2:]):.3f}) = {gbytes / k / 1e9:.2f} TB/s of G "
                       f"({gbytes / k / 1e9 / 8:.1%} of 8 TB/s), {fma / k / 1e9:.2f} T FP64 multiply-adds/s; {k / cor_ms:.2f} x k_pred_correct; host fold {np.median(fold[2:]):.1f} ms; "
                       f"{len(A.hits())} hits", flush=True)
+                if perm:
+                    A.set_permutations(perm, seed=1)
+                    pms = []
+                    for _ in range(reps):
+                        A.perm_scan_pred(P)
+                        pms.append(A.perm_times())
+                    kp = float(np.median([t[0] for t in pms[2:]]))
+                    pfma = float(ppl) * (perm + 1) * nk * ns
+                    print(f"      {perm} permutations: k_assoc_perm {kp:.1f} ms (min {min(t[0] for t in pms[2:]):.1f}, max {max(t[0] for t in pms[2:]):.1f}) = "
+                          f"{pfma / kp / 1e9:.2f} T FP64 multiply-adds/s; host fold {np.median([t[1] for t in pms[2:]]):.1f} ms; "
+                          f"{sum(r['n_ge'] == 0 for r in A.perm_results())} of {len(pheno)} phenotypes with p_perm = 1 / (B + 1)", flush=True)
+                    A.set_permutations(0)
             A.close()
         P.close()
+
+
+def perm_yardstick(lib, ylib, nss, ntr, kpl, ppl, B, reps=7):
+    import torch
+
+    nk = ntr * kpl
+    nk_cum = (np.arange(1, ntr + 1, dtype=np.uint64) * kpl).astype(np.uint32)
+    for ns in nss:
+        g = torch.Generator(device="cuda").manual_seed(5)
+        G = torch.rand((nk, ns), dtype=torch.float32, device="cuda", generator=g) * 3.0 + 0.5
+        torch.cuda.synchronize()
+        pheno, off, idx = tables(ns, ntr, ppl)
+        npheno = len(pheno)
+        perms = pkg.assoc_perm_generate(lib, ns, B, 1)
+        # the yardstick: every (phenotype, b) an explicit phenotype, slot 0 the identity, the loci's lists widened to match
+        explicit = np.empty((npheno * (B + 1), ns))
+        explicit[0::B + 1] = pheno
+        for b in range(B):
+            explicit[b + 1::B + 1] = pheno[:, perms[b]]
+        eidx = (idx.astype(np.uint64)[:, None] * (B + 1) + np.arange(B + 1, dtype=np.uint64)[None, :]).astype(np.uint32).ravel()
+        eoff = off * (B + 1)
+        E = pkg.Assoc(ylib, ns, np.arange(ns), explicit)
+        E.set_pairs(eoff, eidx)
+        A = pkg.Assoc(lib, ns, np.arange(ns), pheno)
+        A.set_pairs(off, idx)
+
+        def timed(call, read):
+            ms = []
+            for _ in range(reps):
+                call()
+                ms.append(read())
+            return float(np.median(ms[2:])), min(ms[2:]), max(ms[2:])
+
+        ys = timed(lambda: E.scan_device(G, nk, nk_cum=nk_cum), lambda: E.times()[0])
+        A.set_permutations(B, perms=perms)
+        ps = timed(lambda: A.perm_scan_device(G, nk, nk_cum=nk_cum), lambda: A.perm_times()[0])
+        eb = np.array([b["r"] ** 2 for b in E.best()]).reshape(npheno, B + 1)
+        T = np.array([A.perm_stats(p) for p in range(0, npheno, max(1, npheno // 50))])
+        worst = float(np.abs(T - eb[::max(1, npheno // 50)]).max())
+        A.set_permutations(B, perms=np.tile(np.arange(ns, dtype=np.uint32), (B, 1)))
+        ident = timed(lambda: A.perm_scan_device(G, nk, nk_cum=nk_cum), lambda: A.perm_times()[0])
+        fma = float(ppl) * (B + 1) * nk * ns
+        print(f"{ns} samples x {nk} rows ({ntr} loci x {kpl}), {ppl} phenotypes per locus, B = {B}: {ppl * (B + 1)} columns per row\n"
+              f"  k_assoc_scan fed the permuted vectors ({'the yardstick library' if ylib is not lib else 'this library'}): {ys[0]:.2f} ms (min {ys[1]:.2f}, max {ys[2]:.2f}) = {fma / ys[0] / 1e9:.2f} T multiply-adds/s\n"
+              f"  k_assoc_perm: {ps[0]:.2f} ms (min {ps[1]:.2f}, max {ps[2]:.2f}) = {fma / ps[0] / 1e9:.2f} T multiply-adds/s; {ys[0] / ps[0]:.2f} x the yardstick's speed; largest |T - r^2 of the scan| {worst:.2e}\n"
+              f"  k_assoc_perm with identity permutations (the gather a plain read): {ident[0]:.2f} ms: the scattered gather costs {(ps[0] - ident[0]) / ps[0]:.1%} of the kernel's time", flush=True)
+        A.close()
+        E.close()
+        del G
 
 
 def workflow(lib, ns, ntr, kpl, ppl=5):
@@ -140,13 +209,20 @@ def main():
     ap.add_argument("--kpl", type=int, default=184)
     ap.add_argument("--covar", default="0")
     ap.add_argument("--workflow", action="store_true")
+    ap.add_argument("--perm", type=int, default=0)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--perm-yardstick", action="store_true")
+    ap.add_argument("--yardstick-lib", default=None)
     a = ap.parse_args()
     import torch  # noqa: F401  (before libdbtk_hip.so is loaded, so that both bind to the one HIP runtime: INTEGRATION.md 5)
     lib = pkg.Dbtk()
-    if a.workflow:
+    if a.perm_yardstick:
+        ylib = pkg.Dbtk(a.yardstick_lib) if a.yardstick_lib else lib
+        perm_yardstick(lib, ylib, [int(v) for v in (a.ns or "256,879").split(",")], a.ntr or 1000, a.kpl, int(a.ppl.split(",")[0]), a.perm or 100, a.reps)
+    elif a.workflow:
         workflow(lib, int((a.ns or "256").split(",")[0]), a.ntr or 2000, a.kpl)
     else:
-        rates(lib, [int(v) for v in (a.ns or "256,879").split(",")], [int(v) for v in a.ppl.split(",")], a.ntr or 20000, a.kpl, [int(v) for v in a.covar.split(",")])
+        rates(lib, [int(v) for v in (a.ns or "256,879").split(",")], [int(v) for v in a.ppl.split(",")], a.ntr or 20000, a.kpl, [int(v) for v in a.covar.split(",")], a.perm, a.reps)
 
 
 if __name__ == "__main__":
